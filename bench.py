@@ -22,6 +22,13 @@ reported. ``value`` = sum over trials of (batch x steps) / max_time (samples are
 counted once per trial, not per replica -- SURVEY.md section 6 metric).
 
 Run: python bench.py --gpus N --steps K --warmup W   (N>1 via torch.distributed.run)
+
+A plain run sets up, warms up, times the K steps and prints the result line.
+``--dump-outputs DIR`` also writes the training state the last timed step left
+(``DIR/<name>.npy``; data, weights and sampler are seeded, so the same
+arguments give the same inputs in every run and two builds can be compared
+array for array). ``--full`` is reserved for measurements and checks that need
+runs of their own; the benchmark has none today.
 """
 
 from __future__ import annotations
@@ -68,6 +75,33 @@ def _timing_barrier(world, dev):
     return global_barrier, "gloo"
 
 
+DUMP_BUDGET_BYTES = 60 * 2 ** 20  # --dump-outputs: every trial's arrays together stay under 64 MB
+
+
+def _dump_outputs(out_dir, trainer, tid, ntrials, steps):
+    """Write what ``train_steps`` left a caller of trial ``tid`` after the last
+    timed step: the parameter arena, both Adam moments, and the losses of the
+    timed steps (oldest first, the last step's loss last; at most the length of
+    the loss ring). One trial writes ``<name>.npy``, several write
+    ``trial<tid>_<name>.npy``. An arena larger than its share of the budget is
+    stored as a fixed seeded sample of its elements (the same indices every run)."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    prefix = f"trial{tid}_" if ntrials > 1 else ""
+    cap = DUMP_BUDGET_BYTES // (ntrials * 3) // 4
+    for name in ("params", "exp_avg", "exp_avg_sq"):
+        arr = getattr(trainer, name).detach().to("cpu", torch.float32).numpy()
+        if arr.size > cap:
+            arr = arr[np.sort(np.random.default_rng(0).choice(arr.size, size=cap, replace=False))]
+        np.save(os.path.join(out_dir, prefix + name + ".npy"), arr)
+    hist = trainer.loss_history()
+    step = trainer.read_state()["step"]
+    n = min(steps, len(hist), step)
+    loss = np.asarray([hist[(step - n + i) % len(hist)] for i in range(n)], np.float32)
+    np.save(os.path.join(out_dir, prefix + "loss.npy"), loss)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -87,6 +121,13 @@ def main(argv=None):
     ap.add_argument("--trials-per-gpu", type=int, default=1,
                     help="trial packing: T concurrent trials per single-rank group (one HIP stream each); "
                          "the headline config is T=1 (K = N trials)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write every trial's training state as the last timed step left "
+                         "it (params, exp_avg, exp_avg_sq, and the losses of the timed steps) to DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run whatever the benchmark measures or checks beyond the headline figure in runs "
+                         "of its own; there is none at present: set-up, warm-up, the timed steps and the state "
+                         "checks on the result line are all a plain run does, so the flag changes nothing yet")
     a = ap.parse_args(argv)
 
     from multidisttorch_amd.runtime.env import apply_cu_split
@@ -234,6 +275,9 @@ def main(argv=None):
         if msg:
             health.append(msg)
             ok = False
+    if a.dump_outputs and trainers and grank == 0:  # replicas of a trial hold the same state: one writes
+        for t, tr in enumerate(trainers):
+            _dump_outputs(a.dump_outputs, tr, gid * T + t, K * T, a.steps)
     # intra-group data parallelism: every replica of a trial must hold bitwise the
     # same parameters after the timed steps (the averaged gradient is identical on
     # every member; tests/gpu/conv_ddp_worker.py asserts the same)
