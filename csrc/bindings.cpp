@@ -39,7 +39,9 @@ PYBIND11_MODULE(_C, m) {
       .def("bucket_split", &mdt::MlpVaeEngine::bucket_split)
       .def("set_hparams", &mdt::MlpVaeEngine::set_hparams, py::arg("lr"), py::arg("beta1"),
            py::arg("beta2"), py::arg("eps"), py::arg("weight_decay"), py::arg("kl_beta"),
-           py::arg("grad_scale"), py::arg("seed"), py::arg("decoupled_wd") = false)
+           py::arg("grad_scale"), py::arg("seed"), py::arg("decoupled_wd") = false,
+           py::arg("lr_warmup_steps") = 0, py::arg("lr_decay") = 0, py::arg("lr_decay_steps") = 0,
+           py::arg("lr_min_ratio") = 0.0, py::arg("kl_anneal_steps") = 0)
       .def("set_cursor", &mdt::MlpVaeEngine::set_cursor)
       .def("set_step", &mdt::MlpVaeEngine::set_step)
       .def("reset_loss", &mdt::MlpVaeEngine::reset_loss)

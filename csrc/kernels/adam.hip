@@ -38,7 +38,7 @@ __global__ void __launch_bounds__(256) loss_finalize(const HParams* hp, TrainSta
   __syncthreads();
   const float kld = block_sum(sk, scratch);
   if (threadIdx.x == 0) {
-    const float loss = bce + hp->kl_beta * kld;
+    const float loss = bce + st->kl_t * kld;  // the step's KL weight (eval states: the full beta)
     st->loss_hist[(st->step - 1) % kLossHist] = loss;
     st->epoch_loss += (double)loss;
     st->epoch_count += 1.0;

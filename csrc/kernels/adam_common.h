@@ -19,10 +19,11 @@ __device__ __forceinline__ AdamC adam_consts_block(const TrainState* st, const H
     const double bc1 = 1.0 - st->b1pow;
     const double bc2 = 1.0 - st->b2pow;
     AdamC c;
-    c.step_size = (float)(hp->lr_d / bc1);
+    const double lr_t = st->lr_t;  // lr_d * f_lr(t), recorded by the thread that advanced the step
+    c.step_size = (float)(lr_t / bc1);
     c.bc2s = (float)sqrt(bc2);
     c.b1 = hp->beta1; c.b2 = hp->beta2; c.eps = hp->eps; c.wd = hp->weight_decay;
-    c.gs = hp->grad_scale; c.lr = hp->lr; c.decoupled = hp->decoupled_wd;
+    c.gs = hp->grad_scale; c.lr = (float)lr_t; c.decoupled = hp->decoupled_wd;
     *sh = c;
   }
   __syncthreads();
@@ -30,7 +31,7 @@ __device__ __forceinline__ AdamC adam_consts_block(const TrainState* st, const H
 }
 
 // Same constants when the step state was advanced earlier IN THIS LAUNCH by
-// another workgroup (dependent jobs_multi_k launch): beta^t through sc1 vector
+// another workgroup (dependent jobs_multi_k launch): beta^t and lr_t through sc1 vector
 // loads, so neither this CU's L1 nor the scalar cache can serve an old copy.
 __device__ __forceinline__ AdamC adam_consts_block_sc1(const TrainState* st, const HParams* hp, AdamC* sh) {
   if (threadIdx.x == 0) {
@@ -40,11 +41,13 @@ __device__ __forceinline__ AdamC adam_consts_block_sc1(const TrainState* st, con
         __builtin_bit_cast(double, __hip_atomic_load((gu64*)&s->b1pow, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
     const double b2pow =
         __builtin_bit_cast(double, __hip_atomic_load((gu64*)&s->b2pow, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+    const double lr_t =
+        __builtin_bit_cast(double, __hip_atomic_load((gu64*)&s->lr_t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
     AdamC c;
-    c.step_size = (float)(hp->lr_d / (1.0 - b1pow));
+    c.step_size = (float)(lr_t / (1.0 - b1pow));
     c.bc2s = (float)sqrt(1.0 - b2pow);
     c.b1 = hp->beta1; c.b2 = hp->beta2; c.eps = hp->eps; c.wd = hp->weight_decay;
-    c.gs = hp->grad_scale; c.lr = hp->lr; c.decoupled = hp->decoupled_wd;
+    c.gs = hp->grad_scale; c.lr = (float)lr_t; c.decoupled = hp->decoupled_wd;
     *sh = c;
   }
   __syncthreads();

@@ -95,7 +95,9 @@ struct FwdArgs {
 
 struct BwdArgs {
   Weights w;
-  const HParams* hp;
+  // KL weight of the step being computed: TrainState.kl_next when the step is
+  // advanced after this launch (t = step + 1), HParams.kl_beta with no state
+  const float* klw;
   const float* mulv;
   const float* eps;
   const __bf16* a1;
@@ -983,7 +985,7 @@ __device__ __forceinline__ void bwd_body(const BwdArgs& a, uint8_t* lds, int n) 
 #pragma unroll
     for (int i = 0; i < 8; ++i) dz1 += DZR[256 + i * 32 + c];
     const float dz = dz0 + dz1;  // the paired step's (role-0 part + role-1 part)
-    const float beta = a.hp->kl_beta;
+    const float beta = *a.klw;
     // merged step: mu | logvar and eps from the forward's LDS (H, Red); else from memory
     const float* Hm = reinterpret_cast<const float*>(lds + L::H);
     const float mu = MERGED ? Hm[c] : a.mulv[(size_t)n * 64 + c];

@@ -141,9 +141,9 @@ void fill_fwd(f28::FwdArgs& a, const long long* p, int B, unsigned stream, int t
   a.xtag = P<const unsigned>(p, 31);
 }
 
-void fill_bwd(f28::BwdArgs& a, const long long* p, int M) {
+void fill_bwd(f28::BwdArgs& a, const long long* p, int M, const TrainState* st) {
   fill_weights(a.w, p);
-  a.hp = P<const HParams>(p, 12);
+  a.klw = st ? &st->kl_next : &P<const HParams>(p, 12)->kl_beta;  // device addresses, not dereferenced here
   a.mulv = P<const float>(p, 13);
   a.eps = P<const float>(p, 14);
   a.a1 = P<const __bf16>(p, 15);
@@ -219,7 +219,7 @@ int mdt_f28_step(const long long* pf, const long long* pb, const long long* pp, 
   f28::FwdArgs fa{};
   fill_fwd(fa, pf, B, stream, 1);
   f28::BwdArgs ba{};
-  fill_bwd(ba, pb, M);
+  fill_bwd(ba, pb, M, fa.st);
   f28::PairCtl pc{};
   pc.M = M;
   pc.pair = pair ? 1 : 0;
@@ -248,10 +248,11 @@ int mdt_f28_step(const long long* pf, const long long* pb, const long long* pp, 
   return (int)hipGetLastError();
 }
 
-int mdt_f28_backward(const long long* p, int M, hipStream_t s) {
+// `st` (optional): the training state whose step the NEXT launch advances
+int mdt_f28_backward(const long long* p, int M, const void* st, hipStream_t s) {
   if (M <= 0) return 1;
   f28::BwdArgs a{};
-  fill_bwd(a, p, M);
+  fill_bwd(a, p, M, reinterpret_cast<const TrainState*>(st));
   hipLaunchKernelGGL(f28::f28_bwd_k, dim3(M), dim3(f28::kThreads), 0, s, a);
   return (int)hipGetLastError();
 }

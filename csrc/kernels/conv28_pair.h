@@ -790,7 +790,8 @@ __device__ __forceinline__ void pair_rest(uint8_t* lds, int n, int r) {
     uint32_t pv[1];
     xget<1>(xi, gi, tg + 5, pv, err, near);
     const float dz = r ? bitsf(pv[0]) + mine : mine + bitsf(pv[0]);
-    const float beta = tab<L, const HParams>(lds, kTHp)->kl_beta;
+    // the KL weight of the step being computed (t = step + 1: the step is advanced by a later launch)
+    const float beta = tab<L, const TrainState>(lds, kTSt)->kl_next;
     const float mu = Hs[c], lv = Hs[32 + c], ep = Eps[c];
     const float sd = expf(0.5f * lv);
     const float dm = dz + beta * mu;

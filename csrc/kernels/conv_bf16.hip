@@ -42,11 +42,11 @@ __global__ void __launch_bounds__(256) reparam_k(const float* mulv, float* eps, 
 
 // dz (f32 [B, Z], from the decoder Linear's backward-data) -> d[mu|lv].
 __global__ void __launch_bounds__(256) reparam_bwd_k(const float* dz, const float* mulv, const float* eps,
-                                                     float* dmulv, __bf16* dmulv16, int B, int Z, const HParams* hp) {
+                                                     float* dmulv, __bf16* dmulv16, int B, int Z, const float* klw) {
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= B * Z) return;
   const int i = e / Z, c = e - i * Z;
-  const float beta = hp->kl_beta;
+  const float beta = *klw;  // TrainState.kl_t of the running step (or HParams.kl_beta)
   const float mu = mulv[(size_t)i * 2 * Z + c], lv = mulv[(size_t)i * 2 * Z + Z + c];
   const float sd = expf(0.5f * lv);
   const float g = dz[e];
@@ -112,9 +112,7 @@ __global__ void __launch_bounds__(256) conv_loss_finalize_k(LossArgs la, int adv
 // step++ and the Adam beta^t running products (first launch of a step).
 __global__ void step_begin_k(TrainState* st, const HParams* hp) {
   if (threadIdx.x == 0 && blockIdx.x == 0) {
-    st->step = st->step + 1;
-    st->b1pow *= hp->beta1_d;
-    st->b2pow *= hp->beta2_d;
+    step_advance(st, hp);
   }
 }
 
@@ -208,9 +206,9 @@ int mdt_reparam(const float* mulv, float* eps, void* z16, float* z32, int B, int
 }
 
 int mdt_reparam_bwd(const float* dz, const float* mulv, const float* eps, float* dmulv, void* dmulv16, int B, int Z,
-                    const void* hp, hipStream_t s) {
+                    const float* klw, hipStream_t s) {
   hipLaunchKernelGGL(reparam_bwd_k, dim3(cdivh((long long)B * Z, 256)), dim3(256), 0, s, dz, mulv, eps, dmulv,
-                     reinterpret_cast<__bf16*>(dmulv16), B, Z, reinterpret_cast<const HParams*>(hp));
+                     reinterpret_cast<__bf16*>(dmulv16), B, Z, klw);
   return (int)hipGetLastError();
 }
 
@@ -297,9 +295,9 @@ int mdt_combine_reparam(const float* slab, int ks, const float* bias, float* mul
 }
 
 int mdt_combine_reparam_bwd(const float* slab, int ks, const float* mulv, const float* eps, float* dmulv,
-                            void* dmulv16, float* dz, int B, int Z, const void* hp, hipStream_t s) {
+                            void* dmulv16, float* dz, int B, int Z, const float* klw, hipStream_t s) {
   const CombineReparamBwdArgs a{slab, ks, splitk_rp(ks), mulv, eps, dmulv, reinterpret_cast<__bf16*>(dmulv16), dz, B,
-                                Z, reinterpret_cast<const HParams*>(hp)};
+                                Z, klw};
   hipLaunchKernelGGL(combine_reparam_bwd_k, dim3(combine_reparam_blocks(ks, B, Z)), dim3(256), 0, s, a);
   return (int)hipGetLastError();
 }

@@ -29,7 +29,7 @@ __device__ __forceinline__ void loss_finalize_body(const LossArgs& la, float* sc
   const float kld = block_sum(sk, scratch);
   if (threadIdx.x == 0) {
     TrainState* st = la.st;
-    const float loss = bce + la.hp->kl_beta * kld;
+    const float loss = bce + st->kl_t * kld;  // the step begun in an earlier launch wrote it
     st->loss_hist[(st->step - 1) % kLossHist] = loss;
     st->epoch_loss += (double)loss;
     st->epoch_count += 1.0;
@@ -56,10 +56,8 @@ __device__ __forceinline__ void loss_step_body(const LossArgs& la, float* scratc
   const float kld = block_sum(sk, scratch);
   if (threadIdx.x == 0) {
     TrainState* st = la.st;
-    st->step = st->step + 1;
-    st->b1pow *= la.hp->beta1_d;
-    st->b2pow *= la.hp->beta2_d;
-    const float loss = bce + la.hp->kl_beta * kld;
+    step_advance(st, la.hp);
+    const float loss = bce + st->kl_t * kld;  // t = the step just advanced to
     st->loss_hist[(st->step - 1) % kLossHist] = loss;
     st->epoch_loss += (double)loss;
     st->epoch_count += 1.0;
@@ -250,7 +248,7 @@ struct CombineReparamBwdArgs {
   __bf16* dmulv16;
   float* dz;
   int B, Z;
-  const HParams* hp;
+  const float* klw;  // the step's KL weight: TrainState.kl_t (or HParams.kl_beta: no schedule)
 };
 
 // `red` >= 1024 floats (16-B aligned)
@@ -259,7 +257,7 @@ __device__ __forceinline__ void combine_reparam_bwd_rows_body(const CombineRepar
   // this lane's mu / logvar / eps and beta before the slab sum (one round trip
   // fewer at the kernel's end)
   const int c = t < Z ? t : 0, e = i * Z + c;
-  const float beta = a.hp->kl_beta;
+  const float beta = *a.klw;
   const float mu = a.mulv[(size_t)i * 2 * Z + c], lv = a.mulv[(size_t)i * 2 * Z + Z + c], ee = a.eps[e];
   combine_rows_partial(a.slab, a.ks, (long long)a.B * Z, (long long)i * Z, Z, red);
   __syncthreads();
@@ -294,7 +292,7 @@ __device__ __forceinline__ void combine_reparam_bwd_body(const CombineReparamBwd
   for (int r = 0; r < a.rp; ++r) g += red[r * cnt + col];
   const int i = e / a.Z, c = e - i * a.Z;
   if (a.dz) a.dz[e] = g;
-  const float beta = a.hp->kl_beta;
+  const float beta = *a.klw;
   const float mu = a.mulv[(size_t)i * 2 * a.Z + c], lv = a.mulv[(size_t)i * 2 * a.Z + a.Z + c];
   const float sd = expf(0.5f * lv);
   const float dm = g + beta * mu;

@@ -131,12 +131,7 @@ __device__ __forceinline__ void thin_conv_body(const ThinConvArgs& ta, uint8_t* 
           reinterpret_cast<const float4*>(X + (size_t)(rows ? rows[i] : i) * d.H * d.W)[c];
     }
   }
-  if (ta.hp && bid == 0 && threadIdx.x == 0) {
-    TrainState* st = ta.st;
-    st->step = st->step + 1;
-    st->b1pow *= ta.hp->beta1_d;
-    st->b2pow *= ta.hp->beta2_d;
-  }
+  if (ta.hp && bid == 0 && threadIdx.x == 0) step_advance(ta.st, ta.hp);
   float xin[TAPS];
 #pragma unroll
   for (int t = 0; t < TAPS; ++t) {
@@ -654,12 +649,7 @@ __device__ void thin_conv_mfma_body(const ThinConvArgs& ta, uint8_t* lds, int bi
   const TIN* img = X + (size_t)(rows ? rows[n] : n) * d.H * d.W;
   // (the gathered rows xb -- BCE target, weight-gradient input -- are written
   // from the patch below: this workgroup's own 8 input rows, no second read)
-  if (ta.hp && bid == 0 && tid == 0) {
-    TrainState* st = ta.st;
-    st->step = st->step + 1;
-    st->b1pow *= ta.hp->beta1_d;
-    st->b2pow *= ta.hp->beta2_d;
-  }
+  if (ta.hp && bid == 0 && tid == 0) step_advance(ta.st, ta.hp);
   // input rows 2 oy0 - 1 .. 2 oy0 + 8, columns -1 .. 128 (zero padding
   // stored; thin_conv_mfma_ok fixes W = 128), unrolled so every load is in
   // flight before the first LDS store waits

@@ -1,5 +1,6 @@
 // Host/device-shared structures of the fused MLP-VAE step (see vae_mlp.hip).
 #pragma once
+#include <math.h>
 #include <stdint.h>
 #include <hip/hip_runtime.h>
 
@@ -20,6 +21,11 @@ constexpr int kLossHist = 4096;     // per-step loss ring (host reads at log poi
 //                                    F3/B3 read).
 // So `step` counts steps started: the RNG counter of the running step is
 // step-1 and Adam's 1-based t is step.
+//
+// The thread that advances `step` (step_advance below) also evaluates the
+// trial's lr / KL-weight schedule for the new t and records the effective
+// values here, so every consumer of the step reads plain numbers and the host
+// reads back what the kernels used.
 struct TrainState {
   int64_t step;
   int32_t cursor;      // batch index within the epoch's index list
@@ -27,6 +33,12 @@ struct TrainState {
   double b1pow, b2pow; // beta1^step, beta2^step (Adam bias corrections; F1 advances them)
   double epoch_loss;   // running sum of per-batch losses since the host reset it
   double epoch_count;  // batches accumulated in epoch_loss
+  double lr_t;         // effective lr of step `step`: lr_d * f_lr(step) (Adam reads this, not HParams.lr)
+  float kl_t;          // effective KL weight of step `step`: (float)(kl_beta_d * f_kl(step))
+  float kl_next;       // ... of step `step + 1`: for the fused 28x28 forward/backward, which run
+                       // BEFORE their step is advanced (no block of that launch writes it)
+  int32_t sched_off;   // 1: factors are 1 whatever the step (eval states: eval uses the full beta)
+  int32_t pad_;
   float loss_hist[kLossHist];
 };
 
@@ -37,7 +49,59 @@ struct HParams {
   int32_t decoupled_wd;
   uint32_t seed_lo, seed_hi;
   double lr_d, beta1_d, beta2_d;  // double copies: torch computes lr/bc1 in double
+  double kl_beta_d;
+  // schedule (all 0 = off: both factors are exactly 1.0 and lr_d * 1.0,
+  // (float)kl_beta_d are the unscheduled values bit for bit)
+  double lr_min_ratio;            // r: cosine floor as a fraction of lr
+  int32_t lr_warmup;              // W: linear warm-up steps
+  int32_t lr_decay;               // 0 none, 1 cosine
+  int32_t lr_decay_steps;         // T: total steps including warm-up (cosine: T > W)
+  int32_t kl_anneal;              // A: KL weight ramps linearly over the first A steps
 };
+
+constexpr int kLrDecayNone = 0, kLrDecayCosine = 1;
+
+// Schedule factors of the 1-based optimizer step t, in double; the same
+// arithmetic as hpo/schedule.py (the device's cos(pi p) is cospi(p)).
+__host__ __device__ inline double sched_lr_factor(const HParams& hp, long long t) {
+  if (hp.lr_warmup > 0 && t <= hp.lr_warmup) return (double)t / (double)hp.lr_warmup;
+  if (hp.lr_decay == kLrDecayCosine) {
+    const double q = (double)(t - hp.lr_warmup) / (double)(hp.lr_decay_steps - hp.lr_warmup);
+    const double p = q < 1.0 ? q : 1.0;
+#ifdef __HIP_DEVICE_COMPILE__
+    const double c = cospi(p);
+#else
+    const double c = cos(3.14159265358979323846 * p);
+#endif
+    return hp.lr_min_ratio + (1.0 - hp.lr_min_ratio) * 0.5 * (1.0 + c);
+  }
+  return 1.0;
+}
+__host__ __device__ inline double sched_kl_factor(const HParams& hp, long long t) {
+  if (hp.kl_anneal <= 0) return 1.0;
+  const double q = (double)t / (double)hp.kl_anneal;
+  return q < 1.0 ? q : 1.0;
+}
+// Effective values of step t into a state image (device: the advancing
+// thread; host: set_step / set_hparams re-seed them like the beta^t products).
+__host__ __device__ inline void sched_store(TrainState* st, const HParams& hp, long long t) {
+  const bool on = st->sched_off == 0;
+  st->lr_t = hp.lr_d * (on ? sched_lr_factor(hp, t) : 1.0);
+  st->kl_t = (float)(hp.kl_beta_d * (on ? sched_kl_factor(hp, t) : 1.0));
+  st->kl_next = (float)(hp.kl_beta_d * (on ? sched_kl_factor(hp, t + 1) : 1.0));
+}
+
+#ifdef __HIPCC__
+// The ONE place a step is advanced (one thread per step, see the protocol
+// above): step, the Adam beta^t products and the schedule's effective values.
+__device__ __forceinline__ void step_advance(TrainState* st, const HParams* hp) {
+  const long long t = st->step + 1;
+  st->step = t;
+  st->b1pow *= hp->beta1_d;
+  st->b2pow *= hp->beta2_d;
+  sched_store(st, *hp, t);
+}
+#endif
 
 struct VaeArgs {
   int M, B, D, H, Z;

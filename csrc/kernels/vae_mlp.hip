@@ -173,10 +173,7 @@ __global__ void __launch_bounds__(kThreads) vae_f1(VaeArgs a) {
     }
   }
   if (blockIdx.x == 0 && threadIdx.x == 0) {
-    TrainState* st = a.st;
-    st->step = st->step + 1;
-    st->b1pow = st->b1pow * a.hp->beta1_d;
-    st->b2pow = st->b2pow * a.hp->beta2_d;
+    step_advance(a.st, a.hp);
   }
   STAMP(0, 2);
 }
@@ -499,8 +496,8 @@ __global__ void __launch_bounds__(kThreads) vae_b2(VaeArgs a, int nrow, int nw3,
     __syncthreads();
     const float kld = block_sum(sk, scratch);
     if (threadIdx.x == 0) {
-      const float loss = bce + a.hp->kl_beta * kld;
       TrainState* st = a.st;
+      const float loss = bce + st->kl_t * kld;  // F1 of this step wrote it (eval: full beta)
       st->loss_hist[(st->step - 1) % kLossHist] = loss;
       st->epoch_loss += (double)loss;
       st->epoch_count += 1.0;
@@ -583,7 +580,7 @@ __global__ void __launch_bounds__(kThreads) vae_b2(VaeArgs a, int nrow, int nw3,
   }
   __syncthreads();
   STAMP(4, 1);
-  const float beta = a.hp->kl_beta;
+  const float beta = a.st->kl_t;  // the step's KL weight, written by F1 (an earlier launch)
   float dmu = 0.f, dlv = 0.f;
   if (mine) {
     float dz = 0.f;

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../kernels/vae_mlp.h"
+#include "sched_host.h"
 
 #include "../kernels/conv_igemm.h"
 
@@ -27,7 +28,7 @@ int mdt_gather_rows(const float* X, const int* idx, const void* st, int B, int M
 int mdt_reparam(const float* mulv, float* eps, void* z16, float* z32, int B, int Z, const void* st, const void* hp,
                 unsigned stream, float* kld_part, hipStream_t s);
 int mdt_reparam_bwd(const float* dz, const float* mulv, const float* eps, float* dmulv, void* dmulv16, int B, int Z,
-                    const void* hp, hipStream_t s);
+                    const float* klw, hipStream_t s);
 int mdt_bce_logits(const float* logits, const float* X, const int* rows, int B, int P, void* dlog16, float* recon,
                    float* part, float* gpart, hipStream_t s);
 int mdt_conv_loss_finalize(const float* bce_part, int nb, const float* kld_part, int nk, void* st, const void* hp,
@@ -61,7 +62,7 @@ int mdt_combine_reparam(const float* slab, int ks, const float* bias, float* mul
                         int B, int Z, const void* st, const void* hp, unsigned stream, float* kld_part, hipStream_t s);
 int mdt_combine_reparam_blocks(int ks, int B, int Z);
 int mdt_combine_reparam_bwd(const float* slab, int ks, const float* mulv, const float* eps, float* dmulv,
-                            void* dmulv16, float* dz, int B, int Z, const void* hp, hipStream_t s);
+                            void* dmulv16, float* dz, int B, int Z, const float* klw, hipStream_t s);
 int mdt_job_wgrad(mdt::JobBlob* j, const void* G16, const void* X, int x_is_f32, mdt::ConvDesc d, float* out);
 int mdt_job_thin_conv(mdt::JobBlob* j, const void* X, int x_is_f32, const float* Wf, mdt::ConvDesc d,
                       const float* bias, int relu, void* y16, const void* omask, float* colsum, const int* idx,
@@ -76,7 +77,7 @@ int mdt_pack_jobs_multi_stamps(void* img, void* stamps);
 int mdt_launch_jobs_multi(const void* dev_pack, int grid, int dep, hipStream_t s);
 int mdt_f28_forward(const long long* p, int B, int M, unsigned stream, int train, hipStream_t s);
 int mdt_f28_forward_pair(const long long* p, const long long* pp, int B, int M, unsigned stream, hipStream_t s);
-int mdt_f28_backward(const long long* p, int M, hipStream_t s);
+int mdt_f28_backward(const long long* p, int M, const void* st, hipStream_t s);
 int mdt_f28_step(const long long* pf, const long long* pb, const long long* pp, int B, int M, unsigned stream,
                  int pair, int delay_us, hipStream_t s);
 int mdt_f28_pair_words();
@@ -291,10 +292,25 @@ void reparam(const at::Tensor& mulv, at::Tensor eps, at::Tensor z16, const c10::
      "reparam");
 }
 
+// Device address of the KL weight a backward kernel of the running step uses:
+// TrainState.kl_t of `state` (written when the step was begun, an earlier
+// launch; follows the trial's schedule) or, with no state, HParams.kl_beta.
+const float* kl_weight_ptr(const at::Tensor& hparams, const c10::optional<at::Tensor>& state) {
+  if (state.has_value() && state->defined()) {
+    TORCH_CHECK(state->is_cuda() && state->numel() * state->element_size() >= (int64_t)sizeof(TrainState),
+                "state: a TrialState device buffer");
+    return reinterpret_cast<const float*>(static_cast<const char*>(state->data_ptr()) + offsetof(TrainState, kl_t));
+  }
+  TORCH_CHECK(hparams.is_cuda() && hparams.numel() * hparams.element_size() >= (int64_t)sizeof(HParams),
+              "hparams: a TrialState device buffer");
+  return reinterpret_cast<const float*>(static_cast<const char*>(hparams.data_ptr()) + offsetof(HParams, kl_beta));
+}
+
 void reparam_bwd(const at::Tensor& dz, const at::Tensor& mulv, const at::Tensor& eps, at::Tensor dmulv,
-                 const c10::optional<at::Tensor>& dmulv16, int64_t B, int64_t Z, const at::Tensor& hparams) {
+                 const c10::optional<at::Tensor>& dmulv16, int64_t B, int64_t Z, const at::Tensor& hparams,
+                 const c10::optional<at::Tensor>& state) {
   rc(mdt_reparam_bwd(dz.data_ptr<float>(), mulv.data_ptr<float>(), eps.data_ptr<float>(), dmulv.data_ptr<float>(),
-                     const_cast<void*>(opt_ptr(dmulv16)), (int)B, (int)Z, hparams.data_ptr(), cur()),
+                     const_cast<void*>(opt_ptr(dmulv16)), (int)B, (int)Z, kl_weight_ptr(hparams, state), cur()),
      "reparam_bwd");
 }
 
@@ -507,11 +523,20 @@ void f28_forward(const std::vector<c10::optional<at::Tensor>>& t, int64_t B, int
   rc(mdt_f28_forward(p.data(), (int)B, (int)M, (unsigned)stream, train ? 1 : 0, cur()), "f28_forward");
 }
 
-void f28_backward(const std::vector<c10::optional<at::Tensor>>& t, int64_t M) {
+// `state` (optional): the training state whose step is advanced AFTER this
+// launch (the fused step's loss job): the backward then uses the KL weight of
+// step + 1 recorded there; without it, HParams.kl_beta.
+void f28_backward(const std::vector<c10::optional<at::Tensor>>& t, int64_t M, const c10::optional<at::Tensor>& state) {
   TORCH_CHECK(M > 0, "f28_backward: bad M");
   const int dev = t[0].has_value() ? (int)t[0]->device().index() : 0;
   const auto p = f28_ptrs(t, f28_bwd_slots(), M, dev);
-  rc(mdt_f28_backward(p.data(), (int)M, cur()), "f28_backward");
+  const void* st = nullptr;
+  if (state.has_value() && state->defined()) {
+    TORCH_CHECK(state->is_cuda() && state->numel() * state->element_size() >= (int64_t)sizeof(TrainState),
+                "f28_backward: state must be a TrialState device buffer");
+    st = state->data_ptr();
+  }
+  rc(mdt_f28_backward(p.data(), (int)M, st, cur()), "f28_backward");
 }
 
 // Forward + backward of one training step in ONE launch (f28_step_k). With
@@ -695,12 +720,13 @@ void combine_reparam(const at::Tensor& ws, int64_t ks, const c10::optional<at::T
 
 void combine_reparam_bwd(const at::Tensor& ws, int64_t ks, const at::Tensor& mulv, const at::Tensor& eps,
                          at::Tensor dmulv, const c10::optional<at::Tensor>& dmulv16,
-                         const c10::optional<at::Tensor>& dz, int64_t B, int64_t Z, const at::Tensor& hparams) {
+                         const c10::optional<at::Tensor>& dz, int64_t B, int64_t Z, const at::Tensor& hparams,
+                         const c10::optional<at::Tensor>& state) {
   check_f32(ws, "ws");
   TORCH_CHECK(ws.numel() >= ks * B * Z && dmulv.numel() >= B * 2 * Z, "combine_reparam_bwd: buffer too small");
   rc(mdt_combine_reparam_bwd(ws.data_ptr<float>(), (int)ks, mulv.data_ptr<float>(), eps.data_ptr<float>(),
                              dmulv.data_ptr<float>(), const_cast<void*>(opt_ptr(dmulv16)), (float*)opt_ptr(dz), (int)B,
-                             (int)Z, hparams.data_ptr(), cur()),
+                             (int)Z, kl_weight_ptr(hparams, state), cur()),
      "combine_reparam_bwd");
 }
 
@@ -715,22 +741,29 @@ class TrialStateBuf {
     set_hparams(1e-3, 0.9, 0.999, 1e-8, 0.0, 1.0, 1.0, 0, false);
   }
   void set_hparams(double lr, double b1, double b2, double eps, double wd, double kl_beta, double gs, int64_t seed,
-                   bool decoupled) {
+                   bool decoupled, int64_t lr_warmup = 0, int64_t lr_decay = 0, int64_t lr_decay_steps = 0,
+                   double lr_min_ratio = 0.0, int64_t kl_anneal = 0) {
     HParams h;
     std::memset(&h, 0, sizeof(h));
     h.lr = (float)lr; h.beta1 = (float)b1; h.beta2 = (float)b2; h.eps = (float)eps; h.weight_decay = (float)wd;
     h.kl_beta = (float)kl_beta; h.grad_scale = (float)gs; h.decoupled_wd = decoupled ? 1 : 0;
     h.seed_lo = (uint32_t)((uint64_t)seed & 0xffffffffu); h.seed_hi = (uint32_t)((uint64_t)seed >> 32);
     h.lr_d = lr; h.beta1_d = b1; h.beta2_d = b2;
+    sched_fill(h, kl_beta, lr_warmup, lr_decay, lr_decay_steps, lr_min_ratio, kl_anneal);
+    hp_ = h;
     const bool changed = b1 != b1_ || b2 != b2_;
     b1_ = b1; b2_ = b2;
     auto cpu = torch::empty({(int64_t)sizeof(HParams)}, torch::kUInt8);
     std::memcpy(cpu.data_ptr(), &h, sizeof(h));
     hparams.narrow(0, 0, sizeof(HParams)).copy_(cpu);
+    const int64_t tstep = (int64_t)read_state(false)[0], estep = (int64_t)read_state(true)[0];
     if (changed) {
-      pows(train_state, (int64_t)read_state(false)[0]);
-      pows(eval_state, (int64_t)read_state(true)[0]);
+      pows(train_state, tstep);
+      pows(eval_state, estep);
     }
+    // the effective lr / KL weight stored in the states follow the new values
+    sched_seed(train_state, hp_, tstep, false);
+    sched_seed(eval_state, hp_, estep, true);
   }
   void set_cursor(bool eval, int64_t cursor, int64_t nbatches) {
     int32_t v[2] = {(int32_t)cursor, (int32_t)nbatches};
@@ -744,13 +777,15 @@ class TrialStateBuf {
     at::Tensor& s = eval ? eval_state : train_state;
     s.narrow(0, offsetof(TrainState, step), 8).copy_(cpu);
     pows(s, step);
+    sched_seed(s, hp_, step, eval);
   }
   void reset_loss(bool eval) { (eval ? eval_state : train_state).narrow(0, offsetof(TrainState, epoch_loss), 16).zero_(); }
   std::vector<double> read_state(bool eval) {
     auto cpu = (eval ? eval_state : train_state).narrow(0, 0, offsetof(TrainState, loss_hist)).to(torch::kCPU);
     TrainState h;
     std::memcpy(&h, cpu.data_ptr(), offsetof(TrainState, loss_hist));
-    return {(double)h.step, (double)h.cursor, (double)h.nbatches, h.epoch_loss, h.epoch_count};
+    // + the effective lr and KL weight of the last completed step (what its kernels used)
+    return {(double)h.step, (double)h.cursor, (double)h.nbatches, h.epoch_loss, h.epoch_count, h.lr_t, (double)h.kl_t};
   }
   at::Tensor loss_history(bool eval) {
     return (eval ? eval_state : train_state)
@@ -769,6 +804,7 @@ class TrialStateBuf {
   }
   int64_t dev_;
   double b1_ = -1, b2_ = -1;
+  HParams hp_{};  // host copy: set_step re-seeds the schedule's effective values from it
 };
 
 void bind_conv(pybind11::module& m) {
@@ -795,7 +831,7 @@ void bind_conv(pybind11::module& m) {
   m.def("launch_jobs_multi", &launch_jobs_multi, py::arg("dev_pack"), py::arg("grid"), py::arg("dep") = false);
   m.def("f28_forward", &f28_forward, py::arg("tensors"), py::arg("B"), py::arg("M"), py::arg("stream"),
         py::arg("train"), py::arg("pair") = std::vector<c10::optional<at::Tensor>>{});
-  m.def("f28_backward", &f28_backward, py::arg("tensors"), py::arg("M"));
+  m.def("f28_backward", &f28_backward, py::arg("tensors"), py::arg("M"), py::arg("state") = py::none());
   m.def("f28_pair_words", &mdt_f28_pair_words);
   m.def("f28_step", &f28_step, py::arg("fwd_tensors"), py::arg("bwd_tensors"), py::arg("B"), py::arg("M"),
         py::arg("stream"), py::arg("pair") = std::vector<c10::optional<at::Tensor>>{},
@@ -819,7 +855,8 @@ void bind_conv(pybind11::module& m) {
         py::arg("recon") = py::none(), py::arg("part") = py::none(), py::arg("gpart") = py::none());
   m.def("gather_rows", &gather_rows);
   m.def("reparam", &reparam);
-  m.def("reparam_bwd", &reparam_bwd);
+  m.def("reparam_bwd", &reparam_bwd, py::arg("dz"), py::arg("mulv"), py::arg("eps"), py::arg("dmulv"),
+        py::arg("dmulv16"), py::arg("B"), py::arg("Z"), py::arg("hparams"), py::arg("state") = py::none());
   m.def("bce_logits", &bce_logits, py::arg("logits"), py::arg("X"), py::arg("rows"), py::arg("B"), py::arg("P"),
         py::arg("dlog16"), py::arg("recon"), py::arg("part"), py::arg("gpart") = py::none());
   m.def("loss_finalize2", &loss_finalize2, py::arg("bce_part"), py::arg("nb"), py::arg("kld_part"), py::arg("nk"),
@@ -850,11 +887,16 @@ void bind_conv(pybind11::module& m) {
   m.def("wtrans", &wtrans, py::arg("w16"), py::arg("w16t"), py::arg("segs"), py::arg("units"), py::arg("nunits"),
         py::arg("job") = py::none());
   m.def("combine_reparam", &combine_reparam);
-  m.def("combine_reparam_bwd", &combine_reparam_bwd);
+  m.def("combine_reparam_bwd", &combine_reparam_bwd, py::arg("ws"), py::arg("ks"), py::arg("mulv"), py::arg("eps"),
+        py::arg("dmulv"), py::arg("dmulv16"), py::arg("dz"), py::arg("B"), py::arg("Z"), py::arg("hparams"),
+        py::arg("state") = py::none());
   m.def("combine_reparam_blocks", &mdt_combine_reparam_blocks);
   py::class_<TrialStateBuf>(m, "TrialState")
       .def(py::init<int64_t>())
-      .def("set_hparams", &TrialStateBuf::set_hparams)
+      .def("set_hparams", &TrialStateBuf::set_hparams, py::arg("lr"), py::arg("beta1"), py::arg("beta2"),
+           py::arg("eps"), py::arg("weight_decay"), py::arg("kl_beta"), py::arg("grad_scale"), py::arg("seed"),
+           py::arg("decoupled_wd"), py::arg("lr_warmup_steps") = 0, py::arg("lr_decay") = 0,
+           py::arg("lr_decay_steps") = 0, py::arg("lr_min_ratio") = 0.0, py::arg("kl_anneal_steps") = 0)
       .def("set_cursor", &TrialStateBuf::set_cursor)
       .def("set_step", &TrialStateBuf::set_step)
       .def("reset_loss", &TrialStateBuf::reset_loss)

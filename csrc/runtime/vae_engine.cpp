@@ -8,6 +8,7 @@
 #include <stdexcept>
 
 #include "../kernels/vae_mlp.h"
+#include "sched_host.h"
 
 extern "C" int mdt_adam_step(float* p, const float* g, float* m, float* v, long long n,
                              const mdt::HParams* hp, mdt::TrainState* st, hipStream_t s);
@@ -111,7 +112,8 @@ at::Tensor MlpVaeEngine::act(const std::string& name, int64_t M) {
 
 void MlpVaeEngine::set_hparams(double lr, double beta1, double beta2, double eps,
                                double weight_decay, double kl_beta, double grad_scale,
-                               int64_t seed, bool decoupled_wd) {
+                               int64_t seed, bool decoupled_wd, int64_t lr_warmup, int64_t lr_decay,
+                               int64_t lr_decay_steps, double lr_min_ratio, int64_t kl_anneal) {
   HParams h;
   std::memset(&h, 0, sizeof(h));
   h.lr = (float)lr; h.beta1 = (float)beta1; h.beta2 = (float)beta2; h.eps = (float)eps;
@@ -119,6 +121,7 @@ void MlpVaeEngine::set_hparams(double lr, double beta1, double beta2, double eps
   h.grad_scale = (float)grad_scale;
   h.decoupled_wd = decoupled_wd ? 1 : 0;
   h.lr_d = lr; h.beta1_d = beta1; h.beta2_d = beta2;
+  sched_fill(h, kl_beta, lr_warmup, lr_decay, lr_decay_steps, lr_min_ratio, kl_anneal);
   const bool betas_changed = (beta1 != beta1_) || (beta2 != beta2_);
   beta1_ = beta1; beta2_ = beta2;
   h.seed_lo = (uint32_t)((uint64_t)seed & 0xffffffffu);
@@ -126,10 +129,15 @@ void MlpVaeEngine::set_hparams(double lr, double beta1, double beta2, double eps
   auto cpu = torch::empty({(int64_t)sizeof(HParams)}, torch::kUInt8);
   std::memcpy(cpu.data_ptr(), &h, sizeof(h));
   hparams.narrow(0, 0, sizeof(HParams)).copy_(cpu);
+  hp_ = h;
+  const int64_t tstep = (int64_t)read_state(false)[0], estep = (int64_t)read_state(true)[0];
   if (betas_changed) {  // keep the device beta^t products consistent with the new betas
-    set_step((int64_t)read_state(false)[0]);
-    write_pows(eval_state, (int64_t)read_state(true)[0]);
+    write_pows(train_state, tstep);
+    write_pows(eval_state, estep);
   }
+  // the effective lr / KL weight stored in the states follow the new values
+  sched_seed(train_state, hp_, tstep, false);
+  sched_seed(eval_state, hp_, estep, true);
 }
 
 void MlpVaeEngine::write_pows(at::Tensor& s, int64_t step) {
@@ -152,6 +160,7 @@ void MlpVaeEngine::set_step(int64_t step) {
   std::memcpy(cpu.data_ptr(), &step, 8);
   train_state.narrow(0, offsetof(TrainState, step), 8).copy_(cpu);
   write_pows(train_state, step);
+  sched_seed(train_state, hp_, step, false);
 }
 
 void MlpVaeEngine::reset_loss(bool eval) {
@@ -164,7 +173,8 @@ std::vector<double> MlpVaeEngine::read_state(bool eval) {
   auto cpu = s.narrow(0, 0, offsetof(TrainState, loss_hist)).to(torch::kCPU);
   TrainState h;
   std::memcpy(&h, cpu.data_ptr(), offsetof(TrainState, loss_hist));
-  return {(double)h.step, (double)h.cursor, (double)h.nbatches, h.epoch_loss, h.epoch_count};
+  // + the effective lr and KL weight of the last completed step (what its kernels used)
+  return {(double)h.step, (double)h.cursor, (double)h.nbatches, h.epoch_loss, h.epoch_count, h.lr_t, (double)h.kl_t};
 }
 
 at::Tensor MlpVaeEngine::loss_history(bool eval) {

@@ -16,6 +16,8 @@
 #include <tuple>
 #include <vector>
 
+#include "../kernels/vae_mlp.h"
+
 namespace mdt {
 
 struct LayoutEntry {
@@ -33,11 +35,13 @@ class MlpVaeEngine {
   int64_t bucket_split() const { return split_; }  // arena offset where fc4 starts
 
   void set_hparams(double lr, double beta1, double beta2, double eps, double weight_decay,
-                   double kl_beta, double grad_scale, int64_t seed, bool decoupled_wd);
+                   double kl_beta, double grad_scale, int64_t seed, bool decoupled_wd, int64_t lr_warmup = 0,
+                   int64_t lr_decay = 0, int64_t lr_decay_steps = 0, double lr_min_ratio = 0.0,
+                   int64_t kl_anneal = 0);
   void set_cursor(bool eval, int64_t cursor, int64_t nbatches);
   void set_step(int64_t step);
   void reset_loss(bool eval);
-  std::vector<double> read_state(bool eval);          // step, cursor, nbatches, epoch_loss, epoch_count
+  std::vector<double> read_state(bool eval);          // step, cursor, nbatches, epoch_loss, epoch_count, lr, kl_beta
   at::Tensor loss_history(bool eval);                  // CPU float tensor [kLossHist]
 
   void forward(const at::Tensor& X, const at::Tensor& idx, int64_t M, bool train, bool eval,
@@ -57,6 +61,7 @@ class MlpVaeEngine {
   void write_pows(at::Tensor& state, int64_t step);
   int64_t B_, D_, H_, Z_, total_, split_;
   double beta1_ = -1.0, beta2_ = -1.0;
+  HParams hp_{};  // host copy: set_step re-seeds the schedule's effective values from it
   int last_f2_blocks_ = 0, last_f3_blocks_ = 0;
   std::vector<LayoutEntry> layout_;
   at::Tensor stamps_;

@@ -9,7 +9,11 @@ Each file holds only tensors and plain Python scalars/strings, so it loads
 with ``torch.load(weights_only=True)`` (never unpickles code):
   model        state_dict under the reference's parameter names (fc1.weight, ...)
   optimizer    {"step", "exp_avg", "exp_avg_sq"} flat arenas (layout recorded)
-  trial        TrialSpec fields (group_id, epochs, lr, beta, seed)
+  trial        TrialSpec fields (group_id, epochs, lr, beta, seed, and the
+               lr / KL-weight schedule fields as given)
+  schedule     the trainer's resolved Schedule (hpo/schedule.py) or None; a
+               load restores it, so a resumed trial continues its schedule
+               from the restored step
   progress     {"epoch": completed epochs, "step": optimizer steps}
   rng          {"seed", "rng_stream"} (Philox is counter-based: the step
                counter + seed fully determine the noise stream)
@@ -38,11 +42,14 @@ def save_trial(ckpt_dir: str, trainer, spec, epoch: int, extra: Optional[dict] =
     d = trial_dir(ckpt_dir, spec.group_id)
     os.makedirs(d, exist_ok=True)
     opt = trainer.optimizer_state()
+    sched = getattr(trainer, "schedule", None)
     payload = {
         "format": "multidisttorch_amd.trial.v1",
         "model": trainer.state_dict(),
         "optimizer": {"step": int(opt["step"]), "exp_avg": opt["exp_avg"], "exp_avg_sq": opt["exp_avg_sq"]},
-        "trial": {k: (float(v) if isinstance(v, float) else int(v)) for k, v in spec.to_dict().items()},
+        "trial": {k: (float(v) if isinstance(v, float) else v if isinstance(v, str) else int(v))
+                  for k, v in spec.to_dict().items()},
+        "schedule": sched.to_dict() if sched is not None else None,
         "progress": {"epoch": int(epoch), "step": int(opt["step"])},
         "rng": {"seed": int(trainer.seed), "rng_stream": int(trainer.rng_stream)},
         "layout": [[n, int(o)] + [int(x) for x in s] for n, o, s in trainer.layout],
@@ -88,5 +95,9 @@ def load_latest(ckpt_dir: str, group_id: int, trainer) -> Optional[dict]:
     if ck["layout"] != lay:
         raise ValueError(f"{path}: parameter arena layout mismatch")
     trainer.load_state_dict(ck["model"])
-    trainer.load_optimizer_state(ck["optimizer"])
+    if ck.get("schedule") is not None:
+        from ..hpo.schedule import Schedule
+
+        trainer.set_schedule(Schedule(**ck["schedule"]))
+    trainer.load_optimizer_state(ck["optimizer"])  # sets the step: the schedule continues from it
     return dict(ck["progress"], path=path, trial=ck["trial"])

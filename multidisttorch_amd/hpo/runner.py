@@ -23,6 +23,7 @@ from __future__ import annotations
 
 import math
 import os
+import struct
 import sys
 import time
 from dataclasses import dataclass, field
@@ -42,6 +43,7 @@ from ..runtime.bootstrap import bound_device, global_barrier
 from ..runtime.faults import (InjectedFault, TrialCorrupted, TrialTimeout, agree_healthy, fault_step, group_timeout_s, guarded,
                               heartbeat_s, maybe_inject, trial_watch)
 from ..utils.images import flush_images, save_image_async
+from .schedule import LR_DECAYS, Schedule
 from .trial import TrialSpec
 
 __all__ = ["RunOptions", "TrialResult", "run_trial", "run_packed_trials", "idle_rank"]
@@ -91,20 +93,42 @@ def _results_dir(opts: RunOptions, group_id: int, group_rank: int) -> str:
     return f"results-{group_rank}"
 
 
-def _make_trainer(spec: TrialSpec, opts: RunOptions, device, group_rank: int, D: int):
+def _schedule_words(s) -> list:
+    """A Schedule as six int64 words (flag, W, decay kind, T, A, bits of r) for the resume broadcast."""
+    if s is None:
+        return [0] * 6
+    return [1, s.lr_warmup_steps, LR_DECAYS.index(s.lr_decay), s.lr_decay_steps, s.kl_anneal_steps,
+            struct.unpack("<q", struct.pack("<d", s.lr_min_ratio))[0]]
+
+
+def _schedule_from_words(w):
+    if not w[0]:
+        return None
+    return Schedule(w[1], LR_DECAYS[w[2]], w[3], struct.unpack("<d", struct.pack("<q", w[5]))[0], w[4])
+
+
+def _total_steps(spec: TrialSpec, opts: RunOptions, n_shard: int) -> int:
+    """Optimizer steps of the whole trial: the default cosine horizon."""
+    return spec.epochs * -(-n_shard // opts.batch_size)
+
+
+def _make_trainer(spec: TrialSpec, opts: RunOptions, device, group_rank: int, D: int,
+                  total_steps: Optional[int] = None):
+    sched = spec.schedule(total_steps)
+    sched = sched if sched.active else None
     if opts.model == "mlp":
         from ..models.mlp_trainer import MlpVaeTrainer
 
         return MlpVaeTrainer(batch_size=opts.batch_size, D=D, device=device, backend=opts.backend,
                              seed=spec.seed, lr=spec.lr, kl_beta=spec.beta, rng_stream=group_rank,
-                             use_graphs=opts.use_graphs, graph_steps=opts.graph_steps)
+                             use_graphs=opts.use_graphs, graph_steps=opts.graph_steps, schedule=sched)
     if opts.model == "conv":
         from ..models.conv_vae import ConvVaeTrainer
 
         return ConvVaeTrainer(batch_size=opts.batch_size, image=opts.image_size,
                               z=32 if opts.image_size == 28 else 64, device=device, backend=opts.backend,
                               seed=spec.seed, lr=spec.lr, kl_beta=spec.beta, rng_stream=group_rank,
-                              use_graphs=opts.use_graphs, graph_steps=opts.graph_steps)
+                              use_graphs=opts.use_graphs, graph_steps=opts.graph_steps, schedule=sched)
     raise ValueError(f"unknown model {opts.model!r}")
 
 
@@ -337,7 +361,8 @@ def run_trial(spec: TrialSpec, group, opts: RunOptions, data=None, num_trials: O
         print(f"[mdt] trial {spec.group_id}: train data {train.name} ({'synthetic' if train.synthetic else 'IDX'}, "
               f"{len(train)} x {tuple(train.shape)})", file=sys.stderr, flush=True)
     D = int(train.data.shape[1])
-    trainer = _make_trainer(spec, opts, device, grank, D)
+    total_steps = _total_steps(spec, opts, shard_indices(len(train), n_rep, spec.group_id).numel())
+    trainer = _make_trainer(spec, opts, device, grank, D, total_steps)
     if gsize > 1:
         # DDP's _sync_module_states: replicas start from group rank 0's weights
         broadcast_params([trainer.params], group)
@@ -345,8 +370,8 @@ def run_trial(spec: TrialSpec, group, opts: RunOptions, data=None, num_trials: O
         if opts.bucket_mb == "auto":
             idx0 = shard_indices(len(train), n_rep, spec.group_id)
             key = f"{opts.model}-{opts.image_size}-b{opts.batch_size}-n{trainer.numel}-s{gsize}"
-            bounds, kind, timings = autotune_comm(lambda: _make_trainer(spec, opts, device, grank, D), group,
-                                                  train.data, idx0, key=key)
+            bounds, kind, timings = autotune_comm(
+                lambda: _make_trainer(spec, opts, device, grank, D, total_steps), group, train.data, idx0, key=key)
             print0(f"bucket autotune (group of {gsize}): {timings} -> {kind or 'default'} {bounds}",
                    process_group=group)
         else:
@@ -371,7 +396,9 @@ def run_trial(spec: TrialSpec, group, opts: RunOptions, data=None, num_trials: O
             start_epoch = prog["epoch"] + 1
             print0(f"resumed trial {spec.group_id} from {prog['path']} (epoch {prog['epoch']})", process_group=group)
         if gsize > 1:
-            meta = torch.tensor([0 if err is None else 1, start_epoch, trainer.step_count], dtype=torch.int64,
+            # + the schedule rank 0's checkpoint restored (it wins over the command line on every member)
+            meta = torch.tensor([0 if err is None else 1, start_epoch, trainer.step_count] +
+                                _schedule_words(trainer.schedule if prog is not None else None), dtype=torch.int64,
                                 device=device if dist.get_backend(group) == "nccl" else "cpu")
             broadcast_params([meta], group)
             if int(meta[0].item()) != 0:
@@ -381,6 +408,9 @@ def run_trial(spec: TrialSpec, group, opts: RunOptions, data=None, num_trials: O
                                    f"stopping every member")
             broadcast_params([trainer.params, trainer.exp_avg, trainer.exp_avg_sq], group)
             start_epoch = int(meta[1].item())
+            sched = _schedule_from_words([int(v) for v in meta[3:].tolist()])
+            if sched is not None:
+                trainer.set_schedule(sched)
             trainer.set_step(int(meta[2].item()))
             trainer.refresh_weights()
         elif err is not None:
@@ -471,9 +501,13 @@ def _run_epoch(trainer, epoch, n_shard, train, test, opts, group, rdir, shape, g
         with trace.range(f"ckpt_{epoch}"):
             ckpt.save_trial(opts.ckpt_dir, trainer, spec, epoch)
     _mark("ckpt_s", t)
+    # lr / kl_beta: the effective values of the epoch's last step as the kernels
+    # recorded them (= lr_base / beta when the trial has no schedule)
+    st = trainer.read_state()
     metrics.log(epoch=epoch, train_loss_sum=train_loss, train_loss=train_loss / len(train),
                 test_loss=test_loss, epoch_train_s=t_train, samples=n_shard,
-                train_samples_per_s=n_shard / max(t_train, 1e-9), lr=spec.lr, beta=spec.beta, **phases)
+                train_samples_per_s=n_shard / max(t_train, 1e-9), lr=st["lr"], kl_beta=st["kl_beta"],
+                lr_base=spec.lr, beta=spec.beta, **phases)
     return train_loss, test_loss
 
 
@@ -501,7 +535,8 @@ def run_packed_trials(specs, group, opts: RunOptions, data=None, num_trials: Opt
     shape = (1, opts.image_size, opts.image_size)
     tr = []
     for spec in specs:
-        trainer = _make_trainer(spec, opts, device, 0, D)
+        trainer = _make_trainer(spec, opts, device, 0, D,
+                                _total_steps(spec, opts, shard_indices(len(train), total, spec.group_id).numel()))
         if len(specs) > 1 and hasattr(trainer, "f28_pair"):
             # packed trials fill the chip already; the one-workgroup-per-sample
             # step keeps their numerics independent of how the trials interleave

@@ -12,6 +12,8 @@ import math
 from dataclasses import asdict, dataclass
 from typing import List, Optional, Sequence
 
+from .schedule import Schedule
+
 __all__ = ["TrialSpec", "reference_schedule", "default_sweep", "parse_list", "build_specs"]
 
 
@@ -22,9 +24,24 @@ class TrialSpec:
     lr: float = 1e-3
     beta: float = 1.0
     seed: int = 0
+    # lr / KL-weight schedule (hpo/schedule.py), all off by default.
+    # lr_decay_steps = 0 with cosine decay: the runner uses the trial's total step count
+    lr_warmup_steps: int = 0
+    lr_decay: str = "none"
+    lr_decay_steps: int = 0
+    lr_min_ratio: float = 0.0
+    kl_anneal_steps: int = 0
 
     def to_dict(self):
         return asdict(self)
+
+    def schedule(self, total_steps: Optional[int] = None) -> Schedule:
+        """The trial's ``Schedule``; ``total_steps`` (epochs x batches per epoch)
+        stands in for an unset ``lr_decay_steps`` under cosine decay."""
+        T = self.lr_decay_steps
+        if self.lr_decay == "cosine" and T == 0 and total_steps is not None:
+            T = int(total_steps)
+        return Schedule(self.lr_warmup_steps, self.lr_decay, T, self.lr_min_ratio, self.kl_anneal_steps)
 
 
 def reference_schedule(num_groups: int, epochs: int, lr: float = 1e-3, beta: float = 1.0,
@@ -54,11 +71,24 @@ def parse_list(s: Optional[str], cast=float) -> Optional[List]:
 
 def build_specs(num_groups: int, epochs: int, lrs: Optional[Sequence[float]] = None,
                 betas: Optional[Sequence[float]] = None, seed: int = 0,
-                epoch_offset: bool = True) -> List[TrialSpec]:
+                epoch_offset: bool = True, lr_warmups: Optional[Sequence[int]] = None,
+                lr_decays: Optional[Sequence[str]] = None, lr_decay_steps: Optional[Sequence[int]] = None,
+                lr_min_ratios: Optional[Sequence[float]] = None,
+                kl_anneals: Optional[Sequence[int]] = None) -> List[TrialSpec]:
     """Per-group specs. A single value broadcasts; a list is indexed by group (cycled)."""
+    def pick(vals, g, default):
+        return vals[g % len(vals)] if vals else default
+
     out = []
     for g in range(num_groups):
         lr = lrs[g % len(lrs)] if lrs else 1e-3
         b = betas[g % len(betas)] if betas else 1.0
-        out.append(TrialSpec(g, epochs + (g if epoch_offset else 0), float(lr), float(b), seed + g))
+        spec = TrialSpec(g, epochs + (g if epoch_offset else 0), float(lr), float(b), seed + g,
+                         lr_warmup_steps=int(pick(lr_warmups, g, 0)), lr_decay=str(pick(lr_decays, g, "none")),
+                         lr_decay_steps=int(pick(lr_decay_steps, g, 0)),
+                         lr_min_ratio=float(pick(lr_min_ratios, g, 0.0)),
+                         kl_anneal_steps=int(pick(kl_anneals, g, 0)))
+        # bad values fail here, not in the middle of a run (T = 0 under cosine is resolved by the runner)
+        spec.schedule(total_steps=spec.lr_warmup_steps + 1 if spec.lr_decay_steps == 0 else None)
+        out.append(spec)
     return out

@@ -36,6 +36,7 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
+from ..hpo.schedule import Schedule
 from ..ops import native
 from ..ops.philox import reparam_eps
 from .eval_graphs import GraphedEval
@@ -206,8 +207,12 @@ class ConvVaeTrainer(GraphedEval):
     def __init__(self, batch_size: int = 128, image: int = 28, channels: int = 1, z: int = 32, device=None,
                  backend: Optional[str] = None, seed: int = 0, lr: float = 1e-3, kl_beta: float = 1.0,
                  betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0, decoupled_wd: bool = False,
-                 rng_stream: int = 0, use_graphs: bool = True, graph_steps: int = 10, init_seed: Optional[int] = None):
+                 rng_stream: int = 0, use_graphs: bool = True, graph_steps: int = 10, init_seed: Optional[int] = None,
+                 schedule: Optional[Schedule] = None):
         self.B, self.image, self.channels, self.Z = batch_size, image, channels, z
+        # lr warm-up / cosine decay and KL annealing (hpo/schedule.py); None = off.
+        # On the hip backend the kernels evaluate it from the device step counter.
+        self.schedule = schedule
         self.D = image * image * channels
         self.H = None
         self.device = torch.device(device) if device is not None else (
@@ -352,11 +357,26 @@ class ConvVaeTrainer(GraphedEval):
             self.hp[k] = float(v)
         self._push_hparams()
 
+    def set_schedule(self, schedule: Optional[Schedule]):
+        """Replace the schedule (None = off). It continues from the current
+        step; captured step graphs stay valid (the parameters are device-resident)."""
+        self.schedule = schedule
+        self._push_hparams()
+
     def _push_hparams(self):
         if self.backend == "hip":
             h = self.hp
             self.state.set_hparams(h["lr"], h["beta1"], h["beta2"], h["eps"], h["weight_decay"], h["kl_beta"],
-                                   h["grad_scale"], self.seed, self.decoupled_wd)
+                                   h["grad_scale"], self.seed, self.decoupled_wd,
+                                   **(self.schedule or Schedule()).native_args())
+
+    def _effective(self, t: int):
+        """(lr_t, beta_t) of optimizer step t on the torch backend, as doubles:
+        lr * f_lr(t) and kl_beta * f_kl(t), the products the device forms."""
+        s, h = self.schedule, self.hp
+        if s is None:
+            return h["lr"], h["kl_beta"]
+        return h["lr"] * s.lr_factor(t), h["kl_beta"] * s.kl_factor(t)
 
     # ----------------------------------------------------------- state
     @property
@@ -407,8 +427,13 @@ class ConvVaeTrainer(GraphedEval):
     def read_state(self, eval=False):
         if self.backend == "hip":
             s = self.state.read_state(eval)
-            return dict(step=int(s[0]), cursor=int(s[1]), nbatches=int(s[2]), epoch_loss=s[3], epoch_count=s[4])
-        return dict(self._st_eval if eval else self._st)
+            return dict(step=int(s[0]), cursor=int(s[1]), nbatches=int(s[2]), epoch_loss=s[3], epoch_count=s[4],
+                        lr=s[5], kl_beta=s[6])
+        # lr / kl_beta: the effective values of the last completed step (eval: always the full ones)
+        st = dict(self._st_eval if eval else self._st)
+        lr, kl = (self.hp["lr"], self.hp["kl_beta"]) if eval else self._effective(st["step"])
+        st["lr"], st["kl_beta"] = float(lr), float(np.float32(kl))
+        return st
 
     def loss_history(self, eval=False):
         if self.backend == "hip":
@@ -964,10 +989,10 @@ class ConvVaeTrainer(GraphedEval):
                     if ks > 1:  # split-K combine fused with the reparameterisation backward
                         after.append(lambda ks=ks: C.combine_reparam_bwd(p["ws"], ks, self.mulv, self.eps, self.dmulv,
                                                                          self.dmulv16, self.dz, M, self.Z,
-                                                                         st.hparams))
+                                                                         st.hparams, state=st.train_state))
                     else:
                         after.append(lambda: C.reparam_bwd(self.dz, self.mulv, self.eps, self.dmulv, self.dmulv16,
-                                                           M, self.Z, st.hparams))
+                                                           M, self.Z, st.hparams, state=st.train_state))
                     cso = p["colsum"][prev.name]
                     carry.append(lambda job, cso=cso: C.colsum(self.dmulv16, M, 2 * self.Z, p["rows_per"], cso,
                                                                job=job))
@@ -1260,7 +1285,7 @@ class ConvVaeTrainer(GraphedEval):
                        pair_delay_us=self.f28_pair_delay_us)
         else:
             C.f28_forward(p["fwd"], self.B, M, self.rng_stream, True)
-            C.f28_backward(p["bwd"], M)
+            C.f28_backward(p["bwd"], M, state=st.train_state)
         red = self.reducer
         if red is None:
             if self.f28_fin_merge:
@@ -1394,7 +1419,8 @@ class ConvVaeTrainer(GraphedEval):
         x = X[rows]
         eps = torch.from_numpy(reparam_eps(M, self.Z, self.seed, self.rng_stream, st["step"])).to(self.device)
         self.model.zero_grad(set_to_none=True)
-        loss, *_ = self.model.loss(x, eps, self.hp["kl_beta"])
+        lr_t, kl_t = self._effective(st["step"] + 1)
+        loss, *_ = self.model.loss(x, eps, kl_t)
         loss.backward()
         with torch.no_grad():
             gv = self.named_grads()
@@ -1404,7 +1430,7 @@ class ConvVaeTrainer(GraphedEval):
                 self.reducer.launch_all()
                 self.reducer.wait_all()
             h = self.hp
-            reference_adam_(self.params, self.grads, self.exp_avg, self.exp_avg_sq, st["step"] + 1, h["lr"],
+            reference_adam_(self.params, self.grads, self.exp_avg, self.exp_avg_sq, st["step"] + 1, lr_t,
                             h["beta1"], h["beta2"], h["eps"], h["weight_decay"], h["grad_scale"], self.decoupled_wd)
             self.model.from_arena(self.named_parameters())
         lv = float(loss.detach())

@@ -28,6 +28,7 @@ from typing import Dict, List, Optional
 import numpy as np
 import torch
 
+from ..hpo.schedule import Schedule
 from ..ops import native
 from ..ops.philox import reparam_eps
 from .eval_graphs import GraphedEval
@@ -44,8 +45,11 @@ class MlpVaeTrainer(GraphedEval):
                  device=None, backend: Optional[str] = None, seed: int = 0, init_seed: Optional[int] = None,
                  lr: float = 1e-3, kl_beta: float = 1.0, betas=(0.9, 0.999), eps: float = 1e-8,
                  weight_decay: float = 0.0, decoupled_wd: bool = False, rng_stream: int = 0,
-                 use_graphs: bool = True, graph_steps: int = 10):
+                 use_graphs: bool = True, graph_steps: int = 10, schedule: Optional[Schedule] = None):
         self.B, self.D, self.H, self.Z = batch_size, D, H, Z
+        # lr warm-up / cosine decay and KL annealing (hpo/schedule.py); None = off.
+        # On the hip backend the kernels evaluate it from the device step counter.
+        self.schedule = schedule
         self.device = torch.device(device) if device is not None else (
             torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu"))
         if backend is None:
@@ -128,11 +132,26 @@ class MlpVaeTrainer(GraphedEval):
             self.hp[k] = float(v)
         self._push_hparams()
 
+    def set_schedule(self, schedule: Optional[Schedule]):
+        """Replace the schedule (None = off). It continues from the current
+        step; captured step graphs stay valid (the parameters are device-resident)."""
+        self.schedule = schedule
+        self._push_hparams()
+
     def _push_hparams(self):
         if self.engine is not None:
             h = self.hp
             self.engine.set_hparams(h["lr"], h["beta1"], h["beta2"], h["eps"], h["weight_decay"],
-                                    h["kl_beta"], h["grad_scale"], self.seed, self.decoupled_wd)
+                                    h["kl_beta"], h["grad_scale"], self.seed, self.decoupled_wd,
+                                    **(self.schedule or Schedule()).native_args())
+
+    def _effective(self, t: int):
+        """(lr_t, beta_t) of optimizer step t on the torch backend, as doubles:
+        lr * f_lr(t) and kl_beta * f_kl(t), the products the device forms."""
+        s, h = self.schedule, self.hp
+        if s is None:
+            return h["lr"], h["kl_beta"]
+        return h["lr"] * s.lr_factor(t), h["kl_beta"] * s.kl_factor(t)
 
     # ------------------------------------------------------------------ state
     @property
@@ -165,8 +184,12 @@ class MlpVaeTrainer(GraphedEval):
         if self.engine is not None:
             s = self.engine.read_state(eval)
             return dict(step=int(s[0]), cursor=int(s[1]), nbatches=int(s[2]), epoch_loss=s[3],
-                        epoch_count=s[4])
-        return dict(self._st_eval if eval else self._st)
+                        epoch_count=s[4], lr=s[5], kl_beta=s[6])
+        # lr / kl_beta: the effective values of the last completed step (eval: always the full ones)
+        st = dict(self._st_eval if eval else self._st)
+        lr, kl = (self.hp["lr"], self.hp["kl_beta"]) if eval else self._effective(st["step"])
+        st["lr"], st["kl_beta"] = float(lr), float(np.float32(kl))
+        return st
 
     def loss_history(self, eval: bool = False) -> np.ndarray:
         if self.engine is not None:
@@ -273,26 +296,27 @@ class MlpVaeTrainer(GraphedEval):
         X, idx = self._data[0], self._data[1]
         st = self._st
         h = self.hp
+        lr_t, kl_t = self._effective(st["step"] + 1)
         cpu = self._cpu_native()
         if cpu is not None:
             loss = cpu.forward_backward(self._cpu_w, self._cpu_g, X, idx, st["cursor"] * self.B, M, self.seed,
-                                        self.rng_stream, st["step"], h["kl_beta"])
+                                        self.rng_stream, st["step"], kl_t)
         else:
             rows = idx[st["cursor"] * self.B: st["cursor"] * self.B + M].long()
             x = X[rows]
             eps = torch.from_numpy(reparam_eps(M, self.Z, self.seed, self.rng_stream, st["step"])).to(self.device)
-            f = reference_step(self.named_parameters(), self.named_grads(), x, eps, h["kl_beta"])
+            f = reference_step(self.named_parameters(), self.named_grads(), x, eps, kl_t)
             loss = None
         if self.reducer is not None:
             self.reducer.launch(1)
             self.reducer.launch(0)
             self.reducer.wait_all()
         if cpu is not None:
-            cpu.adam(self.params, self.grads, self.exp_avg, self.exp_avg_sq, st["step"] + 1, h["lr"], h["beta1"],
+            cpu.adam(self.params, self.grads, self.exp_avg, self.exp_avg_sq, st["step"] + 1, lr_t, h["beta1"],
                      h["beta2"], h["eps"], h["weight_decay"], h["grad_scale"], self.decoupled_wd)
         else:
             reference_adam_(self.params, self.grads, self.exp_avg, self.exp_avg_sq, st["step"] + 1,
-                            h["lr"], h["beta1"], h["beta2"], h["eps"], h["weight_decay"], h["grad_scale"],
+                            lr_t, h["beta1"], h["beta2"], h["eps"], h["weight_decay"], h["grad_scale"],
                             self.decoupled_wd)
             loss = float(f["loss"])
         self._hist[st["step"] % LOSS_HIST] = loss

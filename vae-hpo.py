@@ -8,7 +8,9 @@ epochs). Launch one process per GPU with any launcher the reference supports
 (jsrun / srun / mpirun) or torchrun / ``python -m multidisttorch_amd.launch``.
 
 Extensions (opt-in, default output unchanged): ``--lr`` / ``--beta`` (scalar or
-comma list, one per trial), ``--seed``, ``--ckpt-dir`` + ``--resume``,
+comma list, one per trial), the per-trial schedules ``--lr-warmup`` / ``--lr-decay``
+/ ``--lr-decay-steps`` / ``--lr-min-ratio`` / ``--kl-anneal`` (same form;
+multidisttorch_amd/hpo/schedule.py), ``--seed``, ``--ckpt-dir`` + ``--resume``,
 ``--metrics-dir`` (JSONL + aggregate samples/s), ``--per-group-results``, ``--bucket-mb``,
 ``--no-graphs``, ``--backend {hip,torch}``, ``--synthetic/--real-data``,
 ``--trials-per-group T`` (T concurrent trials per single-rank group, one HIP
@@ -42,6 +44,14 @@ def parse_args(argv=None):
     # ---- extensions ----
     parser.add_argument("--lr", type=str, default=None, help="learning rate(s), comma list per trial")
     parser.add_argument("--beta", type=str, default=None, help="KLD weight(s), comma list per trial")
+    # per-trial schedules (hpo/schedule.py): a scalar or a comma list per trial, like --lr / --beta
+    parser.add_argument("--lr-warmup", type=str, default=None, help="linear lr warm-up steps")
+    parser.add_argument("--lr-decay", type=str, default=None, help="lr decay after the warm-up: none | cosine")
+    parser.add_argument("--lr-decay-steps", type=str, default=None,
+                        help="total steps of the lr schedule, warm-up included (default: the trial's step count)")
+    parser.add_argument("--lr-min-ratio", type=str, default=None, help="cosine floor as a fraction of lr, in [0, 1]")
+    parser.add_argument("--kl-anneal", type=str, default=None,
+                        help="steps over which the KLD weight ramps linearly from 0 to --beta")
     parser.add_argument("--seed", type=int, default=0, help="base seed (trial g uses seed+g)")
     parser.add_argument("--no-epoch-offset", action="store_true", help="all trials train --epochs epochs")
     parser.add_argument("--log-interval", type=int, default=10)
@@ -101,7 +111,10 @@ def main(argv=None):
 
     T = max(1, args.trials_per_group)
     specs = build_specs(ngroups * T, args.epochs, parse_list(args.lr), parse_list(args.beta), args.seed,
-                        epoch_offset=not args.no_epoch_offset)
+                        epoch_offset=not args.no_epoch_offset, lr_warmups=parse_list(args.lr_warmup, int),
+                        lr_decays=parse_list(args.lr_decay, lambda s: s.strip()),
+                        lr_decay_steps=parse_list(args.lr_decay_steps, int),
+                        lr_min_ratios=parse_list(args.lr_min_ratio), kl_anneals=parse_list(args.kl_anneal, int))
     opts = RunOptions(batch_size=args.batch_size, log_interval=args.log_interval,
                       backend=args.backend, use_graphs=not args.no_graphs, graph_steps=args.graph_steps,
                       ckpt_dir=args.ckpt_dir, resume=args.resume, metrics_dir=args.metrics_dir,
