@@ -16,6 +16,7 @@ void bind_conv(pybind11::module& m);
 void bind_rccl(pybind11::module& m);
 void bind_p2p(pybind11::module& m);
 void bind_cpu(pybind11::module& m);
+void bind_iw(pybind11::module& m);
 }  // namespace mdt
 
 PYBIND11_MODULE(_C, m) {
@@ -30,6 +31,7 @@ PYBIND11_MODULE(_C, m) {
   mdt::bind_rccl(m);
   mdt::bind_p2p(m);
   mdt::bind_cpu(m);
+  mdt::bind_iw(m);
 
   py::class_<mdt::MlpVaeEngine>(m, "MlpVaeEngine")
       .def(py::init<int64_t, int64_t, int64_t, int64_t, int64_t>(), py::arg("batch"),
@@ -56,6 +58,13 @@ PYBIND11_MODULE(_C, m) {
       .def("act", &mdt::MlpVaeEngine::act)
       .def("decode", &mdt::MlpVaeEngine::decode)
       .def("set_stamps", &mdt::MlpVaeEngine::set_stamps)
+      .def("iw_begin", &mdt::MlpVaeEngine::iw_begin, py::arg("nbatches"))
+      .def("iw_batch", &mdt::MlpVaeEngine::iw_batch, py::arg("X"), py::arg("idx"), py::arg("M"), py::arg("K"),
+           py::arg("chunk"), py::arg("row_nll"), py::arg("row_neg_elbo"))
+      .def("iw_read", &mdt::MlpVaeEngine::iw_read)
+      .def("iw_capacity", &mdt::MlpVaeEngine::iw_capacity)
+      .def("iw_act", &mdt::MlpVaeEngine::iw_act, py::arg("name"), py::arg("S"), py::arg("M"))
+      .def_readonly("iw_state", &mdt::MlpVaeEngine::iw_state)
       .def_readonly("params", &mdt::MlpVaeEngine::params)
       .def_readonly("grads", &mdt::MlpVaeEngine::grads)
       .def_readonly("exp_avg", &mdt::MlpVaeEngine::exp_avg)

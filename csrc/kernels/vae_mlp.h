@@ -143,6 +143,7 @@ VaeGrid vae_grid(const VaeArgs& a);
 extern "C" {
 int mdt_vae_check(const mdt::VaeArgs* a);
 int mdt_vae_forward(const mdt::VaeArgs* a, hipStream_t s);
+int mdt_vae_encode(const mdt::VaeArgs* a, hipStream_t s);  // F1 only
 int mdt_vae_backward(const mdt::VaeArgs* a, hipStream_t s, int part);
 int mdt_vae_decode(const mdt::VaeArgs* a, const float* zin, hipStream_t s);
 }

@@ -26,13 +26,9 @@
 #include "tile_gemm.h"
 #include "vae_mlp.h"
 #include "adam_common.h"
+#include "vae_mlp_dev.h"
 
 namespace mdt {
-
-constexpr int kWaves = 8;
-constexpr int kThreads = kWaves * 64;
-
-__device__ __forceinline__ int cdiv_d(int a, int b) { return (a + b - 1) / b; }
 
 // Phase timestamps for the profiling tool (obs/stamps.py); a null pointer
 // (production) costs one uniform branch. Slot 7 holds where the wave ran:
@@ -66,36 +62,6 @@ struct EpiBiasRelu {
     return 0.f;
   }
 };
-
-// Slab geometry: TH = H/16 slices; [mu|lv] slabs are NTM = ceil(2Z/16) tiles
-// wide (SW floats), dz slabs NTZ = ceil(Z/16) tiles (SWZ floats). F2/B2 run
-// GROUPS = ceil(TH/8) blocks per row tile, one 16-column output tile per wave.
-struct SlabGeo {
-  int th, ntm, sw, ntz, swz, groups;
-  __device__ __host__ SlabGeo(int H, int Z)
-      : th((H + 15) / 16), ntm((2 * Z + 15) / 16), sw(((2 * Z + 15) / 16) * 16), ntz((Z + 15) / 16),
-        swz(((Z + 15) / 16) * 16), groups(((H + 15) / 16 + kWaves - 1) / kWaves) {}
-};
-
-// Transposes a 16x16 C-layout tile (wave 0's registers: col = lane&15,
-// rows 4q..4q+3) into an LDS [row][k] image readable as A fragments.
-__device__ __forceinline__ void tile_to_lds(float (*t)[20], const float (&v)[4]) {
-  const int lane = lane_id();
-#pragma unroll
-  for (int rr = 0; rr < 4; ++rr) t[4 * (lane >> 4) + rr][lane & 15] = v[rr];
-}
-
-// 16x16 MFMA with A from the LDS tile (k = 16) and a prefetched B fragment.
-__device__ __forceinline__ f32x4 lds_tile_mma(float (*t)[20], const float (&b)[4]) {
-  const int lane = lane_id();
-  const float4 av = *reinterpret_cast<const float4*>(&t[lane & 15][4 * (lane >> 4)]);
-  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-  acc = mfma16x16x4(av.x, b[0], acc);
-  acc = mfma16x16x4(av.y, b[1], acc);
-  acc = mfma16x16x4(av.z, b[2], acc);
-  acc = mfma16x16x4(av.w, b[3], acc);
-  return acc;
-}
 
 // One block = one 16x16 tile (ti, tj) of h1, its K = D split over the 8
 // waves. The relu'd tile then feeds the encoder head as a split-K slice:
@@ -748,6 +714,14 @@ extern "C" int mdt_vae_forward(const VaeArgs* a, hipStream_t s) {
   hipLaunchKernelGGL(vae_f1, dim3(g.f1), dim3(kThreads), 0, s, *a);
   hipLaunchKernelGGL(vae_f2, dim3(g.f2), dim3(kThreads), 0, s, *a);
   hipLaunchKernelGGL(vae_f3, dim3(g.f3), dim3(kThreads), 0, s, *a);
+  return (int)hipGetLastError();
+}
+
+// F1 alone: the encoder of a pass that samples the latent itself (vae_iw.hip).
+extern "C" int mdt_vae_encode(const VaeArgs* a, hipStream_t s) {
+  const int rc = mdt_vae_check(a);
+  if (rc) return rc;
+  hipLaunchKernelGGL(vae_f1, dim3(vae_grid(*a).f1), dim3(kThreads), 0, s, *a);
   return (int)hipGetLastError();
 }
 

@@ -7,6 +7,7 @@
 #include <cstring>
 #include <stdexcept>
 
+#include "../kernels/vae_iw.h"
 #include "../kernels/vae_mlp.h"
 #include "sched_host.h"
 
@@ -81,6 +82,7 @@ MlpVaeEngine::MlpVaeEngine(int64_t batch, int64_t D, int64_t H, int64_t Z, int64
   train_state = torch::zeros({st_bytes}, bopt);
   eval_state = torch::zeros({st_bytes}, bopt);
   hparams = torch::zeros({align64((int64_t)sizeof(HParams))}, bopt);
+  iw_state = iw_state_new(device_index);
   set_hparams(1e-3, 0.9, 0.999, 1e-8, 0.0, 1.0, 1.0, 0, false);
 }
 
@@ -298,6 +300,174 @@ at::Tensor MlpVaeEngine::decode(const at::Tensor& z) {
   check_rc(mdt_vae_decode(&a, z.data_ptr<float>(), c10::hip::getCurrentHIPStream().stream()),
            "vae decode");
   return act("recon", a.M).clone();
+}
+
+// ------------------------------------------------- importance-weighted pass ----
+at::Tensor iw_state_new(int64_t device_index) {
+  auto bopt = torch::TensorOptions().dtype(torch::kUInt8).device(torch::kCUDA, device_index);
+  return torch::zeros({align64((int64_t)sizeof(IwState))}, bopt);
+}
+
+void iw_state_begin(at::Tensor state, int64_t nbatches) {
+  TORCH_CHECK(nbatches > 0, "iw pass: nbatches must be positive");
+  TORCH_CHECK(state.is_cuda() && state.scalar_type() == torch::kUInt8 && state.numel() >= (int64_t)sizeof(IwState),
+              "iw pass: state must come from iw_state_new");
+  state.zero_();
+  TrainState h;
+  std::memset(&h, 0, sizeof(h));
+  h.nbatches = (int32_t)nbatches;
+  h.b1pow = h.b2pow = 1.0;
+  h.sched_off = 1;  // no schedule enters the pass (its first kernel still advances the step there)
+  auto cpu = torch::empty({(int64_t)offsetof(TrainState, loss_hist)}, torch::kUInt8);
+  std::memcpy(cpu.data_ptr(), &h, offsetof(TrainState, loss_hist));
+  state.narrow(0, 0, offsetof(TrainState, loss_hist)).copy_(cpu);
+}
+
+std::vector<double> iw_state_read(const at::Tensor& state) {
+  auto cpu = state.to(torch::kCPU);
+  const uint8_t* p = cpu.data_ptr<uint8_t>();
+  TrainState h;
+  std::memcpy(&h, p, offsetof(TrainState, loss_hist));
+  double t[2];
+  std::memcpy(t, p + offsetof(IwState, nll), sizeof(t));
+  return {t[0], t[1], (double)h.step, (double)h.cursor};
+}
+
+void MlpVaeEngine::iw_begin(int64_t nbatches) {
+  iw_state_begin(iw_state, nbatches);
+  iw_nbatches_ = nbatches;
+}
+
+void MlpVaeEngine::iw_batch(const at::Tensor& X, const at::Tensor& idx, int64_t M, int64_t K, int64_t chunk,
+                            at::Tensor row_nll, at::Tensor row_neg_elbo) {
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(params.device());
+  TORCH_CHECK(K >= 1 && chunk >= 1, "iw_batch: K and chunk must be >= 1");
+  TORCH_CHECK((uint64_t)K * (uint64_t)B_ * (uint64_t)Z_ <= (1ull << 32), "iw_batch: K*B*Z exceeds 2^32");
+  TORCH_CHECK(iw_nbatches_ > 0, "iw_batch: call iw_begin first");
+  TORCH_CHECK(idx.numel() >= iw_nbatches_ * B_, "iw_batch: idx shorter than nbatches * B");
+  for (const at::Tensor* t : {&row_nll, &row_neg_elbo})
+    TORCH_CHECK(t->is_cuda() && t->scalar_type() == torch::kFloat32 && t->is_contiguous() &&
+                    t->numel() >= iw_nbatches_ * B_,
+                "iw_batch: row buffers must be contiguous CUDA float32 of >= nbatches * B elements");
+  const int64_t S = std::min(chunk, K);
+  if (S * B_ > iw_cap_ || !iw_ws_.defined()) {
+    iw_cap_ = S * B_;
+    const int64_t n = align64(iw_cap_ * H_) + 2 * align64(iw_cap_ * Z_) + 2 * align64(iw_cap_);
+    iw_ws_ = torch::zeros({n}, params.options());
+    iw_rowbuf_ = torch::zeros({3 * align64(B_)}, params.options());
+  }
+  VaeArgs a;
+  fill_args(&a, X, idx, M, false, true, 0, false);
+  a.st = reinterpret_cast<TrainState*>(iw_state.data_ptr<uint8_t>());  // IwState begins with its TrainState
+  hipStream_t stream = c10::hip::getCurrentHIPStream().stream();
+  check_rc(mdt_vae_encode(&a, stream), "iw encoder");
+  IwArgs w;
+  std::memset(&w, 0, sizeof(w));
+  w.M = a.M; w.B = a.B; w.D = a.D; w.H = a.H; w.Z = a.Z;
+  w.K = (int)K;
+  w.cap_rows = (int)iw_cap_;
+  w.rows_cap = (long long)std::min(row_nll.numel(), row_neg_elbo.numel());
+  w.b2 = a.b2; w.W3 = a.W3; w.b3 = a.b3; w.W4 = a.W4; w.b4 = a.b4;
+  w.slab_mv = a.slab_mv; w.xb = a.xb; w.mulv = a.mulv;
+  float* ws = iw_ws_.data_ptr<float>();
+  w.h3 = ws; ws += align64(iw_cap_ * H_);
+  w.eps = ws; ws += align64(iw_cap_ * Z_);
+  w.z = ws; ws += align64(iw_cap_ * Z_);
+  w.prior = ws; ws += align64(iw_cap_);
+  w.bce = ws;
+  float* rb = iw_rowbuf_.data_ptr<float>();
+  w.lse_m = rb; w.lse_s = rb + align64(B_); w.lw_sum = rb + 2 * align64(B_);
+  w.row_nll = row_nll.data_ptr<float>();
+  w.row_neg_elbo = row_neg_elbo.data_ptr<float>();
+  w.ist = reinterpret_cast<IwState*>(iw_state.data_ptr<uint8_t>());
+  w.hp = a.hp;
+  for (int64_t k0 = 0; k0 < K; k0 += S) {
+    w.k0 = (int)k0;
+    w.S = (int)std::min(S, K - k0);
+    w.first = k0 == 0 ? 1 : 0;
+    w.last = k0 + S >= K ? 1 : 0;
+    check_rc(mdt_iw_chunk(&w, stream), "iw chunk");
+  }
+}
+
+std::vector<double> MlpVaeEngine::iw_read() { return iw_state_read(iw_state); }
+
+at::Tensor MlpVaeEngine::iw_act(const std::string& name, int64_t S, int64_t M) {
+  TORCH_CHECK(iw_ws_.defined() && S >= 1 && M >= 1 && S * M <= iw_cap_, "iw_act: no pass has run at this size");
+  int64_t off = align64(iw_cap_ * H_);
+  if (name == "z") off += align64(iw_cap_ * Z_);
+  else TORCH_CHECK(name == "eps", "iw_act: unknown buffer ", name);
+  return iw_ws_.narrow(0, off, S * M * Z_).view({S, M, Z_});
+}
+
+// ----------------------------------------------- conv-VAE pass: small ops ----
+static float* fptr(const at::Tensor& t, int64_t need, const char* what) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == torch::kFloat32 && t.is_contiguous() && t.numel() >= need, "iw: ",
+              what, " must be a contiguous CUDA float32 tensor of >= ", need, " elements");
+  return t.data_ptr<float>();
+}
+
+static void iw_reparam(const at::Tensor& mulv, int64_t M, int64_t B, int64_t Z, int64_t k0, int64_t S,
+                       const at::Tensor& state, const at::Tensor& hparams, at::Tensor z16, at::Tensor z32,
+                       at::Tensor eps, at::Tensor prior) {
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(mulv.device());
+  TORCH_CHECK(M >= 1 && S >= 1 && S * M <= B, "iw_reparam: a chunk holds at most B virtual rows");
+  TORCH_CHECK(state.numel() >= (int64_t)sizeof(IwState) && hparams.numel() >= (int64_t)sizeof(HParams),
+              "iw_reparam: state / hparams buffers too small");
+  TORCH_CHECK(z16.is_cuda() && z16.scalar_type() == torch::kBFloat16 && z16.is_contiguous() &&
+                  z16.numel() >= S * M * Z,
+              "iw_reparam: z16 must be contiguous CUDA bfloat16 of >= S*M*Z elements");
+  check_rc(mdt_iw_reparam(fptr(mulv, M * 2 * Z, "mulv"), (int)M, (int)B, (int)Z, (int)k0, (int)S, state.data_ptr(),
+                          hparams.data_ptr(), z16.data_ptr(), fptr(z32, S * M * Z, "z32"),
+                          fptr(eps, S * M * Z, "eps"), fptr(prior, S * M, "prior"),
+                          c10::hip::getCurrentHIPStream().stream()),
+           "iw reparam");
+}
+
+static void iw_row_bce(const at::Tensor& logits, const at::Tensor& xb, int64_t V, int64_t M, int64_t P,
+                       at::Tensor bce) {
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(logits.device());
+  TORCH_CHECK(V >= 1 && M >= 1, "iw_row_bce: empty chunk");
+  check_rc(mdt_iw_row_bce(fptr(logits, V * P, "logits"), fptr(xb, M * P, "xb"), (int)V, (int)M, (int)P,
+                          fptr(bce, V, "bce"), c10::hip::getCurrentHIPStream().stream()),
+           "iw row bce");
+}
+
+// rowbuf: [3][B] running max / scaled sum / sum of logw per batch row.
+static void iw_reduce(const at::Tensor& prior, const at::Tensor& bce, at::Tensor rowbuf, at::Tensor row_nll,
+                      at::Tensor row_neg_elbo, at::Tensor state, int64_t M, int64_t B, int64_t K, int64_t S,
+                      bool first, bool last) {
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(prior.device());
+  TORCH_CHECK(M >= 1 && M <= B && S >= 1 && S <= K, "iw_reduce: bad sizes");
+  TORCH_CHECK(state.is_cuda() && state.numel() >= (int64_t)sizeof(IwState), "iw_reduce: state too small");
+  IwArgs w;
+  std::memset(&w, 0, sizeof(w));
+  w.M = (int)M; w.B = (int)B; w.K = (int)K; w.S = (int)S;
+  w.first = first ? 1 : 0; w.last = last ? 1 : 0;
+  w.prior = fptr(prior, S * M, "prior");
+  w.bce = fptr(bce, S * M, "bce");
+  float* rb = fptr(rowbuf, 3 * B, "rowbuf");
+  w.lse_m = rb; w.lse_s = rb + B; w.lw_sum = rb + 2 * B;
+  w.rows_cap = (long long)std::min(row_nll.numel(), row_neg_elbo.numel());
+  w.row_nll = fptr(row_nll, B, "row_nll");
+  w.row_neg_elbo = fptr(row_neg_elbo, B, "row_neg_elbo");
+  w.ist = reinterpret_cast<IwState*>(state.data_ptr());
+  check_rc(mdt_iw_reduce(&w, c10::hip::getCurrentHIPStream().stream()), "iw reduce");
+}
+
+void bind_iw(pybind11::module& m) {
+  namespace py = pybind11;
+  m.def("iw_state_new", &iw_state_new, py::arg("device_index"));
+  m.def("iw_state_begin", &iw_state_begin, py::arg("state"), py::arg("nbatches"));
+  m.def("iw_state_read", &iw_state_read, py::arg("state"));
+  m.def("iw_reparam", &iw_reparam, py::arg("mulv"), py::arg("M"), py::arg("B"), py::arg("Z"), py::arg("k0"),
+        py::arg("S"), py::arg("state"), py::arg("hparams"), py::arg("z16"), py::arg("z32"), py::arg("eps"),
+        py::arg("prior"));
+  m.def("iw_row_bce", &iw_row_bce, py::arg("logits"), py::arg("xb"), py::arg("V"), py::arg("M"), py::arg("P"),
+        py::arg("bce"));
+  m.def("iw_reduce", &iw_reduce, py::arg("prior"), py::arg("bce"), py::arg("rowbuf"), py::arg("row_nll"),
+        py::arg("row_neg_elbo"), py::arg("state"), py::arg("M"), py::arg("B"), py::arg("K"), py::arg("S"),
+        py::arg("first"), py::arg("last"));
 }
 
 }  // namespace mdt

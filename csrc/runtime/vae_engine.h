@@ -26,6 +26,13 @@ struct LayoutEntry {
   std::vector<int64_t> shape;
 };
 
+// Device state of an importance-weighted pass (kernels/vae_iw.h: IwState),
+// shared by both trainers: allocate, zero for a pass of `nbatches`, read back
+// {nll, neg_elbo, step (batches begun), cursor}.
+at::Tensor iw_state_new(int64_t device_index);
+void iw_state_begin(at::Tensor state, int64_t nbatches);
+std::vector<double> iw_state_read(const at::Tensor& state);
+
 class MlpVaeEngine {
  public:
   MlpVaeEngine(int64_t batch, int64_t D, int64_t H, int64_t Z, int64_t device_index);
@@ -53,6 +60,23 @@ class MlpVaeEngine {
   at::Tensor act(const std::string& name, int64_t M);
   void set_stamps(at::Tensor t) { stamps_ = t; }  // int64 [6*512*8*8] or undefined
 
+  // Importance-weighted log-likelihood pass (csrc/kernels/vae_iw.hip). It runs
+  // on a device state of its own (iw_state); train_state / eval_state, their
+  // loss rings and the optimizer arenas are not touched.
+  void iw_begin(int64_t nbatches);  // zero the pass state: cursor 0, step 0, totals 0
+  // One batch of M rows at the pass cursor: encoder once, then the K samples
+  // in chunks of `chunk`; per-row results into row_nll / row_neg_elbo at
+  // cursor*B + i, totals into iw_state. Launches only (graph-capturable once
+  // the workspaces exist: run it once eagerly first).
+  void iw_batch(const at::Tensor& X, const at::Tensor& idx, int64_t M, int64_t K, int64_t chunk,
+                at::Tensor row_nll, at::Tensor row_neg_elbo);
+  std::vector<double> iw_read();    // nll, neg_elbo, step (batches begun), cursor
+  at::Tensor iw_act(const std::string& name, int64_t S, int64_t M);  // "eps" | "z" of the last chunk: [S, M, Z]
+  // virtual rows the chunk workspace holds; it grows (reallocates) when a pass
+  // asks for more, which invalidates graphs captured over the old one
+  int64_t iw_capacity() const { return iw_cap_; }
+  at::Tensor iw_state;
+
   at::Tensor params, grads, exp_avg, exp_avg_sq, acts, partials, train_state, eval_state, hparams;
 
  private:
@@ -65,6 +89,8 @@ class MlpVaeEngine {
   int last_f2_blocks_ = 0, last_f3_blocks_ = 0;
   std::vector<LayoutEntry> layout_;
   at::Tensor stamps_;
+  at::Tensor iw_ws_, iw_rowbuf_;  // chunk workspace (h3 | eps | z | prior | bce) and [3][B] running row state
+  int64_t iw_cap_ = 0, iw_nbatches_ = 0;
   std::vector<std::pair<std::string, int64_t>> act_off_;
 };
 

@@ -71,6 +71,7 @@ class RunOptions:
     synthetic: Optional[bool] = None       # None: IDX files when present, else synthetic; True/False force
     bucket_mb: Optional[object] = None     # None: model default; 0: one bucket; float: MiB cap; "auto": measured
     profile: bool = False                  # roctx ranges + device-synced phase timings in the metrics JSONL
+    iw_samples: int = 0                    # K > 0: importance-weighted test log-likelihood after the last epoch
 
 
 @dataclass
@@ -345,6 +346,27 @@ def _test_epoch(trainer, epoch: int, test, opts: RunOptions, group, rdir: Option
     return test_loss
 
 
+def _iw_eval(trainer, test, opts: RunOptions, group, metrics, device, tag: str = "") -> dict:
+    """One importance-weighted pass over the test set after a trial's last
+    epoch (``--iw-samples K``): the K-sample bound on -log p(x) and the
+    K-sample negative ELBO at beta = 1, per-image means. Unlike the test loss
+    they do not depend on the trial's beta, so trials of a beta sweep compare.
+    Runs after the trial's wall time was taken: samples/s is unaffected."""
+    K = int(opts.iw_samples)
+    t = time.perf_counter()
+    idx = torch.arange(len(test), dtype=torch.int32, device=test.data.device)
+    with trace.range("iw_eval"):
+        r = trainer.evaluate_iw(test.data, idx, K)
+        if device.type == "cuda":
+            torch.cuda.synchronize(device)
+    out = dict(iw_nll=r["nll"] / len(test), iw_neg_elbo=r["neg_elbo"] / len(test), iw_samples=K,
+               iw_s=round(time.perf_counter() - t, 6))
+    print0(tag + "====> Test set IW-{} NLL: {:.4f} ELBO-{}: {:.4f}".format(K, out["iw_nll"], K, out["iw_neg_elbo"]),
+           process_group=group)
+    metrics.log(event="iw_eval", **out)
+    return out
+
+
 def run_trial(spec: TrialSpec, group, opts: RunOptions, data=None, num_trials: Optional[int] = None) -> TrialResult:
     """Train one trial on the ranks of ``group`` (this rank is a member)."""
     world_rank = dist.get_rank() if dist.is_initialized() else 0
@@ -466,8 +488,14 @@ def run_trial(spec: TrialSpec, group, opts: RunOptions, data=None, num_trials: O
     global_barrier()  # parity: vae-hpo.py:172 (waits for the slowest trial)
     t1 = time.time()
     print(world_rank, "Done. time: %f" % (t1 - t0), flush=True)
+    extra = {}
+    if opts.iw_samples > 0 and not failure:
+        with guarded(f"trial {spec.group_id} IW pass (world rank {world_rank})", None,
+                     lambda e: failure.setdefault("error", f"{type(e).__name__}: {e}")):
+            extra = _iw_eval(trainer, test, opts, group, metrics, device)
     return TrialResult(spec.group_id, epochs_done, n_shard, epochs_done * n_shard, t1 - t0,
-                       train_loss / len(train), test_loss, failed=bool(failure), error=failure.get("error", ""))
+                       train_loss / len(train), test_loss, failed=bool(failure), error=failure.get("error", ""),
+                       extra=extra)
 
 
 def _run_epoch(trainer, epoch, n_shard, train, test, opts, group, rdir, shape, gen, device, spec, grank, metrics,
@@ -592,9 +620,16 @@ def run_packed_trials(specs, group, opts: RunOptions, data=None, num_trials: Opt
     global_barrier()
     t1 = time.time()
     print(world_rank, "Done. time: %f" % (t1 - t0), flush=True)
+    for t in tr:
+        t["extra"] = {}
+        if opts.iw_samples > 0 and not t["failure"]:
+            with guarded(f"trial {t['spec'].group_id} IW pass (world rank {world_rank})", None,
+                         lambda e, t=t: t["failure"].setdefault("error", f"{type(e).__name__}: {e}")):
+                t["extra"] = _iw_eval(t["trainer"], test, opts, group, t["metrics"], device,
+                                      tag=f"(trial {t['spec'].group_id}) ")
     return [TrialResult(t["spec"].group_id, t["done"], t["n_shard"], t["done"] * t["n_shard"], t1 - t0,
                         t["train_loss"] / len(train), t["test_loss"], failed=bool(t["failure"]),
-                        error=t["failure"].get("error", "")) for t in tr]
+                        error=t["failure"].get("error", ""), extra=t["extra"]) for t in tr]
 
 
 def idle_rank():

@@ -39,7 +39,8 @@ from torch import nn
 from ..hpo.schedule import Schedule
 from ..ops import native
 from ..ops.philox import reparam_eps
-from .eval_graphs import GraphedEval
+from .eval_graphs import GraphedEval, GraphedIwEval
+from .iw import iw_log_weights
 from .mlp_vae import reference_adam_
 
 __all__ = ["Layer", "conv_vae_spec", "TorchConvVAE", "ConvVaeTrainer", "conv_layout"]
@@ -201,7 +202,7 @@ class TorchConvVAE(nn.Module):
 
 
 # --------------------------------------------------------------------------
-class ConvVaeTrainer(GraphedEval):
+class ConvVaeTrainer(GraphedEval, GraphedIwEval):
     """One trial of the conv VAE. Same driver-facing API as MlpVaeTrainer."""
 
     def __init__(self, batch_size: int = 128, image: int = 28, channels: int = 1, z: int = 32, device=None,
@@ -822,10 +823,12 @@ class ConvVaeTrainer(GraphedEval):
         else:
             self.C.igemm(0, h, self._w(l), d, self._b(l), l.relu, o16, o32, ws=ws, fwd=True, **pro)
 
-    def _forward_hip(self, M, state, stream, want_recon=False, train=True, src=None):
+    def _forward_hip(self, M, state, stream, want_recon=False, train=True, src=None, enc_only=False):
         """Forward of one batch. ``src = (X, idx)``: the batch is gathered from
         the dataset by the step's first kernel (and the step begun there) when
-        the first layer runs on the direct kernel; otherwise by gather_rows."""
+        the first layer runs on the direct kernel; otherwise by gather_rows.
+        ``enc_only``: stop once ``self.mulv`` is written (the importance-weighted
+        pass draws its own samples and runs the decoder per chunk)."""
         C = self.C
         p = self._plan(M)
         hp = self.state.hparams
@@ -875,11 +878,15 @@ class ConvVaeTrainer(GraphedEval):
                             combine=False, fwd=True, **pro)
                     C.combine_reparam(p["ws"], q[10], self._b(l), self.mulv, self.eps, self.z16, None, M, self.Z,
                                       state, hp, stream, self.kld_part)
+                    if enc_only:
+                        return
                     break
             self._layer_fwd(l, h, M, None if last else self.acts[l.name], self.mulv if last else None, p["ws"],
                             **(pro if last else {}))
             h = self.acts[l.name]
         else:
+            if enc_only:
+                return
             C.reparam(self.mulv, self.eps, self.z16, None, M, self.Z, state, hp, stream, self.kld_part)
         h = self.z16
         for l in dec:
@@ -1616,6 +1623,68 @@ class ConvVaeTrainer(GraphedEval):
                 st["epoch_count"] += 1
                 st["step"] += 1
         return self.read_state(eval=True)["epoch_loss"], first
+
+    # importance-weighted log-likelihood pass (models/eval_graphs.py::GraphedIwEval.evaluate_iw)
+    def _iw_logw_torch(self, x, eps):
+        mu, lv = self.model.encode(x)
+        dec = lambda z: self.model.decode_logits(z).permute(0, 2, 3, 1).reshape(z.shape[0], self.D)
+        return iw_log_weights(mu, lv, eps, x, dec)[0]
+
+    def _iw_prepare(self):
+        self._ensure_wt()  # the decoder's parity-mode layers read the transposed copies, as in evaluate() / decode()
+        if getattr(self, "iw_state", None) is None:
+            f32 = dict(dtype=torch.float32, device=self.device)
+            self.iw_state = self.C.iw_state_new(self.device.index or 0)
+            self.iw_eps = torch.zeros(self.B, self.Z, **f32)
+            self.iw_z = torch.zeros(self.B, self.Z, **f32)
+            self.iw_prior = torch.zeros(self.B, **f32)
+            self.iw_bce = torch.zeros(self.B, **f32)
+            self.iw_rowbuf = torch.zeros(3, self.B, **f32)
+
+    def _iw_begin(self, nbatches):
+        self.C.iw_state_begin(self.iw_state, nbatches)
+
+    def _iw_batch(self, M, X, idx, k, S, rows):
+        """One batch at the pass cursor: the layer-path encoder once (also at
+        28x28: the fused forward cannot emit K decodes), then the samples in
+        chunks of at most B virtual rows v = s*M + i through the decoder layers
+        exactly as ``decode()`` runs them, the per-row BCE and the shared
+        reduce kernel (which advances the pass cursor after the last chunk)."""
+        C, st, hp = self.C, self.iw_state, self.state.hparams
+        self._forward_hip(M, st, 0, train=False, src=(X, idx), enc_only=True)
+        dec = [l for l in self.spec if l.name.startswith("dec")]
+        Sc = max(1, min(S, self.B // M))
+        for k0 in range(0, k, Sc):
+            s = min(Sc, k - k0)
+            V = s * M
+            C.iw_reparam(self.mulv, M, self.B, self.Z, k0, s, st, hp, self.z16, self.iw_z, self.iw_eps, self.iw_prior)
+            h = self.z16
+            ws = self._plan(V)["ws"]
+            for l in dec:
+                last = l is dec[-1]
+                self._layer_fwd(l, h, V, None if last else self.acts[l.name], self.logits if last else None, ws)
+                h = self.acts[l.name]
+            C.iw_row_bce(self.logits, self.xb, V, M, self.D, self.iw_bce)
+            C.iw_reduce(self.iw_prior, self.iw_bce, self.iw_rowbuf, rows[0], rows[1], st, M, self.B, k, s,
+                        k0 == 0, k0 + s >= k)
+
+    def _iw_state(self):
+        return self.iw_state
+
+    def _iw_ws_token(self):
+        return 0  # fixed-size buffers (a chunk holds at most B virtual rows)
+
+    def _iw_read(self):
+        r = self.C.iw_state_read(self.iw_state)
+        return r[0], r[1]
+
+    def iw_buffers(self, S: int, M: int):
+        """hip backend: ``mulv[M, 2Z]`` of the last batch of the last
+        ``evaluate_iw`` pass and ``eps`` / ``z`` ``[S, M, Z]`` (f32, before the
+        decoder's bf16 rounding) of its last chunk of S samples (copies)."""
+        n = S * M
+        return dict(mulv=self.mulv[:M].clone(), eps=self.iw_eps.view(-1)[: n * self.Z].view(S, M, self.Z).clone(),
+                    z=self.iw_z.view(-1)[: n * self.Z].view(S, M, self.Z).clone())
 
     @torch.no_grad()
     def decode(self, zz):

@@ -23,11 +23,13 @@ in the same order).
 
 from __future__ import annotations
 
+import numpy as np
 import torch
 
 from ..ops import native
+from .iw import check_iw_args, default_chunk, iw_eps, iw_reduce
 
-__all__ = ["GraphedEval"]
+__all__ = ["GraphedEval", "GraphedIwEval"]
 
 
 class GraphedEval:
@@ -93,3 +95,120 @@ class GraphedEval:
             if tail:
                 self._eval_graph(1, tail, X, idx).replay()
         return first
+
+
+class GraphedIwEval:
+    """Mixin: ``evaluate_iw``, the importance-weighted log-likelihood pass
+    (models/iw.py), eager or graph-replayed like ``GraphedEval``'s passes and
+    independent of them (own index buffer, own graphs, own device state).
+
+    Requires ``self.B``, ``self.Z``, ``self.seed``, ``self.device``,
+    ``self.backend``, ``self.use_graphs`` and
+
+    * torch backend: ``self._iw_logw_torch(x, eps) -> logw[K, M]``;
+    * hip backend: ``self._iw_prepare()`` (once per pass, before any launch),
+      ``self._iw_begin(nbatches)`` (zero the pass state),
+      ``self._iw_batch(M, X, idx, k, S, rows)`` (launch one batch at the pass
+      cursor; ``rows`` is the float32 [2, nbatches*B] per-row result buffer),
+      ``self._iw_state()`` (the pass's device state tensor),
+      ``self._iw_read() -> (nll, neg_elbo)`` and ``self._iw_ws_token()`` (a
+      value that changes whenever a workspace the launches use is reallocated).
+    """
+
+    _iw_idx = None
+    _iw_rows = None
+    _iw_graphs = None
+    _iw_xkey = None
+
+    def _iw_bind(self, idx_padded: torch.Tensor):
+        n = idx_padded.numel()
+        buf = self._iw_idx
+        if buf is None or buf.numel() != n:
+            self._iw_idx = buf = torch.empty(n, dtype=torch.int32, device=self.device)
+            self._iw_rows = torch.zeros(2, n, dtype=torch.float32, device=self.device)
+            self._iw_graphs = {}
+        buf.copy_(idx_padded)
+        return buf, self._iw_rows
+
+    def _iw_graph(self, nbat: int, M: int, k: int, S: int, X: torch.Tensor, idx: torch.Tensor, rows: torch.Tensor):
+        # batch 0 of this pass already ran eagerly at this (k, S): the workspaces have their final size
+        xkey = (X.data_ptr(), X.shape[0], idx.data_ptr(), rows.data_ptr(), self._iw_ws_token())
+        if self._iw_xkey != xkey:  # graphs of the latest eval set (and workspace) only, as GraphedEval
+            self._iw_graphs = {}
+            self._iw_xkey = xkey
+        key = (nbat, M, k, S)
+        g = self._iw_graphs.get(key)
+        if g is None:
+            st = self._iw_state()
+            snap = st.clone()
+            cur = torch.cuda.current_stream()
+            s = torch.cuda.Stream()
+            s.wait_stream(cur)
+            with torch.cuda.stream(s):
+                self._iw_batch(M, X, idx, k, S, rows)  # warm-up: workspaces exist before capture
+            cur.wait_stream(s)
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                for _ in range(nbat):
+                    self._iw_batch(M, X, idx, k, S, rows)
+            st.copy_(snap)
+            native.upload_graph(g)
+            self._iw_graphs[key] = g
+        return g
+
+    @torch.no_grad()
+    def evaluate_iw(self, X: torch.Tensor, idx: torch.Tensor, k: int, chunk_samples=None, return_rows: bool = False):
+        """K-sample importance-weighted bound on -log p(x) and the K-sample
+        negative ELBO (beta = 1) over rows ``X[idx]``, from the same draws.
+
+        Returns ``dict(nll, neg_elbo, rows, k)`` (sums over the rows; with
+        ``return_rows`` also float32 ``row_nll[n]`` / ``row_neg_elbo[n]``).
+        The samples run in chunks of ``chunk_samples`` (default: as many as
+        keep chunk x batch within 8192 decoder rows). Training and eval state
+        are not touched; the result does not depend on ``rng_stream``."""
+        check_iw_args(k, self.B, self.Z)
+        k = int(k)
+        S = default_chunk(k, self.B, chunk_samples)
+        B = self.B
+        idx = idx.to(device=self.device, dtype=torch.int32).contiguous()
+        n = idx.numel()
+        if n == 0:
+            raise ValueError("evaluate_iw needs at least one row")
+        nb = -(-n // B)
+        X = X.contiguous()
+        if self.backend != "hip":
+            rn, re = [], []
+            for b in range(nb):
+                M = min(B, n - b * B)
+                x = X[idx[b * B: b * B + M].long()]
+                eps = torch.from_numpy(np.ascontiguousarray(iw_eps(k, B, self.Z, self.seed, b)[:, :M])).to(self.device)
+                logw = torch.cat([self._iw_logw_torch(x, eps[s: s + S]) for s in range(0, k, S)], 0)
+                a, e = iw_reduce(logw)
+                rn.append(a.float())
+                re.append(e.float())
+            row_nll, row_ne = torch.cat(rn), torch.cat(re)
+            nll, ne = float(row_nll.double().sum()), float(row_ne.double().sum())
+        else:
+            pad = nb * B - n
+            if pad:
+                idx = torch.cat([idx, idx[:1].expand(pad)])  # never read (rows >= M)
+            self._iw_prepare()
+            ibuf, rows = self._iw_bind(idx)
+            self._iw_begin(nb)
+            if self.use_graphs:
+                self._iw_batch(min(B, n), X, ibuf, k, S, rows)
+                full, tail = n // B, n % B
+                if n > B:
+                    if full > 1:
+                        self._iw_graph(full - 1, B, k, S, X, ibuf, rows).replay()
+                    if tail:
+                        self._iw_graph(1, tail, k, S, X, ibuf, rows).replay()
+            else:
+                for b in range(nb):
+                    self._iw_batch(min(B, n - b * B), X, ibuf, k, S, rows)
+            nll, ne = self._iw_read()
+            row_nll, row_ne = rows[0, :n], rows[1, :n]
+        out = dict(nll=float(nll), neg_elbo=float(ne), rows=n, k=k)
+        if return_rows:
+            out["row_nll"], out["row_neg_elbo"] = row_nll.clone(), row_ne.clone()
+        return out

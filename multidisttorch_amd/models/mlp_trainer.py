@@ -31,7 +31,8 @@ import torch
 from ..hpo.schedule import Schedule
 from ..ops import native
 from ..ops.philox import reparam_eps
-from .eval_graphs import GraphedEval
+from .eval_graphs import GraphedEval, GraphedIwEval
+from .iw import mlp_iw_log_weights
 from .mlp_vae import arena_layout, init_params_, reference_adam_, reference_forward, reference_step, views
 
 __all__ = ["MlpVaeTrainer"]
@@ -40,7 +41,7 @@ EVAL_STREAM = 1 << 30
 LOSS_HIST = 4096
 
 
-class MlpVaeTrainer(GraphedEval):
+class MlpVaeTrainer(GraphedEval, GraphedIwEval):
     def __init__(self, batch_size: int = 128, D: int = 784, H: int = 400, Z: int = 20,
                  device=None, backend: Optional[str] = None, seed: int = 0, init_seed: Optional[int] = None,
                  lr: float = 1e-3, kl_beta: float = 1.0, betas=(0.9, 0.999), eps: float = 1e-8,
@@ -462,6 +463,37 @@ class MlpVaeTrainer(GraphedEval):
                 st["step"] += 1
                 st["cursor"] = (st["cursor"] + 1) % nb
         return self.read_state(eval=True)["epoch_loss"], first
+
+    # importance-weighted log-likelihood pass (models/eval_graphs.py::GraphedIwEval.evaluate_iw)
+    def _iw_logw_torch(self, x, eps):
+        return mlp_iw_log_weights(self.named_parameters(), x, eps)[0]
+
+    def _iw_prepare(self):
+        pass
+
+    def _iw_begin(self, nbatches):
+        self.engine.iw_begin(nbatches)
+
+    def _iw_batch(self, M, X, idx, k, S, rows):
+        # encoder once (F1), then per chunk: sample, decoder + per-row BCE, reduce (csrc/kernels/vae_iw.hip)
+        self.engine.iw_batch(X, idx, M, k, S, rows[0], rows[1])
+
+    def _iw_state(self):
+        return self.engine.iw_state
+
+    def _iw_ws_token(self):
+        return self.engine.iw_capacity()  # the engine's chunk workspace grows with chunk_samples
+
+    def _iw_read(self):
+        r = self.engine.iw_read()
+        return r[0], r[1]
+
+    def iw_buffers(self, S: int, M: int) -> Dict[str, torch.Tensor]:
+        """hip backend: ``mulv[M, 2Z]`` of the last batch of the last
+        ``evaluate_iw`` pass and ``eps`` / ``z`` ``[S, M, Z]`` of its last chunk
+        of S samples (copies)."""
+        e = self.engine
+        return dict(mulv=e.act("mulv", M).clone(), eps=e.iw_act("eps", S, M).clone(), z=e.iw_act("z", S, M).clone())
 
     @torch.no_grad()
     def decode(self, z: torch.Tensor) -> torch.Tensor:

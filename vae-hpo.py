@@ -14,7 +14,9 @@ multidisttorch_amd/hpo/schedule.py), ``--seed``, ``--ckpt-dir`` + ``--resume``,
 ``--metrics-dir`` (JSONL + aggregate samples/s), ``--per-group-results``, ``--bucket-mb``,
 ``--no-graphs``, ``--backend {hip,torch}``, ``--synthetic/--real-data``,
 ``--trials-per-group T`` (T concurrent trials per single-rank group, one HIP
-stream each: trial packing on MI355X).
+stream each: trial packing on MI355X), ``--iw-samples K`` (after each trial's
+last epoch: the K-sample importance-weighted test log-likelihood, a score that
+does not depend on the trial's beta).
 """
 
 import argparse
@@ -83,6 +85,9 @@ def parse_args(argv=None):
                         help="train T trials concurrently per (single-rank) group, one HIP stream each")
     parser.add_argument("--bucket-mb", type=str, default=None,
                         help="intra-group all-reduce buckets: MiB cap, 0 = one bucket, 'auto' = measured")
+    parser.add_argument("--iw-samples", type=int, default=0, metavar="K",
+                        help="after each trial's last epoch: K-sample importance-weighted test log-likelihood "
+                             "(a beta-independent score; 0 = off)")
     return parser.parse_args(argv)
 
 
@@ -123,7 +128,7 @@ def main(argv=None):
                       data_dir=args.data_dir,
                       synthetic=False if args.real_data else (True if args.synthetic else None),
                       model=args.model, image_size=args.image_size, bucket_mb=parse_bucket_mb(args.bucket_mb),
-                      profile=args.profile)
+                      profile=args.profile, iw_samples=max(0, args.iw_samples))
     results = []
     member = False
     for group_id, group in enumerate(processes_groups):
@@ -138,13 +143,16 @@ def main(argv=None):
         idle_rank()
 
     # aggregate samples/s: samples once per trial, max wall over ranks
-    mine = [(r.group_id, r.samples, r.wall_s, r.failed) for r in results]
+    mine = [(r.group_id, r.samples, r.wall_s, r.failed) + ((r.extra.get("iw_nll"),) if opts.iw_samples > 0 else ())
+            for r in results]
     gathered = [None] * dist.get_world_size()
     dist.all_gather_object(gathered, mine, group=control_group())
     if dist.get_rank() == 0:
-        per_trial, wall, failed = {}, 0.0, set()
+        per_trial, wall, failed, iw_nll = {}, 0.0, set(), {}
         for lst in gathered:
-            for gid, samples, w, bad in lst or []:
+            for gid, samples, w, bad, *iw in lst or []:
+                if iw and iw[0] is not None:
+                    iw_nll[gid] = iw[0]
                 per_trial[gid] = min(per_trial.get(gid, samples), samples)
                 wall = max(wall, w)
                 if bad:
@@ -154,6 +162,11 @@ def main(argv=None):
                    "wall_s": round(wall, 4),
                    "value": round(sum(per_trial.values()) / max(wall, 1e-9), 1), "unit": "samples/s",
                    "failed_trials": sorted(failed)}
+        if opts.iw_samples > 0:
+            # per-image means over the test set; the lowest bound on -log p(x) is the best trial
+            summary["iw_samples"] = opts.iw_samples
+            summary["iw_nll"] = {str(g): round(v, 4) for g, v in sorted(iw_nll.items())}
+            summary["best_trial_by_iw_nll"] = min(iw_nll, key=lambda g: (iw_nll[g], g)) if iw_nll else None
         if args.metrics_dir:
             os.makedirs(args.metrics_dir, exist_ok=True)
             with open(os.path.join(args.metrics_dir, "aggregate.json"), "w") as f:
