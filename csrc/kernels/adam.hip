@@ -23,7 +23,7 @@ struct AdamArgs {
 
 __global__ void __launch_bounds__(512) adam_flat(AdamArgs a) {
   __shared__ AdamC cs;
-  const AdamC c = adam_consts_block(a.st, a.hp, &cs);
+  const AdamC c = adam_consts_block(a.st, a.hp, &cs, true);
   adam_stream(a.p, a.g, a.m, a.v, 0, a.n4 * 4, blockIdx.x, gridDim.x, c);
 }
 

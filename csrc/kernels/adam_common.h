@@ -9,12 +9,22 @@ namespace mdt {
 struct AdamC {
   float step_size, bc2s, b1, b2, eps, wd, gs, lr;
   int decoupled;
+  // The weights 1 - beta of the two moment updates. torch passes `1 - beta2` as a
+  // double scalar, so its f32 weight is (float)(1 - 0.999) = 0.001f; 1.f - (float)0.999
+  // is 1.3e-5 below it (exp_avg_sq off by that factor: outside rtol 1e-5 once
+  // g^2 > 77). The MLP-VAE kernels (vae_mlp.hip, adam.hip) ask for torch's value
+  // (`torch_omb`); the conv-VAE kernels keep the f32 difference they have always
+  // trained with (docs/KERNELS.md, "MLP-VAE shape domain"). The struct stays
+  // within the 64 bytes the job kernels reserve for it.
+  float omb1, omb2;
 };
+static_assert(sizeof(AdamC) <= 64, "conv_jobs.hip / comm_jobs.h reserve 64 bytes of LDS for AdamC");
 
 // Compute once per block (thread 0, double precision like torch's Python-side
 // scalars) and broadcast through LDS. beta^t comes from the running products
 // F1 keeps in TrainState (t = st->step, 1-based), so no pow() on the device.
-__device__ __forceinline__ AdamC adam_consts_block(const TrainState* st, const HParams* hp, AdamC* sh) {
+__device__ __forceinline__ AdamC adam_consts_block(const TrainState* st, const HParams* hp, AdamC* sh,
+                                                   bool torch_omb = false) {
   if (threadIdx.x == 0) {
     const double bc1 = 1.0 - st->b1pow;
     const double bc2 = 1.0 - st->b2pow;
@@ -24,6 +34,8 @@ __device__ __forceinline__ AdamC adam_consts_block(const TrainState* st, const H
     c.bc2s = (float)sqrt(bc2);
     c.b1 = hp->beta1; c.b2 = hp->beta2; c.eps = hp->eps; c.wd = hp->weight_decay;
     c.gs = hp->grad_scale; c.lr = (float)lr_t; c.decoupled = hp->decoupled_wd;
+    c.omb1 = torch_omb ? (float)(1.0 - hp->beta1_d) : 1.f - c.b1;
+    c.omb2 = torch_omb ? (float)(1.0 - hp->beta2_d) : 1.f - c.b2;
     *sh = c;
   }
   __syncthreads();
@@ -48,6 +60,7 @@ __device__ __forceinline__ AdamC adam_consts_block_sc1(const TrainState* st, con
     c.bc2s = (float)sqrt(1.0 - b2pow);
     c.b1 = hp->beta1; c.b2 = hp->beta2; c.eps = hp->eps; c.wd = hp->weight_decay;
     c.gs = hp->grad_scale; c.lr = (float)lr_t; c.decoupled = hp->decoupled_wd;
+    c.omb1 = 1.f - c.b1; c.omb2 = 1.f - c.b2;
     *sh = c;
   }
   __syncthreads();
@@ -60,8 +73,8 @@ __device__ __forceinline__ void adam_update(float& p, float& m, float& v, float 
     if (c.decoupled) p *= (1.f - c.lr * c.wd);
     else gr = fmaf(c.wd, p, gr);
   }
-  m = fmaf(1.f - c.b1, gr - m, m);          // exp_avg.lerp_(g, 1-b1)
-  v = fmaf(1.f - c.b2, gr * gr, v * c.b2);  // exp_avg_sq.mul_(b2).addcmul_(g, g, 1-b2)
+  m = fmaf(c.omb1, gr - m, m);             // exp_avg.lerp_(g, 1-b1)
+  v = fmaf(c.omb2, gr * gr, v * c.b2);     // exp_avg_sq.mul_(b2).addcmul_(g, g, 1-b2)
   const float denom = sqrtf(v) / c.bc2s + c.eps;
   p = p - c.step_size * (m / denom);        // param.addcdiv_(m, denom, -step_size)
 }

@@ -616,7 +616,7 @@ __global__ void __launch_bounds__(kThreads) vae_b3(VaeArgs a, int nblk_w2, int n
     STAMP(5, 1);
     return;
   }
-  const AdamC c = adam_consts_block(a.st, a.hp, &cs);
+  const AdamC c = adam_consts_block(a.st, a.hp, &cs, true);
   if (bid < nblk_w2) {
     ATrans A{a.dmulv, Z2, Z2, a.M};
     BRowMajor Bh{a.h1, a.H, a.H, a.M};

@@ -180,8 +180,10 @@ class MlpCpuStep {
     float* v = Vo.data_ptr<float>();
     const double bc1 = 1.0 - std::pow(beta1, (double)step), bc2 = 1.0 - std::pow(beta2, (double)step);
     const float step_size = (float)(lr / bc1), bc2s = (float)std::sqrt(bc2);
-    const float b1 = (float)beta1, b2 = (float)beta2, fe = (float)eps, fwd = (float)wd, fgs = (float)gs;
+    const float b2 = (float)beta2, fe = (float)eps, fwd = (float)wd, fgs = (float)gs;
     const float decay = (float)(1.0 - lr * wd);
+    // 1 - beta in double, then rounded, as torch's scalar arguments: 1.f - (float)0.999 is 1.3e-5 off 0.001f
+    const float omb1 = (float)(1.0 - beta1), omb2 = (float)(1.0 - beta2);
     at::parallel_for(0, P.numel(), 16384, [&](int64_t a, int64_t b) {
       for (int64_t i = a; i < b; ++i) {
         float gr = g[i] * fgs;
@@ -190,8 +192,8 @@ class MlpCpuStep {
           if (decoupled) pi *= decay;
           else gr += fwd * pi;
         }
-        const float mi = m[i] + (1.f - b1) * (gr - m[i]);
-        const float vi = v[i] * b2 + (1.f - b2) * gr * gr;
+        const float mi = m[i] + omb1 * (gr - m[i]);
+        const float vi = v[i] * b2 + omb2 * gr * gr;
         m[i] = mi;
         v[i] = vi;
         p[i] = pi - step_size * (mi / (std::sqrt(vi) / bc2s + fe));

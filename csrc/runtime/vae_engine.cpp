@@ -29,9 +29,23 @@ static void check_rc(int rc, const char* what) {
 
 MlpVaeEngine::MlpVaeEngine(int64_t batch, int64_t D, int64_t H, int64_t Z, int64_t device_index)
     : B_(batch), D_(D), H_(H), Z_(Z) {
-  TORCH_CHECK(batch > 0 && batch <= kMaxBatch, "batch must be in [1, ", kMaxBatch, "]");
-  TORCH_CHECK(Z > 0 && Z <= 32, "latent size must be in [1, 32]");
-  TORCH_CHECK(D % 4 == 0 && H % 4 == 0, "D and H must be multiples of 4");
+  // Every shape-only condition of mdt_vae_check at M = B (docs/KERNELS.md, "MLP-VAE
+  // shape domain"): an unsupported shape fails here, by name, not as a return
+  // code of the first step. The kernel-side checks stay (they also see M).
+  TORCH_CHECK(batch > 0 && batch <= kMaxBatch, "MlpVaeEngine: batch size ", batch, " must be in [1, ", kMaxBatch,
+              "]");
+  TORCH_CHECK(Z >= 4 && Z <= 32 && Z % 4 == 0, "MlpVaeEngine: latent size Z = ", Z,
+              " must be a multiple of 4 in [4, 32]");
+  TORCH_CHECK(D >= 4 && D % 4 == 0, "MlpVaeEngine: input size D = ", D, " must be a positive multiple of 4");
+  TORCH_CHECK(H >= 4 && H % 4 == 0, "MlpVaeEngine: hidden size H = ", H, " must be a positive multiple of 4");
+  TORCH_CHECK(H <= 16 * 32, "MlpVaeEngine: hidden size H = ", H, " exceeds the limit of 512 (32 slab slices of 16)");
+  const int64_t row_tiles = (batch + 15) / 16;
+  const int64_t kld_slots = row_tiles * 8, kld_cap = kBcePartial - kKldPartial;
+  TORCH_CHECK(kld_slots <= kld_cap, "MlpVaeEngine: batch size ", batch, " needs ", kld_slots,
+              " KLD partial slots (ceil(B/16)*8), limit ", kld_cap);
+  const int64_t bce_slots = (row_tiles * ((D + 15) / 16) + 1) / 2 * 8, bce_cap = kPartials - kBcePartial;
+  TORCH_CHECK(bce_slots <= bce_cap, "MlpVaeEngine: batch size ", batch, " with D = ", D, " needs ", bce_slots,
+              " BCE partial slots (ceil(ceil(B/16)*ceil(D/16)/2)*8), limit ", bce_cap);
   int64_t off = 0;
   auto add = [&](const std::string& n, std::vector<int64_t> shape, int64_t numel) {
     layout_.push_back({n, off, shape});
@@ -343,6 +357,9 @@ void MlpVaeEngine::iw_batch(const at::Tensor& X, const at::Tensor& idx, int64_t 
   c10::hip::HIPGuardMasqueradingAsCUDA guard(params.device());
   TORCH_CHECK(K >= 1 && chunk >= 1, "iw_batch: K and chunk must be >= 1");
   TORCH_CHECK((uint64_t)K * (uint64_t)B_ * (uint64_t)Z_ <= (1ull << 32), "iw_batch: K*B*Z exceeds 2^32");
+  // mdt_iw_check's shape condition, before the encoder is launched
+  TORCH_CHECK(kIwRowTile * ((H_ + 15) / 16 * 16 + 4) * (int64_t)sizeof(float) <= kIwMaxLds, "iw_batch: hidden size H = ",
+              H_, " exceeds the importance-weighted pass's limit of 496 (64 KiB LDS decoder tile)");
   TORCH_CHECK(iw_nbatches_ > 0, "iw_batch: call iw_begin first");
   TORCH_CHECK(idx.numel() >= iw_nbatches_ * B_, "iw_batch: idx shorter than nbatches * B");
   for (const at::Tensor* t : {&row_nll, &row_neg_elbo})

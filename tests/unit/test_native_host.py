@@ -66,3 +66,19 @@ def test_thin_mfma_wgrad_plan(M):
                 assert info[0] == 110 and info[6] == M * 64 // 4 and info[1] == 32 and info[2] == 16, info
             else:
                 assert info[0] != 110, info
+
+
+@pytest.mark.parametrize("args,msg", [
+    ((32, 64, 64, 10), r"latent size Z = 10 must be a multiple of 4 in \[4, 32\]"),
+    ((32, 64, 64, 36), r"latent size Z = 36"),
+    ((32, 64, 402, 8), r"hidden size H = 402 must be a positive multiple of 4"),
+    ((32, 64, 516, 8), r"hidden size H = 516 exceeds the limit of 512"),
+    ((32, 30, 64, 8), r"input size D = 30 must be a positive multiple of 4"),
+    ((4097, 64, 64, 8), r"batch size 4097 must be in \[1, 4096\]"),
+    ((512, 16384, 64, 8), r"needs 131072 BCE partial slots .* limit 65536"),
+])
+def test_mlp_engine_refuses_unsupported_shapes_by_name(args, msg):
+    """MlpVaeEngine's shape checks (docs/KERNELS.md, "MLP-VAE shape domain") come
+    before any allocation, so they hold on a host without a GPU too."""
+    with pytest.raises(RuntimeError, match=msg):
+        native.require().MlpVaeEngine(*args, 0)
