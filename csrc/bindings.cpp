@@ -17,6 +17,7 @@ void bind_rccl(pybind11::module& m);
 void bind_p2p(pybind11::module& m);
 void bind_cpu(pybind11::module& m);
 void bind_iw(pybind11::module& m);
+void bind_latent(pybind11::module& m);
 }  // namespace mdt
 
 PYBIND11_MODULE(_C, m) {
@@ -32,6 +33,7 @@ PYBIND11_MODULE(_C, m) {
   mdt::bind_p2p(m);
   mdt::bind_cpu(m);
   mdt::bind_iw(m);
+  mdt::bind_latent(m);
 
   py::class_<mdt::MlpVaeEngine>(m, "MlpVaeEngine")
       .def(py::init<int64_t, int64_t, int64_t, int64_t, int64_t>(), py::arg("batch"),
@@ -65,6 +67,11 @@ PYBIND11_MODULE(_C, m) {
       .def("iw_capacity", &mdt::MlpVaeEngine::iw_capacity)
       .def("iw_act", &mdt::MlpVaeEngine::iw_act, py::arg("name"), py::arg("S"), py::arg("M"))
       .def_readonly("iw_state", &mdt::MlpVaeEngine::iw_state)
+      .def("latent_begin", &mdt::MlpVaeEngine::latent_begin, py::arg("nbatches"))
+      .def("latent_batch", &mdt::MlpVaeEngine::latent_batch, py::arg("X"), py::arg("idx"), py::arg("M"),
+           py::arg("rows"))
+      .def("latent_read", &mdt::MlpVaeEngine::latent_read)
+      .def_readonly("latent_state", &mdt::MlpVaeEngine::latent_state)
       .def_readonly("params", &mdt::MlpVaeEngine::params)
       .def_readonly("grads", &mdt::MlpVaeEngine::grads)
       .def_readonly("exp_avg", &mdt::MlpVaeEngine::exp_avg)

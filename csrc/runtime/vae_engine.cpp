@@ -8,6 +8,7 @@
 #include <stdexcept>
 
 #include "../kernels/vae_iw.h"
+#include "../kernels/vae_latent.h"
 #include "../kernels/vae_mlp.h"
 #include "sched_host.h"
 
@@ -415,6 +416,34 @@ at::Tensor MlpVaeEngine::iw_act(const std::string& name, int64_t S, int64_t M) {
   if (name == "z") off += align64(iw_cap_ * Z_);
   else TORCH_CHECK(name == "eps", "iw_act: unknown buffer ", name);
   return iw_ws_.narrow(0, off, S * M * Z_).view({S, M, Z_});
+}
+
+// ------------------------------------------------------ latent report pass ----
+void MlpVaeEngine::latent_begin(int64_t nbatches) {
+  if (!latent_state.defined()) latent_state = latent_state_new(params.device().index());
+  latent_state_begin(latent_state, nbatches);
+  latent_nbatches_ = nbatches;
+}
+
+void MlpVaeEngine::latent_batch(const at::Tensor& X, const at::Tensor& idx, int64_t M, at::Tensor rows) {
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(params.device());
+  TORCH_CHECK(latent_nbatches_ > 0, "latent_batch: call latent_begin first");
+  TORCH_CHECK(idx.numel() >= latent_nbatches_ * B_, "latent_batch: idx shorter than nbatches * B");
+  TORCH_CHECK(rows.is_cuda() && rows.scalar_type() == torch::kFloat32 && rows.is_contiguous() &&
+                  rows.numel() >= latent_nbatches_ * B_ * 2 * Z_,
+              "latent_batch: rows must be contiguous CUDA float32 of >= nbatches * B * 2Z elements");
+  VaeArgs a;
+  fill_args(&a, X, idx, M, false, true, 0, false);
+  a.st = reinterpret_cast<TrainState*>(latent_state.data_ptr<uint8_t>());  // LatentState begins with its TrainState
+  hipStream_t stream = c10::hip::getCurrentHIPStream().stream();
+  check_rc(mdt_vae_encode(&a, stream), "latent encoder");
+  check_rc(mdt_latent_mulv(&a, stream), "latent mulv");
+  latent_collect(act("mulv", M), M, B_, Z_, rows, latent_state);
+}
+
+std::vector<double> MlpVaeEngine::latent_read() {
+  TORCH_CHECK(latent_state.defined(), "latent_read: no pass has run");
+  return latent_state_read(latent_state);
 }
 
 // ----------------------------------------------- conv-VAE pass: small ops ----

@@ -33,6 +33,15 @@ at::Tensor iw_state_new(int64_t device_index);
 void iw_state_begin(at::Tensor state, int64_t nbatches);
 std::vector<double> iw_state_read(const at::Tensor& state);
 
+// Device state of a latent report pass (kernels/vae_latent.h: LatentState),
+// shared by both trainers like the iw state (csrc/runtime/latent_ops.cpp):
+// read back {kl, mi, tc, dwkl, sampled_kl, step (batches begun), cursor}.
+at::Tensor latent_state_new(int64_t device_index);
+void latent_state_begin(at::Tensor state, int64_t nbatches);
+std::vector<double> latent_state_read(const at::Tensor& state);
+// Batch rows mulv[:M] -> pass rows cursor*B + i of `rows` [*, 2Z]; advances the pass cursor.
+void latent_collect(const at::Tensor& mulv, int64_t M, int64_t B, int64_t Z, at::Tensor rows, at::Tensor state);
+
 class MlpVaeEngine {
  public:
   MlpVaeEngine(int64_t batch, int64_t D, int64_t H, int64_t Z, int64_t device_index);
@@ -77,6 +86,16 @@ class MlpVaeEngine {
   int64_t iw_capacity() const { return iw_cap_; }
   at::Tensor iw_state;
 
+  // Latent report pass (csrc/kernels/vae_latent.hip), on a third state of its
+  // own (latent_state): train_state / eval_state / iw_state are not touched.
+  void latent_begin(int64_t nbatches);  // zero the pass state
+  // One batch of M rows at the pass cursor: the encoder (F1), the slab sum to
+  // mulv in the importance-weighted pass's order, then the rows into
+  // `rows` [nbatches*B, 2Z] at cursor*B + i. Launches only (graph-capturable).
+  void latent_batch(const at::Tensor& X, const at::Tensor& idx, int64_t M, at::Tensor rows);
+  std::vector<double> latent_read();    // kl, mi, tc, dwkl, sampled_kl, step (batches begun), cursor
+  at::Tensor latent_state;
+
   at::Tensor params, grads, exp_avg, exp_avg_sq, acts, partials, train_state, eval_state, hparams;
 
  private:
@@ -90,7 +109,7 @@ class MlpVaeEngine {
   std::vector<LayoutEntry> layout_;
   at::Tensor stamps_;
   at::Tensor iw_ws_, iw_rowbuf_;  // chunk workspace (h3 | eps | z | prior | bce) and [3][B] running row state
-  int64_t iw_cap_ = 0, iw_nbatches_ = 0;
+  int64_t iw_cap_ = 0, iw_nbatches_ = 0, latent_nbatches_ = 0;
   std::vector<std::pair<std::string, int64_t>> act_off_;
 };
 

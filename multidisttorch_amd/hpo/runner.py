@@ -72,6 +72,8 @@ class RunOptions:
     bucket_mb: Optional[object] = None     # None: model default; 0: one bucket; float: MiB cap; "auto": measured
     profile: bool = False                  # roctx ranges + device-synced phase timings in the metrics JSONL
     iw_samples: int = 0                    # K > 0: importance-weighted test log-likelihood after the last epoch
+    latent_report: bool = False            # active units + MI / TC / dimension-wise-KL split after the last epoch
+    au_threshold: float = 0.01             # a dimension is active when Var_x(mu_d) exceeds this
 
 
 @dataclass
@@ -367,6 +369,26 @@ def _iw_eval(trainer, test, opts: RunOptions, group, metrics, device, tag: str =
     return out
 
 
+def _latent_eval(trainer, test, opts: RunOptions, group, metrics, device, tag: str = "") -> dict:
+    """One latent report pass over the test set after a trial's last epoch
+    (``--latent-report``, models/latent.py): the analytic KL per dimension, the
+    active units and the split of the KL term into mutual information, total
+    correlation and dimension-wise KL -- why the trial scored as it did. Like
+    the IW pass it runs after the trial's wall time was taken."""
+    t = time.perf_counter()
+    idx = torch.arange(len(test), dtype=torch.int32, device=test.data.device)
+    with trace.range("latent_eval"):
+        r = trainer.evaluate_latent(test.data, idx, au_threshold=opts.au_threshold)
+        if device.type == "cuda":
+            torch.cuda.synchronize(device)
+    r = {k: ([round(float(x), 6) for x in v.tolist()] if torch.is_tensor(v) else v) for k, v in r.items()}
+    r["latent_s"] = round(time.perf_counter() - t, 6)
+    print0(tag + "====> Test set latent: KL {:.4f} active {}/{} MI {:.4f} TC {:.4f} DWKL {:.4f}".format(
+        r["kl"], r["active_units"], len(r["kl_per_dim"]), r["mi"], r["tc"], r["dwkl"]), process_group=group)
+    metrics.log(event="latent_eval", **r)
+    return dict(latent=r)
+
+
 def run_trial(spec: TrialSpec, group, opts: RunOptions, data=None, num_trials: Optional[int] = None) -> TrialResult:
     """Train one trial on the ranks of ``group`` (this rank is a member)."""
     world_rank = dist.get_rank() if dist.is_initialized() else 0
@@ -493,6 +515,10 @@ def run_trial(spec: TrialSpec, group, opts: RunOptions, data=None, num_trials: O
         with guarded(f"trial {spec.group_id} IW pass (world rank {world_rank})", None,
                      lambda e: failure.setdefault("error", f"{type(e).__name__}: {e}")):
             extra = _iw_eval(trainer, test, opts, group, metrics, device)
+    if opts.latent_report and not failure:
+        with guarded(f"trial {spec.group_id} latent pass (world rank {world_rank})", None,
+                     lambda e: failure.setdefault("error", f"{type(e).__name__}: {e}")):
+            extra = dict(extra, **_latent_eval(trainer, test, opts, group, metrics, device))
     return TrialResult(spec.group_id, epochs_done, n_shard, epochs_done * n_shard, t1 - t0,
                        train_loss / len(train), test_loss, failed=bool(failure), error=failure.get("error", ""),
                        extra=extra)
@@ -627,6 +653,11 @@ def run_packed_trials(specs, group, opts: RunOptions, data=None, num_trials: Opt
                          lambda e, t=t: t["failure"].setdefault("error", f"{type(e).__name__}: {e}")):
                 t["extra"] = _iw_eval(t["trainer"], test, opts, group, t["metrics"], device,
                                       tag=f"(trial {t['spec'].group_id}) ")
+        if opts.latent_report and not t["failure"]:
+            with guarded(f"trial {t['spec'].group_id} latent pass (world rank {world_rank})", None,
+                         lambda e, t=t: t["failure"].setdefault("error", f"{type(e).__name__}: {e}")):
+                t["extra"] = dict(t["extra"], **_latent_eval(t["trainer"], test, opts, group, t["metrics"], device,
+                                                             tag=f"(trial {t['spec'].group_id}) "))
     return [TrialResult(t["spec"].group_id, t["done"], t["n_shard"], t["done"] * t["n_shard"], t1 - t0,
                         t["train_loss"] / len(train), t["test_loss"], failed=bool(t["failure"]),
                         error=t["failure"].get("error", ""), extra=t["extra"]) for t in tr]

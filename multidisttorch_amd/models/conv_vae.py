@@ -39,7 +39,7 @@ from torch import nn
 from ..hpo.schedule import Schedule
 from ..ops import native
 from ..ops.philox import reparam_eps
-from .eval_graphs import GraphedEval, GraphedIwEval
+from .eval_graphs import GraphedEval, GraphedIwEval, GraphedLatentEval
 from .iw import iw_log_weights
 from .mlp_vae import reference_adam_
 
@@ -202,7 +202,7 @@ class TorchConvVAE(nn.Module):
 
 
 # --------------------------------------------------------------------------
-class ConvVaeTrainer(GraphedEval, GraphedIwEval):
+class ConvVaeTrainer(GraphedEval, GraphedIwEval, GraphedLatentEval):
     """One trial of the conv VAE. Same driver-facing API as MlpVaeTrainer."""
 
     def __init__(self, batch_size: int = 128, image: int = 28, channels: int = 1, z: int = 32, device=None,
@@ -1685,6 +1685,31 @@ class ConvVaeTrainer(GraphedEval, GraphedIwEval):
         n = S * M
         return dict(mulv=self.mulv[:M].clone(), eps=self.iw_eps.view(-1)[: n * self.Z].view(S, M, self.Z).clone(),
                     z=self.iw_z.view(-1)[: n * self.Z].view(S, M, self.Z).clone())
+
+    # latent report pass (models/eval_graphs.py::GraphedLatentEval.evaluate_latent)
+    def _lat_encode_torch(self, x):
+        return self.model.encode(x)
+
+    def _lat_prepare(self):
+        self._ensure_wt()
+        if getattr(self, "latent_state", None) is None:
+            self.latent_state = self.C.latent_state_new(self.device.index or 0)
+
+    def _lat_begin(self, nbatches):
+        self.C.latent_state_begin(self.latent_state, nbatches)
+
+    def _lat_batch(self, M, X, idx, rows):
+        """One batch at the pass cursor: the layer-path encoder as in
+        ``_iw_batch`` (it begins the step on the pass state), then the collect
+        kernel files ``mulv[:M]`` into the pass buffer and advances the cursor."""
+        self._forward_hip(M, self.latent_state, 0, train=False, src=(X, idx), enc_only=True)
+        self.C.latent_collect(self.mulv, M, self.B, self.Z, rows, self.latent_state)
+
+    def _lat_state(self):
+        return self.latent_state
+
+    def _lat_hparams(self):
+        return self.state.hparams
 
     @torch.no_grad()
     def decode(self, zz):

@@ -28,8 +28,9 @@ import torch
 
 from ..ops import native
 from .iw import check_iw_args, default_chunk, iw_eps, iw_reduce
+from .latent import check_latent_args, latent_eps, latent_report
 
-__all__ = ["GraphedEval", "GraphedIwEval"]
+__all__ = ["GraphedEval", "GraphedIwEval", "GraphedLatentEval"]
 
 
 class GraphedEval:
@@ -212,3 +213,147 @@ class GraphedIwEval:
         if return_rows:
             out["row_nll"], out["row_neg_elbo"] = row_nll.clone(), row_ne.clone()
         return out
+
+
+class GraphedLatentEval:
+    """Mixin: ``evaluate_latent``, the latent report (models/latent.py): active
+    units and the MI / TC / dimension-wise-KL split of the KL term over rows
+    ``X[idx]``. A pass of its own like ``GraphedIwEval``'s (own index buffer,
+    own graphs, own device state): per batch the encoder and a collect kernel
+    that files the batch's ``mu | lv`` rows into the pass buffer; after the last
+    batch the once-per-pass kernels (csrc/kernels/vae_latent.hip) run eagerly.
+
+    Requires ``self.B``, ``self.Z``, ``self.seed``, ``self.device``,
+    ``self.backend``, ``self.use_graphs`` and
+
+    * torch backend: ``self._lat_encode_torch(x) -> (mu, lv)``;
+    * hip backend: ``self._lat_prepare()`` (once per pass, before any launch),
+      ``self._lat_begin(nbatches)`` (zero the pass state),
+      ``self._lat_batch(M, X, idx, rows)`` (launch one batch at the pass
+      cursor; ``rows`` is the float32 [nbatches*B, 2Z] pass buffer),
+      ``self._lat_state()`` (the pass's device state tensor) and
+      ``self._lat_hparams()`` (the device HParams image: the Philox key).
+    """
+
+    # pairs per torch-backend block: [chunk, n, Z] float32 stays within 64 MiB
+    LATENT_CHUNK_ELEMS = 1 << 24
+
+    _lat_idx = None
+    _lat_rows = None
+    _lat_graphs = None
+    _lat_xkey = None
+    _lat_ws = None
+    _lat_last = None
+
+    def _lat_bind(self, idx_padded: torch.Tensor):
+        n = idx_padded.numel()
+        buf = self._lat_idx
+        if buf is None or buf.numel() != n:
+            self._lat_idx = buf = torch.empty(n, dtype=torch.int32, device=self.device)
+            self._lat_rows = torch.zeros(n, 2 * self.Z, dtype=torch.float32, device=self.device)
+            self._lat_graphs = {}
+        buf.copy_(idx_padded)
+        return buf, self._lat_rows
+
+    def _lat_graph(self, nbat: int, M: int, X: torch.Tensor, idx: torch.Tensor, rows: torch.Tensor):
+        xkey = (X.data_ptr(), X.shape[0], idx.data_ptr(), rows.data_ptr())
+        if self._lat_xkey != xkey:  # graphs of the latest eval set only, as GraphedEval
+            self._lat_graphs = {}
+            self._lat_xkey = xkey
+        key = (nbat, M)
+        g = self._lat_graphs.get(key)
+        if g is None:
+            st = self._lat_state()
+            snap = st.clone()
+            cur = torch.cuda.current_stream()
+            s = torch.cuda.Stream()
+            s.wait_stream(cur)
+            with torch.cuda.stream(s):
+                self._lat_batch(M, X, idx, rows)  # warm-up: plans / workspaces exist before capture
+            cur.wait_stream(s)
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                for _ in range(nbat):
+                    self._lat_batch(M, X, idx, rows)
+            st.copy_(snap)
+            native.upload_graph(g)
+            self._lat_graphs[key] = g
+        return g
+
+    def _lat_workspaces(self, n: int):
+        C = native.require()
+        if self._lat_ws is None or self._lat_ws[0] != n:
+            nf, nd = C.latent_ws_numel(n, self.Z)
+            self._lat_ws = (n, [torch.zeros(nf, dtype=torch.float32, device=self.device),
+                                torch.zeros(nd, dtype=torch.float64, device=self.device)])
+        return self._lat_ws[1]
+
+    @torch.no_grad()
+    def evaluate_latent(self, X: torch.Tensor, idx: torch.Tensor, au_threshold: float = 0.01,
+                        return_rows: bool = False) -> dict:
+        """The latent report over rows ``X[idx]``: ``dict(rows, kl, kl_per_dim,
+        mu_var, post_var, active_units, au_threshold, mi, tc, dwkl,
+        sampled_kl)``, per-row means in nats, the per-dimension entries float32
+        ``[Z]`` tensors; with ``return_rows`` also ``lq_joint``, ``lq_marg``,
+        ``lq_cond``, ``lp`` ``[n]``. Training, eval and iw state are not
+        touched; the result depends on (weights, data, seed, n) only."""
+        idx = idx.to(device=self.device, dtype=torch.int32).contiguous()
+        n = idx.numel()
+        check_latent_args(n, self.Z, au_threshold)
+        B, Z = self.B, self.Z
+        nb = -(-n // B)
+        X = X.contiguous()
+        if self.backend != "hip":
+            mulv = torch.cat([torch.cat(self._lat_encode_torch(X[idx[b * B: b * B + B].long()]), 1)
+                              for b in range(nb)]).float()
+            mu, lv = mulv[:, :Z], mulv[:, Z:]
+            eps = torch.from_numpy(latent_eps(n, Z, self.seed)).to(self.device)
+            out = latent_report(mu, lv, eps, au_threshold, chunk=max(1, self.LATENT_CHUNK_ELEMS // (n * Z)),
+                                return_rows=return_rows)
+            self._lat_last = dict(mulv=mulv.clone(), eps=eps, z=mu + eps * torch.exp(0.5 * lv))
+            return out
+        C = native.require()
+        pad = nb * B - n
+        if pad:
+            idx = torch.cat([idx, idx[:1].expand(pad)])  # never read (rows >= M)
+        self._lat_prepare()
+        ibuf, rows = self._lat_bind(idx)
+        self._lat_begin(nb)
+        if self.use_graphs:
+            self._lat_batch(min(B, n), X, ibuf, rows)
+            full, tail = n // B, n % B
+            if n > B:
+                if full > 1:
+                    self._lat_graph(full - 1, B, X, ibuf, rows).replay()
+                if tail:
+                    self._lat_graph(1, tail, X, ibuf, rows).replay()
+        else:
+            for b in range(nb):
+                self._lat_batch(min(B, n - b * B), X, ibuf, rows)
+        ws = self._lat_workspaces(n)
+        st = self._lat_state()
+        C.latent_report(rows, n, Z, st, self._lat_hparams(), ws)
+        r = C.latent_state_read(st)
+        view = lambda name: C.latent_ws_view(ws[0], n, Z, None, name).clone()
+        mu_var = view("mu_var")
+        out = dict(rows=n, kl=float(r[0]), kl_per_dim=view("kl_per_dim"), mu_var=mu_var, post_var=view("post_var"),
+                   active_units=int((mu_var > au_threshold).sum()), au_threshold=float(au_threshold),
+                   mi=float(r[1]), tc=float(r[2]), dwkl=float(r[3]), sampled_kl=float(r[4]))
+        if return_rows:
+            for k in ("lq_joint", "lq_marg", "lq_cond", "lp"):
+                out[k] = view(k)
+        self._lat_last = n
+        return out
+
+    def latent_buffers(self) -> dict:
+        """``mulv[n, 2Z]``, ``eps[n, Z]`` and ``z[n, Z]`` of the last
+        ``evaluate_latent`` pass (copies)."""
+        last = self._lat_last
+        if last is None:
+            raise RuntimeError("latent_buffers: no evaluate_latent pass has run")
+        if self.backend != "hip":
+            return {k: v.clone() for k, v in last.items()}
+        C, n = native.require(), last
+        ws = self._lat_ws[1]
+        return dict(mulv=self._lat_rows[:n].clone(), eps=C.latent_ws_view(ws[0], n, self.Z, None, "eps").clone(),
+                    z=C.latent_ws_view(ws[0], n, self.Z, None, "z").clone())

@@ -31,8 +31,8 @@ import torch
 from ..hpo.schedule import Schedule
 from ..ops import native
 from ..ops.philox import reparam_eps
-from .eval_graphs import GraphedEval, GraphedIwEval
-from .iw import mlp_iw_log_weights
+from .eval_graphs import GraphedEval, GraphedIwEval, GraphedLatentEval
+from .iw import mlp_encode, mlp_iw_log_weights
 from .mlp_vae import arena_layout, init_params_, reference_adam_, reference_forward, reference_step, views
 
 __all__ = ["MlpVaeTrainer"]
@@ -41,7 +41,7 @@ EVAL_STREAM = 1 << 30
 LOSS_HIST = 4096
 
 
-class MlpVaeTrainer(GraphedEval, GraphedIwEval):
+class MlpVaeTrainer(GraphedEval, GraphedIwEval, GraphedLatentEval):
     def __init__(self, batch_size: int = 128, D: int = 784, H: int = 400, Z: int = 20,
                  device=None, backend: Optional[str] = None, seed: int = 0, init_seed: Optional[int] = None,
                  lr: float = 1e-3, kl_beta: float = 1.0, betas=(0.9, 0.999), eps: float = 1e-8,
@@ -494,6 +494,26 @@ class MlpVaeTrainer(GraphedEval, GraphedIwEval):
         of S samples (copies)."""
         e = self.engine
         return dict(mulv=e.act("mulv", M).clone(), eps=e.iw_act("eps", S, M).clone(), z=e.iw_act("z", S, M).clone())
+
+    # latent report pass (models/eval_graphs.py::GraphedLatentEval.evaluate_latent)
+    def _lat_encode_torch(self, x):
+        return mlp_encode(self.named_parameters(), x)
+
+    def _lat_prepare(self):
+        pass
+
+    def _lat_begin(self, nbatches):
+        self.engine.latent_begin(nbatches)
+
+    def _lat_batch(self, M, X, idx, rows):
+        # encoder (F1) on the pass state, the slab sum to mulv, the rows into the pass buffer
+        self.engine.latent_batch(X, idx, M, rows)
+
+    def _lat_state(self):
+        return self.engine.latent_state
+
+    def _lat_hparams(self):
+        return self.engine.hparams
 
     @torch.no_grad()
     def decode(self, z: torch.Tensor) -> torch.Tensor:

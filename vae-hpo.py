@@ -16,7 +16,9 @@ multidisttorch_amd/hpo/schedule.py), ``--seed``, ``--ckpt-dir`` + ``--resume``,
 ``--trials-per-group T`` (T concurrent trials per single-rank group, one HIP
 stream each: trial packing on MI355X), ``--iw-samples K`` (after each trial's
 last epoch: the K-sample importance-weighted test log-likelihood, a score that
-does not depend on the trial's beta).
+does not depend on the trial's beta), ``--latent-report`` (+ ``--au-threshold``;
+after each trial's last epoch: active units and the MI / TC / dimension-wise-KL
+split of the KL term over the test set).
 """
 
 import argparse
@@ -88,6 +90,11 @@ def parse_args(argv=None):
     parser.add_argument("--iw-samples", type=int, default=0, metavar="K",
                         help="after each trial's last epoch: K-sample importance-weighted test log-likelihood "
                              "(a beta-independent score; 0 = off)")
+    parser.add_argument("--latent-report", action="store_true",
+                        help="after each trial's last epoch: KL per dimension, active units and the MI / TC / "
+                             "dimension-wise-KL split of the KL term over the test set")
+    parser.add_argument("--au-threshold", type=float, default=0.01,
+                        help="a latent dimension is active when the variance of its posterior mean exceeds this")
     return parser.parse_args(argv)
 
 
@@ -128,7 +135,8 @@ def main(argv=None):
                       data_dir=args.data_dir,
                       synthetic=False if args.real_data else (True if args.synthetic else None),
                       model=args.model, image_size=args.image_size, bucket_mb=parse_bucket_mb(args.bucket_mb),
-                      profile=args.profile, iw_samples=max(0, args.iw_samples))
+                      profile=args.profile, iw_samples=max(0, args.iw_samples), latent_report=args.latent_report,
+                      au_threshold=args.au_threshold)
     results = []
     member = False
     for group_id, group in enumerate(processes_groups):
@@ -143,16 +151,22 @@ def main(argv=None):
         idle_rank()
 
     # aggregate samples/s: samples once per trial, max wall over ranks
-    mine = [(r.group_id, r.samples, r.wall_s, r.failed) + ((r.extra.get("iw_nll"),) if opts.iw_samples > 0 else ())
+    lat_keys = ("kl", "active_units", "mi", "tc", "dwkl")
+    mine = [(r.group_id, r.samples, r.wall_s, r.failed) + ((r.extra.get("iw_nll"),) if opts.iw_samples > 0 else ()) +
+            ((r.extra.get("latent"),) if opts.latent_report else ())
             for r in results]
     gathered = [None] * dist.get_world_size()
     dist.all_gather_object(gathered, mine, group=control_group())
     if dist.get_rank() == 0:
-        per_trial, wall, failed, iw_nll = {}, 0.0, set(), {}
+        per_trial, wall, failed, iw_nll, latent = {}, 0.0, set(), {}, {}
         for lst in gathered:
-            for gid, samples, w, bad, *iw in lst or []:
+            for gid, samples, w, bad, *more in lst or []:
+                iw = more[:1] if opts.iw_samples > 0 else []
+                lat = more[-1] if opts.latent_report else None
                 if iw and iw[0] is not None:
                     iw_nll[gid] = iw[0]
+                if lat is not None:
+                    latent[gid] = lat
                 per_trial[gid] = min(per_trial.get(gid, samples), samples)
                 wall = max(wall, w)
                 if bad:
@@ -167,6 +181,10 @@ def main(argv=None):
             summary["iw_samples"] = opts.iw_samples
             summary["iw_nll"] = {str(g): round(v, 4) for g, v in sorted(iw_nll.items())}
             summary["best_trial_by_iw_nll"] = min(iw_nll, key=lambda g: (iw_nll[g], g)) if iw_nll else None
+        if opts.latent_report:
+            # per-image means over the test set (nats); active_units counts Var_x(mu_d) > --au-threshold
+            summary["latent"] = {str(g): {k: (v[k] if k == "active_units" else round(v[k], 4)) for k in lat_keys}
+                                 for g, v in sorted(latent.items())}
         if args.metrics_dir:
             os.makedirs(args.metrics_dir, exist_ok=True)
             with open(os.path.join(args.metrics_dir, "aggregate.json"), "w") as f:
