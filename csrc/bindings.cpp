@@ -35,22 +35,30 @@ PYBIND11_MODULE(_C, m) {
   mdt::bind_iw(m);
   mdt::bind_latent(m);
 
+  // the trial-state owner of both trainers (runtime/trial_state.h); kLossHist: the length of its loss rings
+  m.attr("kLossHist") = (int64_t)mdt::kLossHist;
+  py::class_<mdt::TrialStateBuf>(m, "TrialState")
+      .def(py::init<int64_t>())
+      .def("set_hparams", &mdt::TrialStateBuf::set_hparams, py::arg("lr"), py::arg("beta1"), py::arg("beta2"),
+           py::arg("eps"), py::arg("weight_decay"), py::arg("kl_beta"), py::arg("grad_scale"), py::arg("seed"),
+           py::arg("decoupled_wd"), py::arg("lr_warmup_steps") = 0, py::arg("lr_decay") = 0,
+           py::arg("lr_decay_steps") = 0, py::arg("lr_min_ratio") = 0.0, py::arg("kl_anneal_steps") = 0)
+      .def("set_cursor", &mdt::TrialStateBuf::set_cursor)
+      .def("set_step", &mdt::TrialStateBuf::set_step)
+      .def("reset_loss", &mdt::TrialStateBuf::reset_loss)
+      .def("read_state", &mdt::TrialStateBuf::read_state)
+      .def("loss_history", &mdt::TrialStateBuf::loss_history)
+      .def_readonly("train_state", &mdt::TrialStateBuf::train_state)
+      .def_readonly("eval_state", &mdt::TrialStateBuf::eval_state)
+      .def_readonly("hparams", &mdt::TrialStateBuf::hparams);
+
   py::class_<mdt::MlpVaeEngine>(m, "MlpVaeEngine")
       .def(py::init<int64_t, int64_t, int64_t, int64_t, int64_t>(), py::arg("batch"),
            py::arg("D"), py::arg("H"), py::arg("Z"), py::arg("device_index"))
       .def("layout", &mdt::MlpVaeEngine::layout)
       .def("numel", &mdt::MlpVaeEngine::numel)
       .def("bucket_split", &mdt::MlpVaeEngine::bucket_split)
-      .def("set_hparams", &mdt::MlpVaeEngine::set_hparams, py::arg("lr"), py::arg("beta1"),
-           py::arg("beta2"), py::arg("eps"), py::arg("weight_decay"), py::arg("kl_beta"),
-           py::arg("grad_scale"), py::arg("seed"), py::arg("decoupled_wd") = false,
-           py::arg("lr_warmup_steps") = 0, py::arg("lr_decay") = 0, py::arg("lr_decay_steps") = 0,
-           py::arg("lr_min_ratio") = 0.0, py::arg("kl_anneal_steps") = 0)
-      .def("set_cursor", &mdt::MlpVaeEngine::set_cursor)
-      .def("set_step", &mdt::MlpVaeEngine::set_step)
-      .def("reset_loss", &mdt::MlpVaeEngine::reset_loss)
-      .def("read_state", &mdt::MlpVaeEngine::read_state)
-      .def("loss_history", &mdt::MlpVaeEngine::loss_history)
+      .def_readonly("state", &mdt::MlpVaeEngine::state)
       .def("forward", &mdt::MlpVaeEngine::forward, py::arg("X"), py::arg("idx"), py::arg("M"),
            py::arg("train"), py::arg("eval"), py::arg("rng_stream"), py::arg("want_recon"))
       .def("backward", &mdt::MlpVaeEngine::backward, py::arg("X"), py::arg("idx"), py::arg("M"),
@@ -76,10 +84,7 @@ PYBIND11_MODULE(_C, m) {
       .def_readonly("grads", &mdt::MlpVaeEngine::grads)
       .def_readonly("exp_avg", &mdt::MlpVaeEngine::exp_avg)
       .def_readonly("exp_avg_sq", &mdt::MlpVaeEngine::exp_avg_sq)
-      .def_readonly("partials", &mdt::MlpVaeEngine::partials)
-      .def_readonly("train_state", &mdt::MlpVaeEngine::train_state)
-      .def_readonly("eval_state", &mdt::MlpVaeEngine::eval_state)
-      .def_readonly("hparams", &mdt::MlpVaeEngine::hparams);
+      .def_readonly("partials", &mdt::MlpVaeEngine::partials);
 
   py::class_<mdt::BucketReducer>(m, "BucketReducer")
       .def(py::init<c10::intrusive_ptr<c10d::ProcessGroup>, at::Tensor, std::vector<int64_t>, bool>(),

@@ -11,7 +11,6 @@
 #include <vector>
 
 #include "../kernels/vae_mlp.h"
-#include "sched_host.h"
 
 #include "../kernels/conv_igemm.h"
 
@@ -730,83 +729,6 @@ void combine_reparam_bwd(const at::Tensor& ws, int64_t ks, const at::Tensor& mul
      "combine_reparam_bwd");
 }
 
-// ------------------------------------------------------------------ state ----
-class TrialStateBuf {
- public:
-  TrialStateBuf(int64_t device_index) : dev_(device_index) {
-    auto bopt = torch::TensorOptions().dtype(torch::kUInt8).device(torch::kCUDA, device_index);
-    train_state = torch::zeros({(int64_t)((sizeof(TrainState) + 63) / 64 * 64)}, bopt);
-    eval_state = torch::zeros_like(train_state);
-    hparams = torch::zeros({(int64_t)((sizeof(HParams) + 63) / 64 * 64)}, bopt);
-    set_hparams(1e-3, 0.9, 0.999, 1e-8, 0.0, 1.0, 1.0, 0, false);
-  }
-  void set_hparams(double lr, double b1, double b2, double eps, double wd, double kl_beta, double gs, int64_t seed,
-                   bool decoupled, int64_t lr_warmup = 0, int64_t lr_decay = 0, int64_t lr_decay_steps = 0,
-                   double lr_min_ratio = 0.0, int64_t kl_anneal = 0) {
-    HParams h;
-    std::memset(&h, 0, sizeof(h));
-    h.lr = (float)lr; h.beta1 = (float)b1; h.beta2 = (float)b2; h.eps = (float)eps; h.weight_decay = (float)wd;
-    h.kl_beta = (float)kl_beta; h.grad_scale = (float)gs; h.decoupled_wd = decoupled ? 1 : 0;
-    h.seed_lo = (uint32_t)((uint64_t)seed & 0xffffffffu); h.seed_hi = (uint32_t)((uint64_t)seed >> 32);
-    h.lr_d = lr; h.beta1_d = b1; h.beta2_d = b2;
-    sched_fill(h, kl_beta, lr_warmup, lr_decay, lr_decay_steps, lr_min_ratio, kl_anneal);
-    hp_ = h;
-    const bool changed = b1 != b1_ || b2 != b2_;
-    b1_ = b1; b2_ = b2;
-    auto cpu = torch::empty({(int64_t)sizeof(HParams)}, torch::kUInt8);
-    std::memcpy(cpu.data_ptr(), &h, sizeof(h));
-    hparams.narrow(0, 0, sizeof(HParams)).copy_(cpu);
-    const int64_t tstep = (int64_t)read_state(false)[0], estep = (int64_t)read_state(true)[0];
-    if (changed) {
-      pows(train_state, tstep);
-      pows(eval_state, estep);
-    }
-    // the effective lr / KL weight stored in the states follow the new values
-    sched_seed(train_state, hp_, tstep, false);
-    sched_seed(eval_state, hp_, estep, true);
-  }
-  void set_cursor(bool eval, int64_t cursor, int64_t nbatches) {
-    int32_t v[2] = {(int32_t)cursor, (int32_t)nbatches};
-    auto cpu = torch::empty({8}, torch::kUInt8);
-    std::memcpy(cpu.data_ptr(), v, 8);
-    (eval ? eval_state : train_state).narrow(0, offsetof(TrainState, cursor), 8).copy_(cpu);
-  }
-  void set_step(bool eval, int64_t step) {
-    auto cpu = torch::empty({8}, torch::kUInt8);
-    std::memcpy(cpu.data_ptr(), &step, 8);
-    at::Tensor& s = eval ? eval_state : train_state;
-    s.narrow(0, offsetof(TrainState, step), 8).copy_(cpu);
-    pows(s, step);
-    sched_seed(s, hp_, step, eval);
-  }
-  void reset_loss(bool eval) { (eval ? eval_state : train_state).narrow(0, offsetof(TrainState, epoch_loss), 16).zero_(); }
-  std::vector<double> read_state(bool eval) {
-    auto cpu = (eval ? eval_state : train_state).narrow(0, 0, offsetof(TrainState, loss_hist)).to(torch::kCPU);
-    TrainState h;
-    std::memcpy(&h, cpu.data_ptr(), offsetof(TrainState, loss_hist));
-    // + the effective lr and KL weight of the last completed step (what its kernels used)
-    return {(double)h.step, (double)h.cursor, (double)h.nbatches, h.epoch_loss, h.epoch_count, h.lr_t, (double)h.kl_t};
-  }
-  at::Tensor loss_history(bool eval) {
-    return (eval ? eval_state : train_state)
-        .narrow(0, offsetof(TrainState, loss_hist), sizeof(float) * kLossHist)
-        .to(torch::kCPU)
-        .view(torch::kFloat32);
-  }
-  at::Tensor train_state, eval_state, hparams;
-
- private:
-  void pows(at::Tensor& s, int64_t step) {
-    double v[2] = {std::pow(b1_, (double)step), std::pow(b2_, (double)step)};
-    auto cpu = torch::empty({16}, torch::kUInt8);
-    std::memcpy(cpu.data_ptr(), v, 16);
-    s.narrow(0, offsetof(TrainState, b1pow), 16).copy_(cpu);
-  }
-  int64_t dev_;
-  double b1_ = -1, b2_ = -1;
-  HParams hp_{};  // host copy: set_step re-seeds the schedule's effective values from it
-};
-
 void bind_conv(pybind11::module& m) {
   namespace py = pybind11;
   m.def("igemm_plan", &igemm_plan, py::arg("mode"), py::arg("desc"), py::arg("allow_split"), py::arg("fwd") = false);
@@ -891,20 +813,6 @@ void bind_conv(pybind11::module& m) {
         py::arg("dmulv"), py::arg("dmulv16"), py::arg("dz"), py::arg("B"), py::arg("Z"), py::arg("hparams"),
         py::arg("state") = py::none());
   m.def("combine_reparam_blocks", &mdt_combine_reparam_blocks);
-  py::class_<TrialStateBuf>(m, "TrialState")
-      .def(py::init<int64_t>())
-      .def("set_hparams", &TrialStateBuf::set_hparams, py::arg("lr"), py::arg("beta1"), py::arg("beta2"),
-           py::arg("eps"), py::arg("weight_decay"), py::arg("kl_beta"), py::arg("grad_scale"), py::arg("seed"),
-           py::arg("decoupled_wd"), py::arg("lr_warmup_steps") = 0, py::arg("lr_decay") = 0,
-           py::arg("lr_decay_steps") = 0, py::arg("lr_min_ratio") = 0.0, py::arg("kl_anneal_steps") = 0)
-      .def("set_cursor", &TrialStateBuf::set_cursor)
-      .def("set_step", &TrialStateBuf::set_step)
-      .def("reset_loss", &TrialStateBuf::reset_loss)
-      .def("read_state", &TrialStateBuf::read_state)
-      .def("loss_history", &TrialStateBuf::loss_history)
-      .def_readonly("train_state", &TrialStateBuf::train_state)
-      .def_readonly("eval_state", &TrialStateBuf::eval_state)
-      .def_readonly("hparams", &TrialStateBuf::hparams);
 }
 
 }  // namespace mdt

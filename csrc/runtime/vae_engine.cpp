@@ -10,7 +10,6 @@
 #include "../kernels/vae_iw.h"
 #include "../kernels/vae_latent.h"
 #include "../kernels/vae_mlp.h"
-#include "sched_host.h"
 
 extern "C" int mdt_adam_step(float* p, const float* g, float* m, float* v, long long n,
                              const mdt::HParams* hp, mdt::TrainState* st, hipStream_t s);
@@ -28,11 +27,10 @@ static void check_rc(int rc, const char* what) {
   }
 }
 
-MlpVaeEngine::MlpVaeEngine(int64_t batch, int64_t D, int64_t H, int64_t Z, int64_t device_index)
-    : B_(batch), D_(D), H_(H), Z_(Z) {
-  // Every shape-only condition of mdt_vae_check at M = B (docs/KERNELS.md, "MLP-VAE
-  // shape domain"): an unsupported shape fails here, by name, not as a return
-  // code of the first step. The kernel-side checks stay (they also see M).
+// Every shape-only condition of mdt_vae_check at M = B (docs/KERNELS.md, "MLP-VAE
+// shape domain"): an unsupported shape fails here, by name, not as a return
+// code of the first step. The kernel-side checks stay (they also see M).
+static void check_shapes(int64_t batch, int64_t D, int64_t H, int64_t Z) {
   TORCH_CHECK(batch > 0 && batch <= kMaxBatch, "MlpVaeEngine: batch size ", batch, " must be in [1, ", kMaxBatch,
               "]");
   TORCH_CHECK(Z >= 4 && Z <= 32 && Z % 4 == 0, "MlpVaeEngine: latent size Z = ", Z,
@@ -47,6 +45,11 @@ MlpVaeEngine::MlpVaeEngine(int64_t batch, int64_t D, int64_t H, int64_t Z, int64
   const int64_t bce_slots = (row_tiles * ((D + 15) / 16) + 1) / 2 * 8, bce_cap = kPartials - kBcePartial;
   TORCH_CHECK(bce_slots <= bce_cap, "MlpVaeEngine: batch size ", batch, " with D = ", D, " needs ", bce_slots,
               " BCE partial slots (ceil(ceil(B/16)*ceil(D/16)/2)*8), limit ", bce_cap);
+}
+
+// The checks run before the first allocation (the `state` member's).
+MlpVaeEngine::MlpVaeEngine(int64_t batch, int64_t D, int64_t H, int64_t Z, int64_t device_index)
+    : state((check_shapes(batch, D, H, Z), device_index)), B_(batch), D_(D), H_(H), Z_(Z) {
   int64_t off = 0;
   auto add = [&](const std::string& n, std::vector<int64_t> shape, int64_t numel) {
     layout_.push_back({n, off, shape});
@@ -92,13 +95,7 @@ MlpVaeEngine::MlpVaeEngine(int64_t batch, int64_t D, int64_t H, int64_t Z, int64
   a = align64(a + Bpad * th * swz);
   acts = torch::zeros({a}, fopt);
   partials = torch::zeros({kPartials}, fopt);
-  auto bopt = torch::TensorOptions().dtype(torch::kUInt8).device(torch::kCUDA, device_index);
-  const int64_t st_bytes = align64((int64_t)sizeof(TrainState));
-  train_state = torch::zeros({st_bytes}, bopt);
-  eval_state = torch::zeros({st_bytes}, bopt);
-  hparams = torch::zeros({align64((int64_t)sizeof(HParams))}, bopt);
   iw_state = iw_state_new(device_index);
-  set_hparams(1e-3, 0.9, 0.999, 1e-8, 0.0, 1.0, 1.0, 0, false);
 }
 
 std::vector<std::tuple<std::string, int64_t, std::vector<int64_t>>> MlpVaeEngine::layout() const {
@@ -125,80 +122,6 @@ at::Tensor MlpVaeEngine::act(const std::string& name, int64_t M) {
     }
   }
   throw std::runtime_error("mdt: unknown activation " + name);
-}
-
-void MlpVaeEngine::set_hparams(double lr, double beta1, double beta2, double eps,
-                               double weight_decay, double kl_beta, double grad_scale,
-                               int64_t seed, bool decoupled_wd, int64_t lr_warmup, int64_t lr_decay,
-                               int64_t lr_decay_steps, double lr_min_ratio, int64_t kl_anneal) {
-  HParams h;
-  std::memset(&h, 0, sizeof(h));
-  h.lr = (float)lr; h.beta1 = (float)beta1; h.beta2 = (float)beta2; h.eps = (float)eps;
-  h.weight_decay = (float)weight_decay; h.kl_beta = (float)kl_beta;
-  h.grad_scale = (float)grad_scale;
-  h.decoupled_wd = decoupled_wd ? 1 : 0;
-  h.lr_d = lr; h.beta1_d = beta1; h.beta2_d = beta2;
-  sched_fill(h, kl_beta, lr_warmup, lr_decay, lr_decay_steps, lr_min_ratio, kl_anneal);
-  const bool betas_changed = (beta1 != beta1_) || (beta2 != beta2_);
-  beta1_ = beta1; beta2_ = beta2;
-  h.seed_lo = (uint32_t)((uint64_t)seed & 0xffffffffu);
-  h.seed_hi = (uint32_t)((uint64_t)seed >> 32);
-  auto cpu = torch::empty({(int64_t)sizeof(HParams)}, torch::kUInt8);
-  std::memcpy(cpu.data_ptr(), &h, sizeof(h));
-  hparams.narrow(0, 0, sizeof(HParams)).copy_(cpu);
-  hp_ = h;
-  const int64_t tstep = (int64_t)read_state(false)[0], estep = (int64_t)read_state(true)[0];
-  if (betas_changed) {  // keep the device beta^t products consistent with the new betas
-    write_pows(train_state, tstep);
-    write_pows(eval_state, estep);
-  }
-  // the effective lr / KL weight stored in the states follow the new values
-  sched_seed(train_state, hp_, tstep, false);
-  sched_seed(eval_state, hp_, estep, true);
-}
-
-void MlpVaeEngine::write_pows(at::Tensor& s, int64_t step) {
-  double v[2] = {std::pow(beta1_, (double)step), std::pow(beta2_, (double)step)};
-  auto cpu = torch::empty({16}, torch::kUInt8);
-  std::memcpy(cpu.data_ptr(), v, 16);
-  s.narrow(0, offsetof(TrainState, b1pow), 16).copy_(cpu);
-}
-
-void MlpVaeEngine::set_cursor(bool eval, int64_t cursor, int64_t nbatches) {
-  at::Tensor& s = eval ? eval_state : train_state;
-  int32_t v[2] = {(int32_t)cursor, (int32_t)nbatches};
-  auto cpu = torch::empty({8}, torch::kUInt8);
-  std::memcpy(cpu.data_ptr(), v, 8);
-  s.narrow(0, offsetof(TrainState, cursor), 8).copy_(cpu);
-}
-
-void MlpVaeEngine::set_step(int64_t step) {
-  auto cpu = torch::empty({8}, torch::kUInt8);
-  std::memcpy(cpu.data_ptr(), &step, 8);
-  train_state.narrow(0, offsetof(TrainState, step), 8).copy_(cpu);
-  write_pows(train_state, step);
-  sched_seed(train_state, hp_, step, false);
-}
-
-void MlpVaeEngine::reset_loss(bool eval) {
-  at::Tensor& s = eval ? eval_state : train_state;
-  s.narrow(0, offsetof(TrainState, epoch_loss), 16).zero_();
-}
-
-std::vector<double> MlpVaeEngine::read_state(bool eval) {
-  at::Tensor& s = eval ? eval_state : train_state;
-  auto cpu = s.narrow(0, 0, offsetof(TrainState, loss_hist)).to(torch::kCPU);
-  TrainState h;
-  std::memcpy(&h, cpu.data_ptr(), offsetof(TrainState, loss_hist));
-  // + the effective lr and KL weight of the last completed step (what its kernels used)
-  return {(double)h.step, (double)h.cursor, (double)h.nbatches, h.epoch_loss, h.epoch_count, h.lr_t, (double)h.kl_t};
-}
-
-at::Tensor MlpVaeEngine::loss_history(bool eval) {
-  at::Tensor& s = eval ? eval_state : train_state;
-  return s.narrow(0, offsetof(TrainState, loss_hist), sizeof(float) * kLossHist)
-      .to(torch::kCPU)
-      .view(torch::kFloat32);
 }
 
 void MlpVaeEngine::fill_args(void* out, const at::Tensor& X, const at::Tensor& idx, int64_t M,
@@ -246,8 +169,8 @@ void MlpVaeEngine::fill_args(void* out, const at::Tensor& X, const at::Tensor& i
                  ? reinterpret_cast<unsigned long long*>(stamps_.data_ptr<int64_t>())
                  : nullptr;
   a.partials = partials.data_ptr<float>();
-  a.st = reinterpret_cast<TrainState*>((eval ? eval_state : train_state).data_ptr<uint8_t>());
-  a.hp = reinterpret_cast<const HParams*>(hparams.data_ptr<uint8_t>());
+  a.st = reinterpret_cast<TrainState*>((eval ? state.eval_state : state.train_state).data_ptr<uint8_t>());
+  a.hp = reinterpret_cast<const HParams*>(state.hparams.data_ptr<uint8_t>());
 }
 
 void MlpVaeEngine::forward(const at::Tensor& X, const at::Tensor& idx, int64_t M, bool train,
@@ -278,17 +201,17 @@ void MlpVaeEngine::adam() {
   c10::hip::HIPGuardMasqueradingAsCUDA guard(params.device());
   check_rc(mdt_adam_step(params.data_ptr<float>(), grads.data_ptr<float>(),
                          exp_avg.data_ptr<float>(), exp_avg_sq.data_ptr<float>(), total_,
-                         reinterpret_cast<const HParams*>(hparams.data_ptr<uint8_t>()),
-                         reinterpret_cast<TrainState*>(train_state.data_ptr<uint8_t>()),
+                         reinterpret_cast<const HParams*>(state.hparams.data_ptr<uint8_t>()),
+                         reinterpret_cast<TrainState*>(state.train_state.data_ptr<uint8_t>()),
                          c10::hip::getCurrentHIPStream().stream()),
            "adam");
 }
 
 void MlpVaeEngine::loss_finalize(bool eval) {
   c10::hip::HIPGuardMasqueradingAsCUDA guard(params.device());
-  check_rc(mdt_loss_finalize(reinterpret_cast<const HParams*>(hparams.data_ptr<uint8_t>()),
+  check_rc(mdt_loss_finalize(reinterpret_cast<const HParams*>(state.hparams.data_ptr<uint8_t>()),
                              reinterpret_cast<TrainState*>(
-                                 (eval ? eval_state : train_state).data_ptr<uint8_t>()),
+                                 (eval ? state.eval_state : state.train_state).data_ptr<uint8_t>()),
                              partials.data_ptr<float>(), last_f2_blocks_, last_f3_blocks_,
                              c10::hip::getCurrentHIPStream().stream()),
            "loss finalize");

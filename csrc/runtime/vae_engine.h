@@ -7,8 +7,8 @@
 //     arena tail and bucket 1 the head: both are contiguous views, the
 //     all-reduce needs no pack/unpack copies.
 //   acts : one arena for every saved activation / gradient-of-activation.
-//   train_state / eval_state / hparams : device structs read by the kernels,
-//     so a captured hipGraph replays across batches and hparam changes.
+//   state : the trial's train / eval TrainState and HParams (trial_state.h),
+//     device structs read by the kernels.
 #pragma once
 #include <torch/extension.h>
 
@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../kernels/vae_mlp.h"
+#include "trial_state.h"
 
 namespace mdt {
 
@@ -49,16 +50,6 @@ class MlpVaeEngine {
   std::vector<std::tuple<std::string, int64_t, std::vector<int64_t>>> layout() const;
   int64_t numel() const { return total_; }
   int64_t bucket_split() const { return split_; }  // arena offset where fc4 starts
-
-  void set_hparams(double lr, double beta1, double beta2, double eps, double weight_decay,
-                   double kl_beta, double grad_scale, int64_t seed, bool decoupled_wd, int64_t lr_warmup = 0,
-                   int64_t lr_decay = 0, int64_t lr_decay_steps = 0, double lr_min_ratio = 0.0,
-                   int64_t kl_anneal = 0);
-  void set_cursor(bool eval, int64_t cursor, int64_t nbatches);
-  void set_step(int64_t step);
-  void reset_loss(bool eval);
-  std::vector<double> read_state(bool eval);          // step, cursor, nbatches, epoch_loss, epoch_count, lr, kl_beta
-  at::Tensor loss_history(bool eval);                  // CPU float tensor [kLossHist]
 
   void forward(const at::Tensor& X, const at::Tensor& idx, int64_t M, bool train, bool eval,
                int64_t rng_stream, bool want_recon);
@@ -96,15 +87,13 @@ class MlpVaeEngine {
   std::vector<double> latent_read();    // kl, mi, tc, dwkl, sampled_kl, step (batches begun), cursor
   at::Tensor latent_state;
 
-  at::Tensor params, grads, exp_avg, exp_avg_sq, acts, partials, train_state, eval_state, hparams;
+  at::Tensor params, grads, exp_avg, exp_avg_sq, acts, partials;
+  TrialStateBuf state;  // train / eval TrainState and the HParams image (trial_state.h)
 
  private:
   void fill_args(void* args, const at::Tensor& X, const at::Tensor& idx, int64_t M, bool train,
                  bool eval, int64_t rng_stream, bool want_recon);
-  void write_pows(at::Tensor& state, int64_t step);
   int64_t B_, D_, H_, Z_, total_, split_;
-  double beta1_ = -1.0, beta2_ = -1.0;
-  HParams hp_{};  // host copy: set_step re-seeds the schedule's effective values from it
   int last_f2_blocks_ = 0, last_f3_blocks_ = 0;
   std::vector<LayoutEntry> layout_;
   at::Tensor stamps_;

@@ -34,6 +34,7 @@ import torch.distributed as dist
 
 from ..ckpt import checkpoint as ckpt
 from ..data.sampler import reference_num_replicas, shard_indices
+from ..models.trainer_base import LOSS_HIST as LOSS_RING  # per-step loss ring of the trainers
 from ..obs.metrics import TrialMetrics
 from ..obs import trace
 from ..parallel.autotune import autotune_comm
@@ -143,9 +144,6 @@ def _load_data(opts: RunOptions, device):
     test = mnist_like(False, data_dir=opts.data_dir, device=device, size=opts.image_size,
                       synthetic=opts.synthetic, n=opts.test_samples)
     return train, test
-
-
-LOSS_RING = 4096  # per-step loss history ring of the trainers (kLossHist, csrc/kernels/vae_mlp.h)
 
 
 def _steps(trainer, n: int, B: int, events):

@@ -31,21 +31,17 @@ import sys
 from dataclasses import dataclass
 from typing import Dict, List, Optional
 
-import numpy as np
 import torch
 import torch.nn.functional as F
 from torch import nn
 
 from ..hpo.schedule import Schedule
 from ..ops import native
-from ..ops.philox import reparam_eps
-from .eval_graphs import GraphedEval, GraphedIwEval, GraphedLatentEval
 from .iw import iw_log_weights
 from .mlp_vae import reference_adam_
+from .trainer_base import EVAL_STREAM, VaeTrainerBase
 
 __all__ = ["Layer", "conv_vae_spec", "TorchConvVAE", "ConvVaeTrainer", "conv_layout"]
-
-EVAL_STREAM = 1 << 30
 
 
 @dataclass(frozen=True)
@@ -202,7 +198,7 @@ class TorchConvVAE(nn.Module):
 
 
 # --------------------------------------------------------------------------
-class ConvVaeTrainer(GraphedEval, GraphedIwEval, GraphedLatentEval):
+class ConvVaeTrainer(VaeTrainerBase):
     """One trial of the conv VAE. Same driver-facing API as MlpVaeTrainer."""
 
     def __init__(self, batch_size: int = 128, image: int = 28, channels: int = 1, z: int = 32, device=None,
@@ -210,28 +206,16 @@ class ConvVaeTrainer(GraphedEval, GraphedIwEval, GraphedLatentEval):
                  betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0, decoupled_wd: bool = False,
                  rng_stream: int = 0, use_graphs: bool = True, graph_steps: int = 10, init_seed: Optional[int] = None,
                  schedule: Optional[Schedule] = None):
-        self.B, self.image, self.channels, self.Z = batch_size, image, channels, z
-        # lr warm-up / cosine decay and KL annealing (hpo/schedule.py); None = off.
-        # On the hip backend the kernels evaluate it from the device step counter.
-        self.schedule = schedule
+        super().__init__(batch_size, device, backend, seed, rng_stream, lr, kl_beta, betas, eps, weight_decay,
+                         decoupled_wd, use_graphs, graph_steps, schedule)
+        backend = self.backend
+        self.image, self.channels, self.Z = image, channels, z
         self.D = image * image * channels
         self.H = None
-        self.device = torch.device(device) if device is not None else (
-            torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu"))
-        backend = backend or ("hip" if self.device.type == "cuda" else "torch")
-        self.backend = backend
-        self.seed, self.rng_stream = int(seed), int(rng_stream)
-        self.hp = dict(lr=lr, beta1=betas[0], beta2=betas[1], eps=eps, weight_decay=weight_decay,
-                       kl_beta=kl_beta, grad_scale=1.0)
-        self.decoupled_wd = decoupled_wd
         self.spec = conv_vae_spec(image, channels, z)
         self.layout, self.numel = conv_layout(self.spec)
         # first decoder parameter: the default bucket boundary (decoder grads are ready first)
         self.split = next(o for n, o, _ in self.layout if n.startswith("dec"))
-        self.use_graphs = use_graphs and backend == "hip"
-        self.graph_steps = max(1, graph_steps)
-        self._graphs = {}
-        self.reducer = None
         # horizontal fusion of independent backward launches (conv_jobs.hip);
         # MDT_CONV_JOBS=0 issues every op as its own kernel (A/B, bitwise equal)
         self.fuse_jobs = os.getenv("MDT_CONV_JOBS", "1") != "0"
@@ -271,14 +255,6 @@ class ConvVaeTrainer(GraphedEval, GraphedIwEval, GraphedLatentEval):
         self.f28_pair = os.getenv("MDT_F28_PAIR", "1") != "0"
         # eval passes through the same paired form, forward only (MDT_F28_EVAL_PAIR=0: solo f28_fwd_k)
         self._eval_pair = os.getenv("MDT_F28_EVAL_PAIR", "1") != "0"
-        # DDP on the fused 28x28 step: the decoder bucket goes out before the
-        # encoder weight gradients (True), or every bucket after the whole
-        # backward on one stream (False); "auto" (default): overlap only when
-        # the decoder bucket's transfer over one xGMI link outweighs the
-        # measured cost of splitting the weight-gradient launch
-        # (parallel/ddp.py::overlap_pays, profiles/r4_ddp_fused)
-        ov = os.getenv("MDT_DDP_OVERLAP", "auto")
-        self.ddp_overlap = None if ov == "auto" else ov != "0"
         # tests: > 0 delays every partner workgroup (forces the solo fallback); < 0 stalls sample 0's
         # role-1 half after pairing (forces an exchange timeout: f28_err, health_error());
         # MDT_F28_TEST_STALL_US=N sets -N (fault drills through the HPO runner / bench)
@@ -298,7 +274,6 @@ class ConvVaeTrainer(GraphedEval, GraphedIwEval, GraphedLatentEval):
         # the GPU (tests/gpu/conv_ddp_worker.py)
         self.comm_split_tail = False
         self.comm_phase_hook = None
-        self._data = None
         torch.manual_seed(self.seed if init_seed is None else init_seed)
         ref = TorchConvVAE(self.spec, image, channels, z)
         f32 = dict(dtype=torch.float32, device=self.device)
@@ -310,10 +285,6 @@ class ConvVaeTrainer(GraphedEval, GraphedIwEval, GraphedLatentEval):
             self.named_parameters()[name].copy_(t)
         if backend == "torch":
             self.model = ref.to(self.device)
-            self._st = dict(step=0, cursor=0, nbatches=0, epoch_loss=0.0, epoch_count=0.0)
-            self._st_eval = dict(step=0, cursor=0, nbatches=0, epoch_loss=0.0, epoch_count=0.0)
-            self._hist = np.zeros(4096, np.float32)
-            self._hist_eval = np.zeros(4096, np.float32)
         else:
             self.C = native.require()
             self.state = self.C.TrialState(self.device.index or 0)
@@ -326,64 +297,7 @@ class ConvVaeTrainer(GraphedEval, GraphedIwEval, GraphedLatentEval):
         return {"kind": "conv", "image": int(self.image), "channels": int(self.channels), "Z": int(self.Z),
                 "layers": [[l.name, l.kind, l.cin, l.cout, l.k, l.s, l.p] for l in self.spec]}
 
-    def named_parameters(self):
-        return {n: self.params.narrow(0, o, math.prod(s)).view(s) for n, o, s in self.layout}
-
-    def named_grads(self):
-        return {n: self.grads.narrow(0, o, math.prod(s)).view(s) for n, o, s in self.layout}
-
-    def state_dict(self):
-        return {k: v.detach().cpu().clone() for k, v in self.named_parameters().items()}
-
-    @torch.no_grad()
-    def load_state_dict(self, sd):
-        for k, t in self.named_parameters().items():
-            t.copy_(sd[k].to(t.device, torch.float32))
-        if self.backend == "hip":
-            self._cast_weights()
-        else:
-            self.model.from_arena(self.named_parameters())
-
-    def optimizer_state(self):
-        return {"step": self.step_count, "exp_avg": self.exp_avg.cpu().clone(), "exp_avg_sq": self.exp_avg_sq.cpu().clone()}
-
-    @torch.no_grad()
-    def load_optimizer_state(self, st):
-        self.exp_avg.copy_(st["exp_avg"])
-        self.exp_avg_sq.copy_(st["exp_avg_sq"])
-        self.set_step(int(st["step"]))
-
-    def set_hparams(self, **kw):
-        for k, v in kw.items():
-            self.hp[k] = float(v)
-        self._push_hparams()
-
-    def set_schedule(self, schedule: Optional[Schedule]):
-        """Replace the schedule (None = off). It continues from the current
-        step; captured step graphs stay valid (the parameters are device-resident)."""
-        self.schedule = schedule
-        self._push_hparams()
-
-    def _push_hparams(self):
-        if self.backend == "hip":
-            h = self.hp
-            self.state.set_hparams(h["lr"], h["beta1"], h["beta2"], h["eps"], h["weight_decay"], h["kl_beta"],
-                                   h["grad_scale"], self.seed, self.decoupled_wd,
-                                   **(self.schedule or Schedule()).native_args())
-
-    def _effective(self, t: int):
-        """(lr_t, beta_t) of optimizer step t on the torch backend, as doubles:
-        lr * f_lr(t) and kl_beta * f_kl(t), the products the device forms."""
-        s, h = self.schedule, self.hp
-        if s is None:
-            return h["lr"], h["kl_beta"]
-        return h["lr"] * s.lr_factor(t), h["kl_beta"] * s.kl_factor(t)
-
     # ----------------------------------------------------------- state
-    @property
-    def step_count(self):
-        return int(self.read_state()["step"])
-
     @property
     def comm_jobs(self) -> bool:
         """The step can host the fused all-reduce jobs (comm_jobs.h): the
@@ -405,53 +319,16 @@ class ConvVaeTrainer(GraphedEval, GraphedIwEval, GraphedLatentEval):
             if red is not None and hasattr(red, "rebase_epochs"):
                 # the fused jobs' epoch is step + base: keep it increasing
                 red.rebase_epochs(self.step_count, int(step))
-            self.state.set_step(False, int(step))
-        else:
-            self._st["step"] = int(step)
+        super().set_step(step)
 
     def set_cursor(self, cursor, nbatches, eval=False):
         if not eval:
             self._invalidate_prefetch()
-        if self.backend == "hip":
-            self.state.set_cursor(eval, int(cursor), int(nbatches))
-        else:
-            st = self._st_eval if eval else self._st
-            st["cursor"], st["nbatches"] = int(cursor), int(nbatches)
-
-    def reset_loss(self, eval=False):
-        if self.backend == "hip":
-            self.state.reset_loss(eval)
-        else:
-            st = self._st_eval if eval else self._st
-            st["epoch_loss"], st["epoch_count"] = 0.0, 0.0
-
-    def read_state(self, eval=False):
-        if self.backend == "hip":
-            s = self.state.read_state(eval)
-            return dict(step=int(s[0]), cursor=int(s[1]), nbatches=int(s[2]), epoch_loss=s[3], epoch_count=s[4],
-                        lr=s[5], kl_beta=s[6])
-        # lr / kl_beta: the effective values of the last completed step (eval: always the full ones)
-        st = dict(self._st_eval if eval else self._st)
-        lr, kl = (self.hp["lr"], self.hp["kl_beta"]) if eval else self._effective(st["step"])
-        st["lr"], st["kl_beta"] = float(lr), float(np.float32(kl))
-        return st
-
-    def loss_history(self, eval=False):
-        if self.backend == "hip":
-            return self.state.loss_history(eval).numpy()
-        return (self._hist_eval if eval else self._hist).copy()
+        super().set_cursor(cursor, nbatches, eval)
 
     def bind_train_data(self, X, idx):
-        assert X.dim() == 2 and X.shape[1] == self.D and X.dtype == torch.float32
-        n = idx.numel()
-        nb = -(-n // self.B)
-        idx = idx.to(device=self.device, dtype=torch.int32)
-        pad = nb * self.B - n
-        if pad:
-            idx = torch.cat([idx, idx[:1].expand(pad)])
-        self._data = (X.contiguous(), idx.contiguous(), n, nb)
+        super().bind_train_data(X, idx)
         self._invalidate_prefetch()
-        self._graphs.clear()
         self._plans28.clear()
 
     def attach_reducer(self, reducer):
@@ -460,14 +337,7 @@ class ConvVaeTrainer(GraphedEval, GraphedIwEval, GraphedLatentEval):
         A fused xGMI reducer (``XgmiP2PReducer(fused=True)``, kind "xgmi")
         instead contributes all-reduce JOBS to the step's own launches
         (csrc/kernels/comm_jobs.h): no second stream, no events."""
-        self.reducer = reducer
-        self._graphs.clear()
-        from ..parallel.ddp import graph_capturable
-
-        # a host-blocking (c10d/gloo) reducer cannot live inside a step graph: eager steps
-        if not hasattr(self, "_graphs_wanted"):
-            self._graphs_wanted = self.use_graphs
-        self.use_graphs = self._graphs_wanted and graph_capturable(reducer)
+        super().attach_reducer(reducer)
         self._plans28.clear()
         self._comm_packs = {}
         self._comm_tables = {}
@@ -544,9 +414,6 @@ class ConvVaeTrainer(GraphedEval, GraphedIwEval, GraphedLatentEval):
                 acc = 0.0
         bounds.append(0)
         return sorted(set(bounds))
-
-    def default_bucket_bounds(self):
-        return self.bucket_bounds(None)
 
     @torch.no_grad()
     def refresh_weights(self):
@@ -1422,9 +1289,7 @@ class ConvVaeTrainer(GraphedEval, GraphedIwEval, GraphedLatentEval):
     def _step_torch(self, M):
         X, idx = self._data[0], self._data[1]
         st = self._st
-        rows = idx[st["cursor"] * self.B: st["cursor"] * self.B + M].long()
-        x = X[rows]
-        eps = torch.from_numpy(reparam_eps(M, self.Z, self.seed, self.rng_stream, st["step"])).to(self.device)
+        x, eps = self._torch_batch(X, idx, st["cursor"], M, self.rng_stream, st["step"])
         self.model.zero_grad(set_to_none=True)
         lr_t, kl_t = self._effective(st["step"] + 1)
         loss, *_ = self.model.loss(x, eps, kl_t)
@@ -1440,35 +1305,12 @@ class ConvVaeTrainer(GraphedEval, GraphedIwEval, GraphedLatentEval):
             reference_adam_(self.params, self.grads, self.exp_avg, self.exp_avg_sq, st["step"] + 1, lr_t,
                             h["beta1"], h["beta2"], h["eps"], h["weight_decay"], h["grad_scale"], self.decoupled_wd)
             self.model.from_arena(self.named_parameters())
-        lv = float(loss.detach())
-        self._hist[st["step"] % 4096] = lv
-        st["epoch_loss"] += lv
-        st["epoch_count"] += 1
-        st["step"] += 1
-        st["cursor"] += 1
-        if st["nbatches"] and st["cursor"] >= st["nbatches"]:
-            st["cursor"] = 0
+        self._record(float(loss.detach()))
 
     # ----------------------------------------------------------- driver API
     def train_steps(self, n, M=None):
-        M = self.B if M is None else M
-        if n <= 0:
-            return
-        if self.backend == "torch":
-            for _ in range(n):
-                self._step_torch(M)
-            return
-        if not self.use_graphs:
-            for _ in range(n):
-                self._step_hip(M)
-        else:
-            S = self.graph_steps
-            while n >= S:
-                self._replay(S, M)
-                n -= S
-            for _ in range(n):
-                self._replay(1, M)
-        if self._wt_deferred() or self.f28:
+        super().train_steps(n, M)
+        if n > 0 and self.backend == "hip" and (self._wt_deferred() or self.f28):
             # the last step's transposed weight copies (deferred to the next
             # step's first launch, or never needed by the fused 28x28 step) are
             # stale now: eval / decode write them first (_ensure_wt)
@@ -1485,55 +1327,10 @@ class ConvVaeTrainer(GraphedEval, GraphedIwEval, GraphedLatentEval):
             self._wtrans_layers(1, len(self.spec))
             self._wt_stale = False
 
-    def prepare(self, batch_sizes, eval_rows=None):
-        """Set-up work done once before timing starts: capture the step graphs
-        for the batch sizes an epoch uses and run the eval / decode kernels
-        once (code-object load). Training state is left unchanged."""
-        if self.backend != "hip":
-            return
-        if self.use_graphs and self._data is not None:
-            for M in sorted({int(m) for m in batch_sizes if m and m > 0}):
-                for S in {self.graph_steps, 1}:
-                    if (S, M) not in self._graphs:
-                        self._graphs[(S, M)] = self._capture(S, M)
-        if eval_rows is not None and eval_rows.numel():
-            st = self.read_state(eval=True)
-            n = eval_rows.shape[0]
-            self.evaluate(eval_rows, torch.arange(n, device=eval_rows.device, dtype=torch.int32))
-            self.decode(torch.zeros(1, self.Z, device=self.device))
-            self.set_cursor(st["cursor"], st["nbatches"], eval=True)
-            self.reset_loss(eval=True)
-        torch.cuda.synchronize(self.device)
-
-    # strict_graphs: a replay that finds no captured graph raises instead of
-    # capturing lazily (bench.py / autotune set it after ``prepare`` so no
-    # capture ever lands inside a timed region)
-    strict_graphs = False
-
-    def _replay(self, S, M):
-        g = self._graphs.get((S, M))
-        if g is None:
-            if self.strict_graphs:
-                raise RuntimeError(f"no captured step graph for (steps={S}, M={M}); call prepare() first")
-            g = self._capture(S, M)
-            self._graphs[(S, M)] = g
-        g.replay()
-
     def _capture(self, S, M):
         red = self.reducer
         k0 = self.step_count if red is not None and hasattr(red, "rebase_epochs") else None
-        snap = [t.clone() for t in (self.params, self.exp_avg, self.exp_avg_sq, self.state.train_state)]
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            self._step_hip(M)
-        torch.cuda.current_stream().wait_stream(s)
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            for _ in range(S):
-                self._step_hip(M)
-        for t, v in zip((self.params, self.exp_avg, self.exp_avg_sq, self.state.train_state), snap):
-            t.copy_(v)
+        g = super()._capture(S, M)
         if k0 is not None:
             # the warm-up step ran the fused all-reduce jobs at epoch k0 + 1 and
             # published flags for it; the step counter now goes back to k0, so
@@ -1541,7 +1338,6 @@ class ConvVaeTrainer(GraphedEval, GraphedIwEval, GraphedLatentEval):
             # captures at the same points: the rebase is the same everywhere)
             red.rebase_epochs(k0 + 1, k0)
         self._cast_weights()
-        native.upload_graph(g)
         return g
 
     @torch.no_grad()
@@ -1581,48 +1377,18 @@ class ConvVaeTrainer(GraphedEval, GraphedIwEval, GraphedLatentEval):
                                       self.z16, None, None, None, self.recon if want_recon else None, bce, kld, db4,
                                       None]
 
-    def _eval_state(self):
-        return self.state.eval_state
-
     def _eval_recon(self, M):
         return self.recon[: M * self.D].view(M, self.D).clone()
 
+    def _eval_batch_torch(self, X, idx, b, M, want_recon):
+        x, eps = self._torch_batch(X, idx, b, M, EVAL_STREAM + self.rng_stream, self._st_eval["step"])
+        loss, t, _, _ = self.model.loss(x, eps, self.hp["kl_beta"])
+        recon = torch.sigmoid(t).permute(0, 2, 3, 1).reshape(M, self.D).clone() if want_recon else None
+        return float(loss.detach()), recon
+
     def evaluate(self, X, idx, want_first_recon=True):
         self._ensure_wt()
-        idx = idx.to(device=self.device, dtype=torch.int32).contiguous()
-        n = idx.numel()
-        nb = -(-n // self.B)
-        pad = nb * self.B - n
-        if pad:
-            idx = torch.cat([idx, idx[:1].expand(pad)])
-        if self.backend == "hip" and self.use_graphs:
-            first = self._eval_graphed(X.contiguous(), idx, n, want_first_recon)
-            return self.read_state(eval=True)["epoch_loss"], first
-        self.set_cursor(0, nb, eval=True)
-        self.reset_loss(eval=True)
-        first = None
-        for b in range(nb):
-            M = min(self.B, n - b * self.B)
-            if self.backend == "hip":
-                want = want_first_recon and b == 0
-                self._eval_batch(M, X.contiguous(), idx, want)
-                if want:
-                    first = self._eval_recon(M)
-            else:
-                st = self._st_eval
-                rows = idx[b * self.B: b * self.B + M].long()
-                x = X[rows]
-                eps = torch.from_numpy(reparam_eps(M, self.Z, self.seed, EVAL_STREAM + self.rng_stream,
-                                                   st["step"])).to(self.device)
-                loss, t, _, _ = self.model.loss(x, eps, self.hp["kl_beta"])
-                if want_first_recon and b == 0:
-                    first = torch.sigmoid(t).permute(0, 2, 3, 1).reshape(M, self.D).clone()
-                lv = float(loss.detach())
-                self._hist_eval[st["step"] % 4096] = lv
-                st["epoch_loss"] += lv
-                st["epoch_count"] += 1
-                st["step"] += 1
-        return self.read_state(eval=True)["epoch_loss"], first
+        return super().evaluate(X, idx, want_first_recon)
 
     # importance-weighted log-likelihood pass (models/eval_graphs.py::GraphedIwEval.evaluate_iw)
     def _iw_logw_torch(self, x, eps):
@@ -1652,18 +1418,12 @@ class ConvVaeTrainer(GraphedEval, GraphedIwEval, GraphedLatentEval):
         reduce kernel (which advances the pass cursor after the last chunk)."""
         C, st, hp = self.C, self.iw_state, self.state.hparams
         self._forward_hip(M, st, 0, train=False, src=(X, idx), enc_only=True)
-        dec = [l for l in self.spec if l.name.startswith("dec")]
         Sc = max(1, min(S, self.B // M))
         for k0 in range(0, k, Sc):
             s = min(Sc, k - k0)
             V = s * M
             C.iw_reparam(self.mulv, M, self.B, self.Z, k0, s, st, hp, self.z16, self.iw_z, self.iw_eps, self.iw_prior)
-            h = self.z16
-            ws = self._plan(V)["ws"]
-            for l in dec:
-                last = l is dec[-1]
-                self._layer_fwd(l, h, V, None if last else self.acts[l.name], self.logits if last else None, ws)
-                h = self.acts[l.name]
+            self._decode_z16(V)
             C.iw_row_bce(self.logits, self.xb, V, M, self.D, self.iw_bce)
             C.iw_reduce(self.iw_prior, self.iw_bce, self.iw_rowbuf, rows[0], rows[1], st, M, self.B, k, s,
                         k0 == 0, k0 + s >= k)
@@ -1708,8 +1468,14 @@ class ConvVaeTrainer(GraphedEval, GraphedIwEval, GraphedLatentEval):
     def _lat_state(self):
         return self.latent_state
 
-    def _lat_hparams(self):
-        return self.state.hparams
+    def _decode_z16(self, V):
+        """The decoder layers over rows ``z16[:V]`` into ``logits``."""
+        dec = [l for l in self.spec if l.name.startswith("dec")]
+        h, ws = self.z16, self._plan(V)["ws"]
+        for l in dec:
+            last = l is dec[-1]
+            self._layer_fwd(l, h, V, None if last else self.acts[l.name], self.logits if last else None, ws)
+            h = self.acts[l.name]
 
     @torch.no_grad()
     def decode(self, zz):
@@ -1719,17 +1485,11 @@ class ConvVaeTrainer(GraphedEval, GraphedIwEval, GraphedLatentEval):
             return torch.sigmoid(t).permute(0, 2, 3, 1).reshape(zz.shape[0], self.D)
         self._ensure_wt()
         outs = []
-        dec = [l for l in self.spec if l.name.startswith("dec")]
         for i in range(0, zz.shape[0], self.B):
             zc = zz[i:i + self.B]
             M = zc.shape[0]
             self.z16[:M].copy_(zc.to(torch.bfloat16))
-            h = self.z16
-            for l in dec:
-                last = l is dec[-1]
-                self._layer_fwd(l, h, M, None if last else self.acts[l.name], self.logits if last else None,
-                                self._plan(M)["ws"])
-                h = self.acts[l.name]
+            self._decode_z16(M)
             outs.append(torch.sigmoid(self.logits[: M * self.D].view(M, self.D)).clone())
         return torch.cat(outs)
 

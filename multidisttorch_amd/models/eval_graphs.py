@@ -30,7 +30,30 @@ from ..ops import native
 from .iw import check_iw_args, default_chunk, iw_eps, iw_reduce
 from .latent import check_latent_args, latent_eps, latent_report
 
-__all__ = ["GraphedEval", "GraphedIwEval", "GraphedLatentEval"]
+__all__ = ["GraphedEval", "GraphedIwEval", "GraphedLatentEval", "capture_replayable"]
+
+
+def capture_replayable(snapshot_tensors, launch, repeats: int):
+    """A graph of ``repeats`` calls of ``launch()`` that leaves the device
+    state as it found it: the warm-up call (plans, workspaces, communicators
+    and code objects exist before capture) and the capture itself advance the
+    step counter / cursor / Adam moments, so ``snapshot_tensors`` are cloned
+    first and restored afterwards. The graph is uploaded before it is returned."""
+    snap = [t.clone() for t in snapshot_tensors]
+    cur = torch.cuda.current_stream()
+    s = torch.cuda.Stream()
+    s.wait_stream(cur)
+    with torch.cuda.stream(s):
+        launch()
+    cur.wait_stream(s)
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        for _ in range(repeats):
+            launch()
+    for t, v in zip(snapshot_tensors, snap):
+        t.copy_(v)
+    native.upload_graph(g)
+    return g
 
 
 class GraphedEval:
@@ -62,20 +85,7 @@ class GraphedEval:
             self._eval_xkey = xkey
         g = self._eval_graphs.get(key)
         if g is None:
-            st = self._eval_state()
-            snap = st.clone()
-            cur = torch.cuda.current_stream()
-            s = torch.cuda.Stream()
-            s.wait_stream(cur)
-            with torch.cuda.stream(s):
-                self._eval_batch(M, X, idx, False)  # warm-up: plans / workspaces exist before capture
-            cur.wait_stream(s)
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                for _ in range(S):
-                    self._eval_batch(M, X, idx, False)
-            st.copy_(snap)
-            native.upload_graph(g)
+            g = capture_replayable([self._eval_state()], lambda: self._eval_batch(M, X, idx, False), S)
             self._eval_graphs[key] = g
         return g
 
@@ -140,20 +150,7 @@ class GraphedIwEval:
         key = (nbat, M, k, S)
         g = self._iw_graphs.get(key)
         if g is None:
-            st = self._iw_state()
-            snap = st.clone()
-            cur = torch.cuda.current_stream()
-            s = torch.cuda.Stream()
-            s.wait_stream(cur)
-            with torch.cuda.stream(s):
-                self._iw_batch(M, X, idx, k, S, rows)  # warm-up: workspaces exist before capture
-            cur.wait_stream(s)
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                for _ in range(nbat):
-                    self._iw_batch(M, X, idx, k, S, rows)
-            st.copy_(snap)
-            native.upload_graph(g)
+            g = capture_replayable([self._iw_state()], lambda: self._iw_batch(M, X, idx, k, S, rows), nbat)
             self._iw_graphs[key] = g
         return g
 
@@ -263,20 +260,7 @@ class GraphedLatentEval:
         key = (nbat, M)
         g = self._lat_graphs.get(key)
         if g is None:
-            st = self._lat_state()
-            snap = st.clone()
-            cur = torch.cuda.current_stream()
-            s = torch.cuda.Stream()
-            s.wait_stream(cur)
-            with torch.cuda.stream(s):
-                self._lat_batch(M, X, idx, rows)  # warm-up: plans / workspaces exist before capture
-            cur.wait_stream(s)
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                for _ in range(nbat):
-                    self._lat_batch(M, X, idx, rows)
-            st.copy_(snap)
-            native.upload_graph(g)
+            g = capture_replayable([self._lat_state()], lambda: self._lat_batch(M, X, idx, rows), nbat)
             self._lat_graphs[key] = g
         return g
 

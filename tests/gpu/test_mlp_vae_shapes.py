@@ -247,13 +247,13 @@ def test_fused_adam_matches_unfused_gradients_and_float64_adam(sid, native_ext):
     tr.exp_avg_sq.copy_(v0.to(_dev()) * used)
     tr.set_step(2)
     e = tr.engine
-    p0, m0, v0, st0 = tr.params.clone(), tr.exp_avg.clone(), tr.exp_avg_sq.clone(), e.train_state.clone()
+    p0, m0, v0, st0 = tr.params.clone(), tr.exp_avg.clone(), tr.exp_avg_sq.clone(), e.state.train_state.clone()
     e.forward(X, idx, M, True, False, 0, False)
     e.backward(X, idx, M, 0, False)
     torch.cuda.synchronize()
     g_unfused = tr.grads.clone()
     assert torch.equal(tr.params, p0) and torch.equal(tr.exp_avg, m0)
-    e.train_state.copy_(st0)
+    e.state.train_state.copy_(st0)
     tr.grads.zero_()
     e.forward(X, idx, M, True, False, 0, False)
     e.backward(X, idx, M, 0, True)
