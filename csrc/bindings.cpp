@@ -18,6 +18,7 @@ void bind_p2p(pybind11::module& m);
 void bind_cpu(pybind11::module& m);
 void bind_iw(pybind11::module& m);
 void bind_latent(pybind11::module& m);
+void bind_data(pybind11::module& m);
 }  // namespace mdt
 
 PYBIND11_MODULE(_C, m) {
@@ -34,6 +35,7 @@ PYBIND11_MODULE(_C, m) {
   mdt::bind_cpu(m);
   mdt::bind_iw(m);
   mdt::bind_latent(m);
+  mdt::bind_data(m);
 
   // the trial-state owner of both trainers (runtime/trial_state.h); kLossHist: the length of its loss rings
   m.attr("kLossHist") = (int64_t)mdt::kLossHist;

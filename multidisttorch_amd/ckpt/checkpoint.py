@@ -20,6 +20,9 @@ with ``torch.load(weights_only=True)`` (never unpickles code):
   layout       [[name, offset, shape...]] of the arena, for validation
   arch         model kind + dims (mlp: D/H/Z; conv: image/channels/Z + the
                layer table), validated on load before any tensor is copied
+  data         {"binarize": none | threshold | static | dynamic}: the likelihood
+               the trial trains under (data/binarize.py). ``load_latest`` returns
+               it (absent = none); the runner refuses a resume under another one
 Only group rank 0 writes (replicas are identical after the all-reduce);
 writes go to a temp file + atomic rename so a crash never leaves a torn file.
 """
@@ -38,7 +41,8 @@ def trial_dir(ckpt_dir: str, group_id: int) -> str:
     return os.path.join(ckpt_dir, f"trial-{group_id}")
 
 
-def save_trial(ckpt_dir: str, trainer, spec, epoch: int, extra: Optional[dict] = None) -> str:
+def save_trial(ckpt_dir: str, trainer, spec, epoch: int, extra: Optional[dict] = None,
+               binarize: str = "none") -> str:
     d = trial_dir(ckpt_dir, spec.group_id)
     os.makedirs(d, exist_ok=True)
     opt = trainer.optimizer_state()
@@ -54,6 +58,7 @@ def save_trial(ckpt_dir: str, trainer, spec, epoch: int, extra: Optional[dict] =
         "rng": {"seed": int(trainer.seed), "rng_stream": int(trainer.rng_stream)},
         "layout": [[n, int(o)] + [int(x) for x in s] for n, o, s in trainer.layout],
         "arch": trainer.model_meta(),
+        "data": {"binarize": str(binarize)},
     }
     if extra:
         payload["extra"] = extra
@@ -100,4 +105,4 @@ def load_latest(ckpt_dir: str, group_id: int, trainer) -> Optional[dict]:
 
         trainer.set_schedule(Schedule(**ck["schedule"]))
     trainer.load_optimizer_state(ck["optimizer"])  # sets the step: the schedule continues from it
-    return dict(ck["progress"], path=path, trial=ck["trial"])
+    return dict(ck["progress"], path=path, trial=ck["trial"], binarize=(ck.get("data") or {}).get("binarize", "none"))

@@ -33,6 +33,8 @@ import torch
 import torch.distributed as dist
 
 from ..ckpt import checkpoint as ckpt
+from ..data.binarize import Binarizer, check_mode
+from ..data.datasets import ImageSet
 from ..data.sampler import reference_num_replicas, shard_indices
 from ..models.trainer_base import LOSS_HIST as LOSS_RING  # per-step loss ring of the trainers
 from ..obs.metrics import TrialMetrics
@@ -75,6 +77,7 @@ class RunOptions:
     iw_samples: int = 0                    # K > 0: importance-weighted test log-likelihood after the last epoch
     latent_report: bool = False            # active units + MI / TC / dimension-wise-KL split after the last epoch
     au_threshold: float = 0.01             # a dimension is active when Var_x(mu_d) exceeds this
+    binarize: str = "none"                 # none | threshold | static | dynamic (data/binarize.py); one value per run
 
 
 @dataclass
@@ -144,6 +147,41 @@ def _load_data(opts: RunOptions, device):
     test = mnist_like(False, data_dir=opts.data_dir, device=device, size=opts.image_size,
                       synthetic=opts.synthetic, n=opts.test_samples)
     return train, test
+
+
+def _binarizers(spec: TrialSpec, opts: RunOptions, train, test, idx):
+    """``--binarize``: (train Binarizer over the trial's shard, the test set as
+    an ImageSet of its fixed binarized rows), or (None, test) when off. The
+    test rows are drawn here, once; the train rows at the top of every epoch
+    (``_refresh_train``). Every trial holds its own buffers."""
+    if opts.binarize == "none":
+        return None, test
+    bt = Binarizer(opts.binarize, spec.seed, test.data, torch.arange(len(test), dtype=torch.int32), 1)
+    bt.refresh(0)
+    return (Binarizer(opts.binarize, spec.seed, train.data, idx, 0),
+            ImageSet(bt.data, test.shape, test.synthetic, test.name))
+
+
+def _check_resumed_binarize(prog, opts: RunOptions, group_id: int):
+    if prog is not None and prog.get("binarize", "none") != opts.binarize:
+        raise ValueError(f"trial {group_id}: checkpoint {prog['path']} was trained with --binarize "
+                         f"{prog.get('binarize', 'none')}, this run asks for --binarize {opts.binarize}")
+
+
+def _refresh_train(binarizer, trainer, epoch: int, opts: RunOptions, device):
+    """Top of an epoch, on the stream the epoch is enqueued on: redraw the
+    trial's training rows in place (dynamic: every epoch; static / threshold:
+    the first one) and tell the trainer. Seconds taken (device-synced under
+    ``--profile``), or None without ``--binarize``."""
+    if binarizer is None:
+        return None
+    t = time.perf_counter()
+    with trace.range(f"binarize_{epoch}"):
+        if binarizer.refresh(epoch):
+            trainer.train_data_changed()
+        if opts.profile and device.type == "cuda":
+            torch.cuda.current_stream(device).synchronize()
+    return round(time.perf_counter() - t, 6)
 
 
 def _steps(trainer, n: int, B: int, events):
@@ -389,6 +427,7 @@ def _latent_eval(trainer, test, opts: RunOptions, group, metrics, device, tag: s
 
 def run_trial(spec: TrialSpec, group, opts: RunOptions, data=None, num_trials: Optional[int] = None) -> TrialResult:
     """Train one trial on the ranks of ``group`` (this rank is a member)."""
+    check_mode(opts.binarize)
     world_rank = dist.get_rank() if dist.is_initialized() else 0
     world_size = dist.get_world_size() if dist.is_initialized() else 1
     grank = dist.get_rank(group) if dist.is_initialized() else 0
@@ -432,6 +471,7 @@ def run_trial(spec: TrialSpec, group, opts: RunOptions, data=None, num_trials: O
         if grank == 0:
             try:
                 prog = ckpt.load_latest(opts.ckpt_dir, spec.group_id, trainer)
+                _check_resumed_binarize(prog, opts, spec.group_id)
             except Exception as e:  # noqa: BLE001 - re-raised below on every member
                 err = e
         if prog is not None:
@@ -460,8 +500,14 @@ def run_trial(spec: TrialSpec, group, opts: RunOptions, data=None, num_trials: O
     metrics = TrialMetrics(opts.metrics_dir, spec.group_id, enabled=(grank == 0))
 
     idx = shard_indices(len(train), n_rep, spec.group_id)
-    trainer.bind_train_data(train.data, idx)
     n_shard = idx.numel()
+    # --binarize: the trainer reads the binarizer's compact buffer (rewritten in
+    # place every epoch) and every test pass reads the fixed binarized test set
+    binarizer, test = _binarizers(spec, opts, train, test, idx)
+    if binarizer is not None:
+        trainer.bind_train_data(binarizer.data, binarizer.index())
+    else:
+        trainer.bind_train_data(train.data, idx)
     # capture the step graphs and the test-set eval graphs and load the
     # decode kernels now, like the reference's model/DDP construction before
     # its timer starts (vae-hpo.py:159)
@@ -496,7 +542,8 @@ def run_trial(spec: TrialSpec, group, opts: RunOptions, data=None, num_trials: O
                 raise RuntimeError("a replica of this trial failed; stopping the trial on every member")
             maybe_inject(trial=spec.group_id, epoch=epoch, rank=world_rank)
             train_loss, test_loss = _run_epoch(trainer, epoch, n_shard, train, test, opts, group, rdir, shape,
-                                               gen, device, spec, grank, metrics, fault_at=fault_at, watch=watch)
+                                               gen, device, spec, grank, metrics, fault_at=fault_at, watch=watch,
+                                               binarizer=binarizer)
             epochs_done += 1
         if not agree_healthy(spec.group_id, True):
             checked_in = True
@@ -523,13 +570,15 @@ def run_trial(spec: TrialSpec, group, opts: RunOptions, data=None, num_trials: O
 
 
 def _run_epoch(trainer, epoch, n_shard, train, test, opts, group, rdir, shape, gen, device, spec, grank, metrics,
-               step0=None, t_train=None, tag="", fault_at=None, watch=None):
+               step0=None, t_train=None, tag="", fault_at=None, watch=None, binarizer=None, binarize_s=None):
     te = time.perf_counter()
+    if step0 is None:  # (packed trials redraw where they enqueue their epoch)
+        binarize_s = _refresh_train(binarizer, trainer, epoch, opts, device)
     train_loss = _train_epoch(trainer, epoch, n_shard, len(train), opts, group, step0=step0, tag=tag,
                               fault_at=fault_at, watch=watch)
     if t_train is None:
         t_train = time.perf_counter() - te
-    phases = {}
+    phases = {} if binarize_s is None or not opts.profile else {"binarize_s": binarize_s}
 
     def _mark(name, t):
         if opts.profile and device.type == "cuda":
@@ -551,7 +600,7 @@ def _run_epoch(trainer, epoch, n_shard, train, test, opts, group, rdir, shape, g
     t = _mark("sample_s", t)
     if opts.ckpt_dir and grank == 0:
         with trace.range(f"ckpt_{epoch}"):
-            ckpt.save_trial(opts.ckpt_dir, trainer, spec, epoch)
+            ckpt.save_trial(opts.ckpt_dir, trainer, spec, epoch, binarize=opts.binarize)
     _mark("ckpt_s", t)
     # lr / kl_beta: the effective values of the epoch's last step as the kernels
     # recorded them (= lr_base / beta when the trial has no schedule)
@@ -578,6 +627,7 @@ def run_packed_trials(specs, group, opts: RunOptions, data=None, num_trials: Opt
     world_rank = dist.get_rank() if dist.is_initialized() else 0
     world_size = dist.get_world_size() if dist.is_initialized() else 1
     gsize = dist.get_world_size(group) if dist.is_initialized() else 1
+    check_mode(opts.binarize)
     if gsize != 1:
         raise ValueError("trial packing runs independent trials: it needs groups of one rank")
     total = num_trials if num_trials is not None else world_size * len(specs)
@@ -596,17 +646,23 @@ def run_packed_trials(specs, group, opts: RunOptions, data=None, num_trials: Opt
         start = 1
         if opts.ckpt_dir and opts.resume:
             prog = ckpt.load_latest(opts.ckpt_dir, spec.group_id, trainer)
+            _check_resumed_binarize(prog, opts, spec.group_id)
             if prog is not None:
                 start = prog["epoch"] + 1
         idx = shard_indices(len(train), total, spec.group_id)  # packing extension: one shard per trial
-        trainer.bind_train_data(train.data, idx)
-        trainer.prepare([opts.batch_size, idx.numel() % opts.batch_size], test.data if opts.eval_each_epoch else None)
+        binarizer, ttest = _binarizers(spec, opts, train, test, idx)  # --binarize: a buffer pair per trial
+        if binarizer is not None:
+            trainer.bind_train_data(binarizer.data, binarizer.index())
+        else:
+            trainer.bind_train_data(train.data, idx)
+        trainer.prepare([opts.batch_size, idx.numel() % opts.batch_size], ttest.data if opts.eval_each_epoch else None)
         rdir = (f"results-t{spec.group_id}-0" if opts.results else None)
         tr.append(dict(spec=spec, trainer=trainer, start=start, n_shard=idx.numel(), rdir=rdir,
                        stream=torch.cuda.Stream(device) if device.type == "cuda" else None,
                        metrics=TrialMetrics(opts.metrics_dir, spec.group_id, enabled=True),
                        gen=torch.Generator(device="cpu").manual_seed(spec.seed * 7919 + 17),
-                       done=0, train_loss=float("nan"), test_loss=float("nan"), failure={}))
+                       done=0, train_loss=float("nan"), test_loss=float("nan"), failure={},
+                       binarizer=binarizer, test=ttest, binarize_s=None))
     for t in tr:  # a packed epoch is enqueued whole: its losses must fit the ring (checked before any launch)
         nb = -(-t["n_shard"] // opts.batch_size)
         if nb > LOSS_RING:
@@ -624,8 +680,10 @@ def run_packed_trials(specs, group, opts: RunOptions, data=None, num_trials: Opt
                 maybe_inject(trial=t["spec"].group_id, epoch=epoch, rank=world_rank)
                 if t["stream"] is not None:
                     with torch.cuda.stream(t["stream"]):
+                        t["binarize_s"] = _refresh_train(t["binarizer"], t["trainer"], epoch, opts, device)
                         t["step0"], _ = _launch_epoch(t["trainer"], epoch, t["n_shard"], opts)
                 else:
+                    t["binarize_s"] = _refresh_train(t["binarizer"], t["trainer"], epoch, opts, device)
                     t["step0"], _ = _launch_epoch(t["trainer"], epoch, t["n_shard"], opts)
         if device.type == "cuda":
             torch.cuda.synchronize(device)
@@ -637,8 +695,9 @@ def run_packed_trials(specs, group, opts: RunOptions, data=None, num_trials: Opt
             with guarded(f"trial {spec.group_id} (world rank {world_rank})", None,
                          lambda e, t=t: t["failure"].setdefault("error", f"{type(e).__name__}: {e}")):
                 t["train_loss"], t["test_loss"] = _run_epoch(
-                    t["trainer"], epoch, t["n_shard"], train, test, opts, group, t["rdir"], shape, t["gen"], device,
-                    spec, 0, t["metrics"], step0=t["step0"], t_train=t_train, tag=f"(trial {spec.group_id}) ")
+                    t["trainer"], epoch, t["n_shard"], train, t["test"], opts, group, t["rdir"], shape, t["gen"],
+                    device, spec, 0, t["metrics"], step0=t["step0"], t_train=t_train,
+                    tag=f"(trial {spec.group_id}) ", binarize_s=t["binarize_s"])
                 t["done"] += 1
     flush_images()
     global_barrier()
@@ -649,12 +708,12 @@ def run_packed_trials(specs, group, opts: RunOptions, data=None, num_trials: Opt
         if opts.iw_samples > 0 and not t["failure"]:
             with guarded(f"trial {t['spec'].group_id} IW pass (world rank {world_rank})", None,
                          lambda e, t=t: t["failure"].setdefault("error", f"{type(e).__name__}: {e}")):
-                t["extra"] = _iw_eval(t["trainer"], test, opts, group, t["metrics"], device,
+                t["extra"] = _iw_eval(t["trainer"], t["test"], opts, group, t["metrics"], device,
                                       tag=f"(trial {t['spec'].group_id}) ")
         if opts.latent_report and not t["failure"]:
             with guarded(f"trial {t['spec'].group_id} latent pass (world rank {world_rank})", None,
                          lambda e, t=t: t["failure"].setdefault("error", f"{type(e).__name__}: {e}")):
-                t["extra"] = dict(t["extra"], **_latent_eval(t["trainer"], test, opts, group, t["metrics"], device,
+                t["extra"] = dict(t["extra"], **_latent_eval(t["trainer"], t["test"], opts, group, t["metrics"], device,
                                                              tag=f"(trial {t['spec'].group_id}) "))
     return [TrialResult(t["spec"].group_id, t["done"], t["n_shard"], t["done"] * t["n_shard"], t1 - t0,
                         t["train_loss"] / len(train), t["test_loss"], failed=bool(t["failure"]),

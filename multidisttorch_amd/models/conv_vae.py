@@ -331,6 +331,10 @@ class ConvVaeTrainer(VaeTrainerBase):
         self._invalidate_prefetch()
         self._plans28.clear()
 
+    def train_data_changed(self):
+        # the rows the last finalize gathered for the next step (f28_xn) are the old ones
+        self._invalidate_prefetch()
+
     def attach_reducer(self, reducer):
         """Reducer over ``self.grads`` whose bucket bounds fall on layer starts
         (see ``bucket_bounds``); buckets launch as their layers' backward ends.

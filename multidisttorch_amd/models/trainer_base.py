@@ -224,6 +224,12 @@ class VaeTrainerBase(GraphedEval, GraphedIwEval, GraphedLatentEval):
         self._data = (X.contiguous(), idx, n, nb)
         self._graphs.clear()
 
+    def train_data_changed(self):
+        """The bound training rows were rewritten in place (same tensor, same
+        index list: ``data/binarize.py``). Captured step graphs read the rows
+        through the bound pointer at every replay and stay valid; a trainer
+        that keeps rows gathered ahead of the step drops them here."""
+
     # ------------------------------------------------------------------ step
     def attach_reducer(self, reducer):
         """Reducer over ``self.grads`` whose bucket bounds come from ``bucket_bounds``."""

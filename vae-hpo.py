@@ -18,7 +18,9 @@ stream each: trial packing on MI355X), ``--iw-samples K`` (after each trial's
 last epoch: the K-sample importance-weighted test log-likelihood, a score that
 does not depend on the trial's beta), ``--latent-report`` (+ ``--au-threshold``;
 after each trial's last epoch: active units and the MI / TC / dimension-wise-KL
-split of the KL term over the test set).
+split of the KL term over the test set), ``--binarize {none,threshold,static,dynamic}``
+(train and test on {0, 1} pixels, redrawn on the device: the test loss and the
+IW bound are then negative log-likelihoods of binarized data; one value per run).
 """
 
 import argparse
@@ -31,6 +33,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 from utils import *  # noqa: F401,F403  (reference-compatible API + re-exports)
 
+from multidisttorch_amd.data.binarize import BINARIZE_CHOICES
 from multidisttorch_amd.hpo.runner import RunOptions, idle_rank, run_packed_trials, run_trial
 from multidisttorch_amd.hpo.trial import build_specs, parse_list
 from multidisttorch_amd.parallel.autotune import parse_bucket_mb
@@ -95,6 +98,10 @@ def parse_args(argv=None):
                              "dimension-wise-KL split of the KL term over the test set")
     parser.add_argument("--au-threshold", type=float, default=0.01,
                         help="a latent dimension is active when the variance of its posterior mean exceeds this")
+    parser.add_argument("--binarize", type=str, default="none", choices=list(BINARIZE_CHOICES),
+                        help="binarize the data on the device: threshold = x >= 0.5; static = one Bernoulli(x) draw "
+                             "per trial; dynamic = a fresh draw of the training rows every epoch. The test set is "
+                             "drawn once. One value for the whole run: trials of a sweep share a likelihood")
     return parser.parse_args(argv)
 
 
@@ -136,7 +143,7 @@ def main(argv=None):
                       synthetic=False if args.real_data else (True if args.synthetic else None),
                       model=args.model, image_size=args.image_size, bucket_mb=parse_bucket_mb(args.bucket_mb),
                       profile=args.profile, iw_samples=max(0, args.iw_samples), latent_report=args.latent_report,
-                      au_threshold=args.au_threshold)
+                      au_threshold=args.au_threshold, binarize=args.binarize)
     results = []
     member = False
     for group_id, group in enumerate(processes_groups):
@@ -176,6 +183,8 @@ def main(argv=None):
                    "wall_s": round(wall, 4),
                    "value": round(sum(per_trial.values()) / max(wall, 1e-9), 1), "unit": "samples/s",
                    "failed_trials": sorted(failed)}
+        if opts.binarize != "none":
+            summary["binarize"] = opts.binarize  # the likelihood every score of this run is under
         if opts.iw_samples > 0:
             # per-image means over the test set; the lowest bound on -log p(x) is the best trial
             summary["iw_samples"] = opts.iw_samples
