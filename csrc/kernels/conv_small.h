@@ -79,14 +79,16 @@ __host__ __device__ inline int splitk_rp(int ks) {
   while (rp < 64 && rp * 4 < ks) rp *= 2;
   return rp;
 }
-// Row form (the default where it applies: Z a power of two in [8, 512]): one
-// block per sample row. Its 2Z (forward) / Z (backward) slab columns are read
+// Row form (the default where it applies: Z a power of two in [8, 256]): one
+// 256-thread block per sample row, thread c owning latent column c -- hence
+// Z <= 256 (at 512 columns 256.. had no owner: never written, their KLD never
+// summed). Its 2Z (forward) / Z (backward) slab columns are read
 // as float4s by Z/2 (Z/4) lanes per k-slice row -- every wave-instruction
 // covers whole 256-B+ row pieces -- with 256/lanes k-slices in flight, then a
 // fixed-order LDS combine. The element-strided form above reads 16 B of each
 // 64-B segment per wave-instruction (4x the slab bytes fetched: 16.6 MB for a
 // 4 MB slab at the 128x128 decoder Linear) and stays for other Z.
-__host__ __device__ inline bool combine_rows_ok(int Z) { return Z >= 8 && Z <= 512 && (Z & (Z - 1)) == 0; }
+__host__ __device__ inline bool combine_rows_ok(int Z) { return Z >= 8 && Z <= 256 && (Z & (Z - 1)) == 0; }
 __host__ __device__ inline int combine_reparam_blocks(int ks, int B, int Z) {
   if (combine_rows_ok(Z)) return B;
   const int cnt = 256 / splitk_rp(ks);

@@ -120,6 +120,34 @@ static void check_min(const c10::optional<at::Tensor>& t, int64_t n, const char*
   if (t.has_value() && t->defined()) TORCH_CHECK(t->numel() >= n, w, " too small: ", t->numel(), " < ", n);
 }
 
+// Argument checks of the small step kernels (conv_bf16.hip), which take raw
+// pointers: `t` is a contiguous tensor of dtype `ty` with >= n elements on the
+// device of `ref` (the op's first tensor). A bad call stops here, on the host.
+static void check_buf(const at::Tensor& t, c10::ScalarType ty, int64_t n, const at::Tensor& ref, const char* op,
+                      const char* name) {
+  TORCH_CHECK(t.defined() && t.is_cuda() && t.scalar_type() == ty && t.is_contiguous(), op, ": ", name,
+              " must be a contiguous CUDA tensor of dtype ", ty);
+  TORCH_CHECK(t.get_device() == ref.get_device(), op, ": ", name, " is on another device than the op's first tensor");
+  TORCH_CHECK(t.numel() >= n, op, ": ", name, " too small: ", t.numel(), " < ", n);
+}
+static void check_buf(const c10::optional<at::Tensor>& t, c10::ScalarType ty, int64_t n, const at::Tensor& ref,
+                      const char* op, const char* name) {
+  if (t.has_value() && t->defined()) check_buf(*t, ty, n, ref, op, name);
+}
+// a TrialState device buffer (train_state / eval_state / hparams) of >= `bytes` bytes
+static void check_blob(const at::Tensor& t, size_t bytes, const at::Tensor& ref, const char* op, const char* name) {
+  TORCH_CHECK(t.defined() && t.is_cuda() && t.is_contiguous() && t.get_device() == ref.get_device() &&
+                  t.numel() * t.element_size() >= (int64_t)bytes,
+              op, ": ", name, " must be a TrialState buffer (>= ", bytes, " bytes) on the op's device");
+}
+// B x Z latent extents: positive, and the element index fits the 32-bit Philox counter word / int arithmetic
+static void check_bz(int64_t B, int64_t Z, const char* op) {
+  const int64_t lim = int64_t(1) << 30;
+  TORCH_CHECK(B >= 1 && Z >= 1 && B < lim && Z < lim && B * 2 * Z < 2 * lim, op,
+              ": need B >= 1, Z >= 1 and 2 B Z < 2^31, got B = ", B, ", Z = ", Z);
+}
+static int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
 // fwd: the forward-pass call of this geometry (may select the direct kernel
 // where the backward-data call of the same geometry keeps the fusable one)
 std::vector<int64_t> igemm_plan(int64_t mode, const std::vector<int64_t>& dv, bool allow_split, bool fwd) {
@@ -275,6 +303,13 @@ void thin_tconv(const at::Tensor& G16, const at::Tensor& Wf, const std::vector<i
 void colsum(const at::Tensor& G16, int64_t M, int64_t N, int64_t rows_per, at::Tensor slab, Job* job) {
   check_bf16(G16, "G16");
   check_f32(slab, "slab");
+  // 8 bf16 columns (16 B) per thread; rows_per divides below
+  const int64_t lim = int64_t(1) << 30;
+  TORCH_CHECK(M >= 1 && M < lim && N >= 8 && N < lim && N % 8 == 0 && rows_per >= 1 && rows_per < lim &&
+                  M * N < 2 * lim,
+              "colsum: need M >= 1, N a positive multiple of 8 and rows_per >= 1, got M = ", M, ", N = ", N,
+              ", rows_per = ", rows_per);
+  TORCH_CHECK(slab.get_device() == G16.get_device(), "colsum: slab is on another device than G16");
   TORCH_CHECK(G16.numel() >= M * N, "G16 too small");
   TORCH_CHECK(slab.numel() >= ((M + rows_per - 1) / rows_per) * N, "colsum slab too small");
   if (job) {
@@ -286,6 +321,14 @@ void colsum(const at::Tensor& G16, int64_t M, int64_t N, int64_t rows_per, at::T
 
 void reparam(const at::Tensor& mulv, at::Tensor eps, at::Tensor z16, const c10::optional<at::Tensor>& z32, int64_t B,
              int64_t Z, const at::Tensor& state, const at::Tensor& hparams, int64_t stream, at::Tensor kld_part) {
+  check_bz(B, Z, "reparam");
+  check_buf(mulv, torch::kFloat32, B * 2 * Z, mulv, "reparam", "mulv");
+  check_buf(eps, torch::kFloat32, B * Z, mulv, "reparam", "eps");
+  check_buf(z16, torch::kBFloat16, B * Z, mulv, "reparam", "z16");
+  check_buf(z32, torch::kFloat32, B * Z, mulv, "reparam", "z32");
+  check_blob(state, sizeof(TrainState), mulv, "reparam", "state");
+  check_blob(hparams, sizeof(HParams), mulv, "reparam", "hparams");
+  check_buf(kld_part, torch::kFloat32, cdiv64(B * Z, 256), mulv, "reparam", "kld_part");  // one partial per block
   rc(mdt_reparam(mulv.data_ptr<float>(), eps.data_ptr<float>(), z16.data_ptr(), (float*)opt_ptr(z32), (int)B, (int)Z,
                  state.data_ptr(), hparams.data_ptr(), (unsigned)stream, kld_part.data_ptr<float>(), cur()),
      "reparam");
@@ -296,11 +339,13 @@ void reparam(const at::Tensor& mulv, at::Tensor eps, at::Tensor z16, const c10::
 // launch; follows the trial's schedule) or, with no state, HParams.kl_beta.
 const float* kl_weight_ptr(const at::Tensor& hparams, const c10::optional<at::Tensor>& state) {
   if (state.has_value() && state->defined()) {
-    TORCH_CHECK(state->is_cuda() && state->numel() * state->element_size() >= (int64_t)sizeof(TrainState),
+    TORCH_CHECK(state->is_cuda() && state->is_contiguous() &&
+                    state->numel() * state->element_size() >= (int64_t)sizeof(TrainState),
                 "state: a TrialState device buffer");
     return reinterpret_cast<const float*>(static_cast<const char*>(state->data_ptr()) + offsetof(TrainState, kl_t));
   }
-  TORCH_CHECK(hparams.is_cuda() && hparams.numel() * hparams.element_size() >= (int64_t)sizeof(HParams),
+  TORCH_CHECK(hparams.defined() && hparams.is_cuda() && hparams.is_contiguous() &&
+                  hparams.numel() * hparams.element_size() >= (int64_t)sizeof(HParams),
               "hparams: a TrialState device buffer");
   return reinterpret_cast<const float*>(static_cast<const char*>(hparams.data_ptr()) + offsetof(HParams, kl_beta));
 }
@@ -308,6 +353,12 @@ const float* kl_weight_ptr(const at::Tensor& hparams, const c10::optional<at::Te
 void reparam_bwd(const at::Tensor& dz, const at::Tensor& mulv, const at::Tensor& eps, at::Tensor dmulv,
                  const c10::optional<at::Tensor>& dmulv16, int64_t B, int64_t Z, const at::Tensor& hparams,
                  const c10::optional<at::Tensor>& state) {
+  check_bz(B, Z, "reparam_bwd");
+  check_buf(dz, torch::kFloat32, B * Z, dz, "reparam_bwd", "dz");
+  check_buf(mulv, torch::kFloat32, B * 2 * Z, dz, "reparam_bwd", "mulv");
+  check_buf(eps, torch::kFloat32, B * Z, dz, "reparam_bwd", "eps");
+  check_buf(dmulv, torch::kFloat32, B * 2 * Z, dz, "reparam_bwd", "dmulv");
+  check_buf(dmulv16, torch::kBFloat16, B * 2 * Z, dz, "reparam_bwd", "dmulv16");
   rc(mdt_reparam_bwd(dz.data_ptr<float>(), mulv.data_ptr<float>(), eps.data_ptr<float>(), dmulv.data_ptr<float>(),
                      const_cast<void*>(opt_ptr(dmulv16)), (int)B, (int)Z, kl_weight_ptr(hparams, state), cur()),
      "reparam_bwd");
@@ -316,6 +367,17 @@ void reparam_bwd(const at::Tensor& dz, const at::Tensor& mulv, const at::Tensor&
 void gather_rows(const at::Tensor& X, const at::Tensor& idx, const at::Tensor& state, int64_t B, int64_t M,
                  at::Tensor xb) {
   TORCH_CHECK(X.scalar_type() == torch::kFloat32 && idx.scalar_type() == torch::kInt32, "gather_rows dtypes");
+  // Not checkable here: the rows idx[cursor * B + i] depend on device state (the
+  // cursor) and on the index values; the trainer guarantees them (see f28 below)
+  TORCH_CHECK(X.dim() == 2 && X.size(0) >= 1 && X.size(1) >= 4 && X.size(1) % 4 == 0 && X.size(1) < (int64_t(1) << 30),
+              "gather_rows: X must be [rows][P] with P a positive multiple of 4 (16-B row pieces)");
+  const int64_t P = X.size(1);
+  TORCH_CHECK(B >= 1 && M >= 1 && M <= B && B < (int64_t(1) << 30), "gather_rows: need 1 <= M <= B, got M = ", M,
+              ", B = ", B);
+  check_buf(X, torch::kFloat32, P, X, "gather_rows", "X");
+  check_buf(idx, torch::kInt32, B, X, "gather_rows", "idx");  // at least the batch at cursor 0
+  check_blob(state, sizeof(TrainState), X, "gather_rows", "state");
+  check_buf(xb, torch::kFloat32, M * P, X, "gather_rows", "xb");
   rc(mdt_gather_rows(X.data_ptr<float>(), idx.data_ptr<int32_t>(), state.data_ptr(), (int)B, (int)M,
                      (int)X.size(1), xb.data_ptr<float>(), cur()),
      "gather_rows");
@@ -324,6 +386,23 @@ void gather_rows(const at::Tensor& X, const at::Tensor& idx, const at::Tensor& s
 void bce_logits(const at::Tensor& logits, const at::Tensor& X, const c10::optional<at::Tensor>& rows, int64_t B,
                 int64_t P, const c10::optional<at::Tensor>& dlog16, const c10::optional<at::Tensor>& recon,
                 at::Tensor part, const c10::optional<at::Tensor>& gpart) {
+  const int64_t lim = int64_t(1) << 30;
+  TORCH_CHECK(B >= 1 && P >= 1 && B < lim && P < lim, "bce_logits: need B >= 1 and P >= 1, got B = ", B, ", P = ", P);
+  const int64_t n = B * P, nblk = cdiv64(n, 256);
+  TORCH_CHECK(nblk < 2 * lim, "bce_logits: B * P too large");
+  check_buf(logits, torch::kFloat32, n, logits, "bce_logits", "logits");
+  if (rows.has_value() && rows->defined()) {
+    // target row i = X[rows[i]]: the index VALUES are the caller's to keep inside X
+    check_buf(rows, torch::kInt32, B, logits, "bce_logits", "rows");
+    check_buf(X, torch::kFloat32, P, logits, "bce_logits", "X");
+    TORCH_CHECK(X.numel() % P == 0, "bce_logits: X must hold whole rows of P = ", P, " elements");
+  } else {
+    check_buf(X, torch::kFloat32, n, logits, "bce_logits", "X");
+  }
+  check_buf(dlog16, torch::kBFloat16, n, logits, "bce_logits", "dlog16");
+  check_buf(recon, torch::kFloat32, n, logits, "bce_logits", "recon");
+  check_buf(part, torch::kFloat32, nblk, logits, "bce_logits", "part");  // one partial per 256-element block
+  check_buf(gpart, torch::kFloat32, nblk, logits, "bce_logits", "gpart");
   rc(mdt_bce_logits(logits.data_ptr<float>(), X.data_ptr<float>(), (const int*)opt_ptr(rows), (int)B, (int)P,
                     const_cast<void*>(opt_ptr(dlog16)), (float*)opt_ptr(recon), part.data_ptr<float>(),
                     (float*)opt_ptr(gpart), cur()),
@@ -332,7 +411,13 @@ void bce_logits(const at::Tensor& logits, const at::Tensor& X, const c10::option
 
 void loss_finalize2(const at::Tensor& bce_part, int64_t nb, const at::Tensor& kld_part, int64_t nk, at::Tensor state,
                     const at::Tensor& hparams, bool advance_cursor, Job* job, bool advance_step) {
+  TORCH_CHECK(nb >= 0 && nk >= 0 && nb < (int64_t(1) << 31) && nk < (int64_t(1) << 31),
+              "loss_finalize2: partial counts out of range");
   TORCH_CHECK(bce_part.numel() >= nb && kld_part.numel() >= nk, "loss partials too small");
+  check_buf(bce_part, torch::kFloat32, nb, bce_part, "loss_finalize2", "bce_part");
+  check_buf(kld_part, torch::kFloat32, nk, bce_part, "loss_finalize2", "kld_part");
+  check_blob(state, sizeof(TrainState), bce_part, "loss_finalize2", "state");
+  check_blob(hparams, sizeof(HParams), bce_part, "loss_finalize2", "hparams");
   if (job) {
     rc(mdt_job_loss(&job->main, bce_part.data_ptr<float>(), (int)nb, kld_part.data_ptr<float>(), (int)nk,
                     state.data_ptr(), hparams.data_ptr(), (advance_cursor ? 1 : 0) | (advance_step ? 2 : 0)),
@@ -558,6 +643,8 @@ void f28_step(const std::vector<c10::optional<at::Tensor>>& tf, const std::vecto
 }
 
 void step_begin(at::Tensor state, const at::Tensor& hparams) {
+  check_blob(state, sizeof(TrainState), state, "step_begin", "state");
+  check_blob(hparams, sizeof(HParams), state, "step_begin", "hparams");
   rc(mdt_step_begin(state.data_ptr(), hparams.data_ptr(), cur()), "step_begin");
 }
 
@@ -606,6 +693,16 @@ void adam_cast(at::Tensor P, const at::Tensor& G, at::Tensor M, at::Tensor V, at
                int64_t nseg, const at::Tensor& state, const at::Tensor& hparams, bool do_adam) {
   TORCH_CHECK(G.numel() == P.numel() && M.numel() == P.numel() && V.numel() == P.numel() && w16.numel() == P.numel(),
               "adam_cast: P, G, m, v and w16 must be arenas of one size");
+  const int64_t total = P.numel();
+  TORCH_CHECK(total >= 4 && total % 4 == 0, "adam_cast: the arena length must be a positive multiple of 4, got ",
+              total);
+  check_buf(P, torch::kFloat32, total, P, "adam_cast", "P");
+  check_buf(G, torch::kFloat32, total, P, "adam_cast", "G");
+  check_buf(M, torch::kFloat32, total, P, "adam_cast", "m");
+  check_buf(V, torch::kFloat32, total, P, "adam_cast", "v");
+  check_buf(w16, torch::kBFloat16, total, P, "adam_cast", "w16");
+  check_blob(state, sizeof(TrainState), P, "adam_cast", "state");
+  check_blob(hparams, sizeof(HParams), P, "adam_cast", "hparams");
   rc(mdt_adam_cast(P.data_ptr<float>(), G.data_ptr<float>(), M.data_ptr<float>(), V.data_ptr<float>(),
                    w16.data_ptr(), segs.data_ptr(), (int)nseg, P.numel(), state.data_ptr(), hparams.data_ptr(),
                    do_adam ? 1 : 0, cur()),
@@ -708,9 +805,20 @@ void combine_reparam(const at::Tensor& ws, int64_t ks, const c10::optional<at::T
                      at::Tensor eps, at::Tensor z16, const c10::optional<at::Tensor>& z32, int64_t B, int64_t Z,
                      const at::Tensor& state, const at::Tensor& hparams, int64_t stream, at::Tensor kld_part) {
   check_f32(ws, "ws");
-  TORCH_CHECK(ws.numel() >= ks * B * 2 * Z && mulv.numel() >= B * 2 * Z && eps.numel() >= B * Z &&
-                  z16.numel() >= B * Z && kld_part.numel() >= mdt_combine_reparam_blocks((int)ks, (int)B, (int)Z),
-              "combine_reparam: buffer too small");
+  check_bz(B, Z, "combine_reparam");
+  TORCH_CHECK(ks >= 1 && ks < (int64_t(1) << 20), "combine_reparam: need 1 <= ks < 2^20 k-slices, got ", ks);
+  // the row form reads the slab as float4s
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(ws.data_ptr()) % 16 == 0, "combine_reparam: ws must be 16-B aligned");
+  check_buf(ws, torch::kFloat32, ks * B * 2 * Z, ws, "combine_reparam", "ws");
+  check_buf(bias, torch::kFloat32, 2 * Z, ws, "combine_reparam", "bias");
+  check_buf(mulv, torch::kFloat32, B * 2 * Z, ws, "combine_reparam", "mulv");
+  check_buf(eps, torch::kFloat32, B * Z, ws, "combine_reparam", "eps");
+  check_buf(z16, torch::kBFloat16, B * Z, ws, "combine_reparam", "z16");
+  check_buf(z32, torch::kFloat32, B * Z, ws, "combine_reparam", "z32");
+  check_blob(state, sizeof(TrainState), ws, "combine_reparam", "state");
+  check_blob(hparams, sizeof(HParams), ws, "combine_reparam", "hparams");
+  check_buf(kld_part, torch::kFloat32, mdt_combine_reparam_blocks((int)ks, (int)B, (int)Z), ws, "combine_reparam",
+            "kld_part");  // one partial per block
   rc(mdt_combine_reparam(ws.data_ptr<float>(), (int)ks, (const float*)opt_ptr(bias), mulv.data_ptr<float>(),
                          eps.data_ptr<float>(), z16.data_ptr(), (float*)opt_ptr(z32), (int)B, (int)Z, state.data_ptr(),
                          hparams.data_ptr(), (unsigned)stream, kld_part.data_ptr<float>(), cur()),
@@ -722,7 +830,15 @@ void combine_reparam_bwd(const at::Tensor& ws, int64_t ks, const at::Tensor& mul
                          const c10::optional<at::Tensor>& dz, int64_t B, int64_t Z, const at::Tensor& hparams,
                          const c10::optional<at::Tensor>& state) {
   check_f32(ws, "ws");
-  TORCH_CHECK(ws.numel() >= ks * B * Z && dmulv.numel() >= B * 2 * Z, "combine_reparam_bwd: buffer too small");
+  check_bz(B, Z, "combine_reparam_bwd");
+  TORCH_CHECK(ks >= 1 && ks < (int64_t(1) << 20), "combine_reparam_bwd: need 1 <= ks < 2^20 k-slices, got ", ks);
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(ws.data_ptr()) % 16 == 0, "combine_reparam_bwd: ws must be 16-B aligned");
+  check_buf(ws, torch::kFloat32, ks * B * Z, ws, "combine_reparam_bwd", "ws");
+  check_buf(mulv, torch::kFloat32, B * 2 * Z, ws, "combine_reparam_bwd", "mulv");
+  check_buf(eps, torch::kFloat32, B * Z, ws, "combine_reparam_bwd", "eps");
+  check_buf(dmulv, torch::kFloat32, B * 2 * Z, ws, "combine_reparam_bwd", "dmulv");
+  check_buf(dmulv16, torch::kBFloat16, B * 2 * Z, ws, "combine_reparam_bwd", "dmulv16");
+  check_buf(dz, torch::kFloat32, B * Z, ws, "combine_reparam_bwd", "dz");
   rc(mdt_combine_reparam_bwd(ws.data_ptr<float>(), (int)ks, mulv.data_ptr<float>(), eps.data_ptr<float>(),
                              dmulv.data_ptr<float>(), const_cast<void*>(opt_ptr(dmulv16)), (float*)opt_ptr(dz), (int)B,
                              (int)Z, kl_weight_ptr(hparams, state), cur()),

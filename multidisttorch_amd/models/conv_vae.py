@@ -26,6 +26,7 @@ backend and the numerical oracle of the GPU tests.
 from __future__ import annotations
 
 import math
+import operator
 import os
 import sys
 from dataclasses import dataclass
@@ -41,7 +42,7 @@ from .iw import iw_log_weights
 from .mlp_vae import reference_adam_
 from .trainer_base import EVAL_STREAM, VaeTrainerBase
 
-__all__ = ["Layer", "conv_vae_spec", "TorchConvVAE", "ConvVaeTrainer", "conv_layout"]
+__all__ = ["Layer", "conv_vae_spec", "TorchConvVAE", "ConvVaeTrainer", "conv_layout", "check_latent_size"]
 
 
 @dataclass(frozen=True)
@@ -56,6 +57,28 @@ class Layer:
     relu: bool
     in_hw: int         # input spatial size (1 for linear)
     out_hw: int
+
+
+Z_MIN, Z_MAX = 8, 1024
+
+
+def check_latent_size(z) -> int:
+    """The latent sizes ``ConvVaeTrainer`` accepts: multiples of 8 in
+    [Z_MIN, Z_MAX], the same on both backends so a configuration never depends
+    on the backend. The HIP layer path needs z % 8 == 0: z is the reduction
+    length K of the decoder Linear (``plan_fwd`` rejects K % 8 != 0: operands
+    are staged in 16-B pieces of 8 bf16) and its weight gradient reads z16
+    rows in the same pieces; the head's 2z output channels (``plan_wgrad``:
+    CO % 8, the column-sum kernel: N % 8) need only z % 4. The upper end keeps
+    every slab offset of the two Linear layers inside int32 at both image
+    sizes. See docs/KERNELS.md, "conv-VAE small kernels: domain and checks"."""
+    try:
+        zi = operator.index(z)
+    except TypeError:
+        zi = -1
+    if not Z_MIN <= zi <= Z_MAX or zi % 8:
+        raise ValueError(f"conv-VAE latent size z must be a multiple of 8 in [{Z_MIN}, {Z_MAX}], got {z!r}")
+    return zi
 
 
 def conv_vae_spec(image: int = 28, channels: int = 1, z: int = 32) -> List[Layer]:
@@ -206,6 +229,7 @@ class ConvVaeTrainer(VaeTrainerBase):
                  betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0, decoupled_wd: bool = False,
                  rng_stream: int = 0, use_graphs: bool = True, graph_steps: int = 10, init_seed: Optional[int] = None,
                  schedule: Optional[Schedule] = None):
+        z = check_latent_size(z)
         super().__init__(batch_size, device, backend, seed, rng_stream, lr, kl_beta, betas, eps, weight_decay,
                          decoupled_wd, use_graphs, graph_steps, schedule)
         backend = self.backend

@@ -181,8 +181,16 @@ def _emulated_layer_path(tr, x32, eps, beta=1.0):
     return float(loss), out
 
 
-@pytest.mark.parametrize("image,M", [(28, 64), (128, 16), (128, 13)])
-def test_conv_vae_grads_match_bf16_emulated_reference(image, M, native_ext):
+# (image, M, z): z None = the shipped latent size at B = 64 (28x28) / 16 (128x128); the others run the 28x28
+# model at B = 16 over the latent-size domain (models/conv_vae.py check_latent_size): the smallest z, one that
+# is no power of two (element-strided split-K combines), and 128
+_GRAD_CASES = [pytest.param(28, 64, None, id="28-64"), pytest.param(128, 16, None, id="128-16"),
+               pytest.param(128, 13, None, id="128-13")]
+_GRAD_CASES += [pytest.param(28, M, z, id=f"28-{M}-z{z}") for z in (8, 24, 128) for M in (16, 5)]
+
+
+@pytest.mark.parametrize("image,M,z", _GRAD_CASES)
+def test_conv_vae_grads_match_bf16_emulated_reference(image, M, z, native_ext):
     """Layer-path step (28x28 with MDT_CONV_F28=0; 128x128: direct kernels,
     im2col GEMMs, thin edge kernels, split-K head) against a float64 reference
     rounded to bf16 where the kernels store bf16: every gradient tensor within
@@ -193,9 +201,9 @@ def test_conv_vae_grads_match_bf16_emulated_reference(image, M, native_ext):
     from multidisttorch_amd.models.conv_vae import ConvVaeTrainer
 
     dev = torch.device("cuda")
-    B = 64 if image == 28 else 16
-    tr = ConvVaeTrainer(batch_size=B, image=image, z=32 if image == 28 else 64, device=dev, backend="hip", seed=2,
-                        use_graphs=False)
+    B = 16 if z is not None or image != 28 else 64
+    tr = ConvVaeTrainer(batch_size=B, image=image, z=z or (32 if image == 28 else 64), device=dev, backend="hip",
+                        seed=2, use_graphs=False)
     D = image * image
     X = torch.rand(4 * B, D, generator=torch.Generator().manual_seed(3)).to(dev)
     idx = torch.randperm(4 * B, generator=torch.Generator().manual_seed(4)).to(dev, torch.int32)

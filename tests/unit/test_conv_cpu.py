@@ -60,6 +60,22 @@ def test_conv_bucket_bounds_fall_on_layer_starts():
     assert len(tr.bucket_bounds(0.5)) > len(tr.bucket_bounds(8)) >= 2
 
 
+def test_latent_size_outside_the_layer_path_domain_raises_at_construction():
+    """z must be a multiple of 8 in [8, 1024] on BOTH backends (the HIP layer
+    path's GEMM planner rejects the decoder Linear's K = z otherwise, e.g.
+    z = 20, and used to do so only at the first step); the check precedes
+    every device or backend decision, so the hip backend is asserted here too."""
+    import pytest
+
+    for z in (20, 4, 0, -8, 12, 1032, 2048, 32.0, "32", None, True):
+        for backend in ("torch", "hip"):
+            with pytest.raises(ValueError, match="multiple of 8"):
+                ConvVaeTrainer(batch_size=4, image=28, z=z, backend=backend, device="cpu")
+    for z in (8, 24, np.int64(128)):
+        tr = ConvVaeTrainer(batch_size=4, image=28, z=z, backend="torch", device="cpu", seed=0)
+        assert tr.Z == z and tr.named_parameters()["dec_fc.weight"].shape[-1] == z
+
+
 def test_merged_tail_finalizes_every_28x28_layer_once():
     # MDT_F28_FIN_MERGE's job table (ConvVaeTrainer._merged_pack28) has one
     # finalize job per layer of the 28x28 model, released by that layer's
