@@ -2,6 +2,9 @@
 
 Inputs are rounded to bf16 first (the kernels' operand precision), so the
 references differ from the kernels only by f32 summation order.
+These shapes reach tile configurations F6, F7, W0, W1 and W5 only; every
+configuration, element by element under a derived bound, is in
+tests/gpu/test_conv_igemm_tiles.py.
 """
 import pytest
 import torch
