@@ -44,7 +44,8 @@ PYBIND11_MODULE(_C, m) {
       .def("set_hparams", &mdt::TrialStateBuf::set_hparams, py::arg("lr"), py::arg("beta1"), py::arg("beta2"),
            py::arg("eps"), py::arg("weight_decay"), py::arg("kl_beta"), py::arg("grad_scale"), py::arg("seed"),
            py::arg("decoupled_wd"), py::arg("lr_warmup_steps") = 0, py::arg("lr_decay") = 0,
-           py::arg("lr_decay_steps") = 0, py::arg("lr_min_ratio") = 0.0, py::arg("kl_anneal_steps") = 0)
+           py::arg("lr_decay_steps") = 0, py::arg("lr_min_ratio") = 0.0, py::arg("kl_anneal_steps") = 0,
+           py::arg("free_bits") = 0.0)
       .def("set_cursor", &mdt::TrialStateBuf::set_cursor)
       .def("set_step", &mdt::TrialStateBuf::set_step)
       .def("reset_loss", &mdt::TrialStateBuf::reset_loss)

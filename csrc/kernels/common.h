@@ -76,6 +76,46 @@ __device__ __forceinline__ float normal_from_bits(uint32_t a, uint32_t b) {
   return sqrtf(-2.0f * logf(u1)) * cosf(6.283185307179586f * u2);
 }
 
+// ---------------------------------------------------------------------------
+// Free bits (Kingma et al. 2016), the per-sample, per-dimension form: the
+// training objective is BCE + beta * sum_x sum_d max(fb, kl_d(x)) with
+// kl_d = 0.5 (mu^2 + e^lv - 1 - lv) and the floor fb >= 0 in nats
+// (TrainState.fb_t; 0 in eval states). Every site hands both helpers the SAME
+// float `sum` = 1 + lv - mu^2 - sd^2 = -2 kl_d: kl_sum_fma in the fused 28x28
+// kernels, kl_sum_plain elsewhere -- each a pinned rounding sequence, so a
+// forward and its backward (other kernels, other launches) cannot disagree on
+// an element. fb = 0 clamps nothing, not even a sum that rounded to a tiny
+// positive (kl_d < 0): outputs are then bit for bit those without the floor.
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ float kl_sum_fma(float mu, float lv, float sd) {
+  return fmaf(-sd, sd, fmaf(-mu, mu, 1.f + lv));
+}
+__device__ __forceinline__ float kl_sum_plain(float mu, float lv, float sd) {
+#pragma clang fp contract(off)  // two products, two subtractions, wherever this is inlined
+  return 1.f + lv - mu * mu - sd * sd;
+}
+__device__ __forceinline__ bool fb_clamped(float sum, float fb) { return fb > 0.f && -0.5f * sum < fb; }
+// Forward: the element's term of the KLD sum (the caller's -0.5f * is exact,
+// so a clamped element contributes exactly fb).
+__device__ __forceinline__ float fb_fwd(float sum, float fb) { return fb_clamped(sum, fb) ? -2.f * fb : sum; }
+// Backward: the KL weight of the element's gradients, 0 where the forward
+// floored it (its KL part is then exactly zero: dmu = dz, dlv = 0.5 dz eps sd).
+__device__ __forceinline__ float fb_bwd(float sum, float fb, float beta) { return fb_clamped(sum, fb) ? 0.f : beta; }
+
+// d[mu] = dz + be mu and d[logvar] = 0.5 dz eps sd + 0.5 be (sd^2 - 1) of one
+// latent element (be: fb_bwd), as explicit fmaf: the contractions the compiler
+// chose for these expressions before the floor existed, spelled out so that
+// the select feeding them (or anything else around them) cannot change how
+// they round. kl_dlv_sum is the one site that contracted the other product
+// (combine_reparam_bwd_rows_body).
+__device__ __forceinline__ float kl_dmu(float dz, float be, float mu) { return fmaf(be, mu, dz); }
+__device__ __forceinline__ float kl_dlv(float dz, float ep, float sd, float be) {
+  return fmaf(sd, 0.5f * dz * ep, 0.5f * be * fmaf(sd, sd, -1.f));
+}
+__device__ __forceinline__ float kl_dlv_sum(float dz, float ep, float sd, float be) {
+  return fmaf(0.5f * be, fmaf(sd, sd, -1.f), 0.5f * dz * ep * sd);
+}
+
 // Write-through stores for a kernel's large outputs that the NEXT launch
 // reads. Plain stores leave their lines dirty in the XCD's L2 until the
 // end-of-kernel release writes them back -- a tail of ~bytes / 6 TB/s after

@@ -98,6 +98,8 @@ struct BwdArgs {
   // KL weight of the step being computed: TrainState.kl_next when the step is
   // advanced after this launch (t = step + 1), HParams.kl_beta with no state
   const float* klw;
+  // ... and its free-bits floor: TrainState.fb_t (0 in an eval state), HParams.free_bits with no state
+  const float* fbw;
   const float* mulv;
   const float* eps;
   const __bf16* a1;
@@ -639,13 +641,15 @@ __device__ __forceinline__ void fwd_rest(const FwdArgs& a, uint8_t* lds, int n) 
       const int c = tid;
       const float mu = Hs[c], lv = Hs[32 + c];
       const unsigned long long stp = (unsigned long long)a.st->step;
+      const float fb = a.st->fb_t;  // the free-bits floor, with the step's load
       const u32x4 bits = philox4x32_10(u32x4{(uint32_t)(n * 32 + c), a.stream, (uint32_t)(stp & 0xffffffffu),
                                              (uint32_t)(stp >> 32)},
                                        a.hp->seed_lo, a.hp->seed_hi);
       const float ep = normal_from_bits(bits.x, bits.y);
       const float sd = expf(0.5f * lv);
       const float zz = fmaf(ep, sd, mu);
-      kl = fmaf(-sd, sd, fmaf(-mu, mu, 1.f + lv));  // explicit: one rounding sequence in both bodies
+      // explicit: one rounding sequence in both bodies and in Q4 (free bits, common.h)
+      kl = fb_fwd(kl_sum_fma(mu, lv, sd), fb);
       Zs[c] = (__bf16)zz;
       reinterpret_cast<float*>(lds + L::Red)[c] = ep;  // the merged step's Q4 (Red is free after P3)
       if (a.train) {
@@ -985,15 +989,17 @@ __device__ __forceinline__ void bwd_body(const BwdArgs& a, uint8_t* lds, int n) 
 #pragma unroll
     for (int i = 0; i < 8; ++i) dz1 += DZR[256 + i * 32 + c];
     const float dz = dz0 + dz1;  // the paired step's (role-0 part + role-1 part)
-    const float beta = *a.klw;
+    const float beta = *a.klw, fb = *a.fbw;
     // merged step: mu | logvar and eps from the forward's LDS (H, Red); else from memory
     const float* Hm = reinterpret_cast<const float*>(lds + L::H);
     const float mu = MERGED ? Hm[c] : a.mulv[(size_t)n * 64 + c];
     const float lv = MERGED ? Hm[32 + c] : a.mulv[(size_t)n * 64 + 32 + c];
     const float ep = MERGED ? reinterpret_cast<const float*>(lds + L::Red)[c] : a.eps[(size_t)n * 32 + c];
     const float sd = expf(0.5f * lv);
-    const float dm = dz + beta * mu;
-    const float dl = 0.5f * dz * ep * sd + 0.5f * beta * (sd * sd - 1.f);
+    const float ks = kl_sum_fma(mu, lv, sd);  // as P4 formed it
+    const float be = fb_bwd(ks, fb, beta);
+    const float dm = kl_dmu(dz, be, mu);
+    const float dl = kl_dlv(dz, ep, sd, be);
     DMs[c] = dm;
     DMs[32 + c] = dl;
     a.dmulv[(size_t)n * 64 + c] = dm;

@@ -144,6 +144,7 @@ void fill_fwd(f28::FwdArgs& a, const long long* p, int B, unsigned stream, int t
 void fill_bwd(f28::BwdArgs& a, const long long* p, int M, const TrainState* st) {
   fill_weights(a.w, p);
   a.klw = st ? &st->kl_next : &P<const HParams>(p, 12)->kl_beta;  // device addresses, not dereferenced here
+  a.fbw = st ? &st->fb_t : &P<const HParams>(p, 12)->free_bits;
   a.mulv = P<const float>(p, 13);
   a.eps = P<const float>(p, 14);
   a.a1 = P<const __bf16>(p, 15);

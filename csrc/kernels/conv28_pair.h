@@ -461,7 +461,10 @@ __device__ __forceinline__ void pair_rest(uint8_t* lds, int n, int r) {
     if (tid < 32) {
       const int c = tid;
       // eps first: it needs nothing from the partner, so it overlaps the X1 wait
-      const unsigned long long stp = (unsigned long long)tab<L, const TrainState>(lds, kTSt)->step;
+      // (so does the load of the free-bits floor, issued with the step's)
+      const TrainState* stt = tab<L, const TrainState>(lds, kTSt);
+      const unsigned long long stp = (unsigned long long)stt->step;
+      const float fb = stt->fb_t;
       const HParams* hp = tab<L, const HParams>(lds, kTHp);
       const u32x4 bits = philox4x32_10(u32x4{(uint32_t)(n * 32 + c), stream, (uint32_t)(stp & 0xffffffffu),
                                              (uint32_t)(stp >> 32)},
@@ -477,7 +480,8 @@ __device__ __forceinline__ void pair_rest(uint8_t* lds, int n, int r) {
       Hs[32 + c] = lv;
       const float sd = expf(0.5f * lv);
       const float zz = fmaf(ep, sd, mu);
-      kl = fmaf(-sd, sd, fmaf(-mu, mu, 1.f + lv));  // explicit: one rounding sequence in both bodies
+      // explicit: one rounding sequence in both bodies and in Q4 (free bits, common.h)
+      kl = fb_fwd(kl_sum_fma(mu, lv, sd), fb);
       Zs[c] = (__bf16)zz;
       Eps[c] = ep;
       if (train && r == 0) {
@@ -791,11 +795,13 @@ __device__ __forceinline__ void pair_rest(uint8_t* lds, int n, int r) {
     xget<1>(xi, gi, tg + 5, pv, err, near);
     const float dz = r ? bitsf(pv[0]) + mine : mine + bitsf(pv[0]);
     // the KL weight of the step being computed (t = step + 1: the step is advanced by a later launch)
-    const float beta = tab<L, const TrainState>(lds, kTSt)->kl_next;
+    const float beta = tab<L, const TrainState>(lds, kTSt)->kl_next, fb = tab<L, const TrainState>(lds, kTSt)->fb_t;
     const float mu = Hs[c], lv = Hs[32 + c], ep = Eps[c];
     const float sd = expf(0.5f * lv);
-    const float dm = dz + beta * mu;
-    const float dl = 0.5f * dz * ep * sd + 0.5f * beta * (sd * sd - 1.f);
+    const float ks = kl_sum_fma(mu, lv, sd);  // as X1 + P4 formed it
+    const float be = fb_bwd(ks, fb, beta);
+    const float dm = kl_dmu(dz, be, mu);
+    const float dl = kl_dlv(dz, ep, sd, be);
     DMs[c] = dm;
     DMs[32 + c] = dl;
     if (r == 0) {

@@ -25,6 +25,7 @@ __global__ void __launch_bounds__(256) reparam_k(const float* mulv, float* eps, 
     const int i = e / Z, c = e - i * Z;
     const float mu = mulv[(size_t)i * 2 * Z + c], lv = mulv[(size_t)i * 2 * Z + Z + c];
     const long long stp = st->step - 1;
+    const float fb = st->fb_t;  // the free-bits floor, with the step's load
     const u32x4 bits = philox4x32_10(u32x4{(uint32_t)(i * Z + c), stream, (uint32_t)((unsigned long long)stp & 0xffffffffu),
                                            (uint32_t)((unsigned long long)stp >> 32)},
                                      hp->seed_lo, hp->seed_hi);
@@ -34,7 +35,7 @@ __global__ void __launch_bounds__(256) reparam_k(const float* mulv, float* eps, 
     eps[e] = ep;
     z16[e] = (__bf16)zz;
     if (z32) z32[e] = zz;
-    kl = 1.f + lv - mu * mu - sd * sd;
+    kl = fb_fwd(kl_sum_plain(mu, lv, sd), fb);
   }
   const float s = block_sum(kl, scratch);
   if (threadIdx.x == 0) kld_part[blockIdx.x] = -0.5f * s;
@@ -42,16 +43,20 @@ __global__ void __launch_bounds__(256) reparam_k(const float* mulv, float* eps, 
 
 // dz (f32 [B, Z], from the decoder Linear's backward-data) -> d[mu|lv].
 __global__ void __launch_bounds__(256) reparam_bwd_k(const float* dz, const float* mulv, const float* eps,
-                                                     float* dmulv, __bf16* dmulv16, int B, int Z, const float* klw) {
+                                                     float* dmulv, __bf16* dmulv16, int B, int Z, const float* klw,
+                                                     const float* fbw) {
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= B * Z) return;
   const int i = e / Z, c = e - i * Z;
   const float beta = *klw;  // TrainState.kl_t of the running step (or HParams.kl_beta)
+  const float fb = *fbw;    // TrainState.fb_t (or HParams.free_bits)
   const float mu = mulv[(size_t)i * 2 * Z + c], lv = mulv[(size_t)i * 2 * Z + Z + c];
   const float sd = expf(0.5f * lv);
   const float g = dz[e];
-  const float dm = g + beta * mu;
-  const float dl = 0.5f * g * eps[e] * sd + 0.5f * beta * (sd * sd - 1.f);
+  const float ks = kl_sum_plain(mu, lv, sd);  // as reparam_k formed it
+  const float be = fb_bwd(ks, fb, beta);
+  const float dm = kl_dmu(g, be, mu);
+  const float dl = kl_dlv(g, eps[e], sd, be);
   dmulv[(size_t)i * 2 * Z + c] = dm;
   dmulv[(size_t)i * 2 * Z + Z + c] = dl;
   if (dmulv16) {
@@ -206,9 +211,9 @@ int mdt_reparam(const float* mulv, float* eps, void* z16, float* z32, int B, int
 }
 
 int mdt_reparam_bwd(const float* dz, const float* mulv, const float* eps, float* dmulv, void* dmulv16, int B, int Z,
-                    const float* klw, hipStream_t s) {
+                    const float* klw, const float* fbw, hipStream_t s) {
   hipLaunchKernelGGL(reparam_bwd_k, dim3(cdivh((long long)B * Z, 256)), dim3(256), 0, s, dz, mulv, eps, dmulv,
-                     reinterpret_cast<__bf16*>(dmulv16), B, Z, klw);
+                     reinterpret_cast<__bf16*>(dmulv16), B, Z, klw, fbw);
   return (int)hipGetLastError();
 }
 
@@ -295,9 +300,10 @@ int mdt_combine_reparam(const float* slab, int ks, const float* bias, float* mul
 }
 
 int mdt_combine_reparam_bwd(const float* slab, int ks, const float* mulv, const float* eps, float* dmulv,
-                            void* dmulv16, float* dz, int B, int Z, const float* klw, hipStream_t s) {
+                            void* dmulv16, float* dz, int B, int Z, const float* klw, const float* fbw,
+                            hipStream_t s) {
   const CombineReparamBwdArgs a{slab, ks, splitk_rp(ks), mulv, eps, dmulv, reinterpret_cast<__bf16*>(dmulv16), dz, B,
-                                Z, klw};
+                                Z, klw, fbw};
   hipLaunchKernelGGL(combine_reparam_bwd_k, dim3(combine_reparam_blocks(ks, B, Z)), dim3(256), 0, s, a);
   return (int)hipGetLastError();
 }

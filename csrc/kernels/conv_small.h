@@ -150,6 +150,7 @@ __device__ __forceinline__ void combine_reparam_rows_body(const CombineReparamAr
   // the step, seeds and bias before the slab sum: loaded after it they were a
   // second dependent round trip at the kernel's end
   const long long stp = a.st->step - 1;
+  const float fb = a.st->fb_t;  // the free-bits floor (common.h)
   const uint32_t seed_lo = a.hp->seed_lo, seed_hi = a.hp->seed_hi;
   float bm = 0.f, bl = 0.f;
   if (own && a.bias) {
@@ -175,7 +176,7 @@ __device__ __forceinline__ void combine_reparam_rows_body(const CombineReparamAr
     ep = normal_from_bits(bits.x, bits.y);
     const float sd = expf(0.5f * lv);
     zz = mu + ep * sd;
-    kl = 1.f + lv - mu * mu - sd * sd;
+    kl = fb_fwd(kl_sum_plain(mu, lv, sd), fb);
   }
   // the KLD block sum before the stores (see below)
   const float s = block_sum(kl, red + 1024);
@@ -219,13 +220,14 @@ __device__ __forceinline__ void combine_reparam_body(const CombineReparamArgs& a
       lv += a.bias[a.Z + c];
     }
     const long long stp = a.st->step - 1;
+    const float fb = a.st->fb_t;  // the free-bits floor, with the step's load
     const u32x4 bits = philox4x32_10(u32x4{(uint32_t)(i * a.Z + c), a.stream, (uint32_t)((unsigned long long)stp & 0xffffffffu),
                                            (uint32_t)((unsigned long long)stp >> 32)},
                                      a.hp->seed_lo, a.hp->seed_hi);
     ep = normal_from_bits(bits.x, bits.y);
     const float sd = expf(0.5f * lv);
     zz = mu + ep * sd;
-    kl = 1.f + lv - mu * mu - sd * sd;
+    kl = fb_fwd(kl_sum_plain(mu, lv, sd), fb);
   }
   // the KLD block sum before the stores: its barriers would otherwise wait
   // for their acknowledgements (vmcnt counts stores on CDNA)
@@ -251,6 +253,7 @@ struct CombineReparamBwdArgs {
   float* dz;
   int B, Z;
   const float* klw;  // the step's KL weight: TrainState.kl_t (or HParams.kl_beta: no schedule)
+  const float* fbw;  // the step's free-bits floor: TrainState.fb_t (or HParams.free_bits)
 };
 
 // `red` >= 1024 floats (16-B aligned)
@@ -259,7 +262,7 @@ __device__ __forceinline__ void combine_reparam_bwd_rows_body(const CombineRepar
   // this lane's mu / logvar / eps and beta before the slab sum (one round trip
   // fewer at the kernel's end)
   const int c = t < Z ? t : 0, e = i * Z + c;
-  const float beta = *a.klw;
+  const float beta = *a.klw, fb = *a.fbw;
   const float mu = a.mulv[(size_t)i * 2 * Z + c], lv = a.mulv[(size_t)i * 2 * Z + Z + c], ee = a.eps[e];
   combine_rows_partial(a.slab, a.ks, (long long)a.B * Z, (long long)i * Z, Z, red);
   __syncthreads();
@@ -268,8 +271,10 @@ __device__ __forceinline__ void combine_reparam_bwd_rows_body(const CombineRepar
   for (int r = 0; r < RG; ++r) g += red[r * Z + c];
   if (a.dz) a.dz[e] = g;
   const float sd = expf(0.5f * lv);
-  const float dm = g + beta * mu;
-  const float dl = 0.5f * g * ee * sd + 0.5f * beta * (sd * sd - 1.f);
+  const float ks = kl_sum_plain(mu, lv, sd);  // as the forward body formed it
+  const float be = fb_bwd(ks, fb, beta);
+  const float dm = kl_dmu(g, be, mu);
+  const float dl = kl_dlv_sum(g, ee, sd, be);
   a.dmulv[(size_t)i * 2 * Z + c] = dm;
   a.dmulv[(size_t)i * 2 * Z + Z + c] = dl;
   if (a.dmulv16) {
@@ -294,11 +299,13 @@ __device__ __forceinline__ void combine_reparam_bwd_body(const CombineReparamBwd
   for (int r = 0; r < a.rp; ++r) g += red[r * cnt + col];
   const int i = e / a.Z, c = e - i * a.Z;
   if (a.dz) a.dz[e] = g;
-  const float beta = *a.klw;
+  const float beta = *a.klw, fb = *a.fbw;
   const float mu = a.mulv[(size_t)i * 2 * a.Z + c], lv = a.mulv[(size_t)i * 2 * a.Z + a.Z + c];
   const float sd = expf(0.5f * lv);
-  const float dm = g + beta * mu;
-  const float dl = 0.5f * g * a.eps[e] * sd + 0.5f * beta * (sd * sd - 1.f);
+  const float ks = kl_sum_plain(mu, lv, sd);  // as the forward body formed it
+  const float be = fb_bwd(ks, fb, beta);
+  const float dm = kl_dmu(g, be, mu);
+  const float dl = kl_dlv(g, a.eps[e], sd, be);
   a.dmulv[(size_t)i * 2 * a.Z + c] = dm;
   a.dmulv[(size_t)i * 2 * a.Z + a.Z + c] = dl;
   if (a.dmulv16) {

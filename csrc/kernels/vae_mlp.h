@@ -38,7 +38,8 @@ struct TrainState {
   float kl_next;       // ... of step `step + 1`: for the fused 28x28 forward/backward, which run
                        // BEFORE their step is advanced (no block of that launch writes it)
   int32_t sched_off;   // 1: factors are 1 whatever the step (eval states: eval uses the full beta)
-  int32_t pad_;
+  float fb_t;          // effective free-bits floor (nats per latent element) of the step: HParams.free_bits,
+                       // 0 in eval states (eval reports the true KL, as it uses the full beta)
   float loss_hist[kLossHist];
 };
 
@@ -57,6 +58,8 @@ struct HParams {
   int32_t lr_decay;               // 0 none, 1 cosine
   int32_t lr_decay_steps;         // T: total steps including warm-up (cosine: T > W)
   int32_t kl_anneal;              // A: KL weight ramps linearly over the first A steps
+  // free bits: per-sample, per-dimension KL floor in nats (0 = off, see fb_fwd / fb_bwd in common.h)
+  float free_bits;
 };
 
 constexpr int kLrDecayNone = 0, kLrDecayCosine = 1;
@@ -89,6 +92,7 @@ __host__ __device__ inline void sched_store(TrainState* st, const HParams& hp, l
   st->lr_t = hp.lr_d * (on ? sched_lr_factor(hp, t) : 1.0);
   st->kl_t = (float)(hp.kl_beta_d * (on ? sched_kl_factor(hp, t) : 1.0));
   st->kl_next = (float)(hp.kl_beta_d * (on ? sched_kl_factor(hp, t + 1) : 1.0));
+  st->fb_t = on ? hp.free_bits : 0.f;  // no schedule: the same for every t
 }
 
 #ifdef __HIPCC__

@@ -202,6 +202,7 @@ __global__ void __launch_bounds__(kThreads) vae_f2(VaeArgs a) {
   __syncthreads();
   // phase 2: one (row, latent) element per thread (16*Z <= 512)
   const long long stp = a.st->step - 1;  // F1 of this step already incremented it
+  const float fb = a.st->fb_t;           // ... and recorded the step's free-bits floor (common.h)
   const uint32_t step_lo = (uint32_t)((unsigned long long)stp & 0xffffffffu);
   const uint32_t step_hi = (uint32_t)((unsigned long long)stp >> 32);
   const int e = threadIdx.x;
@@ -220,7 +221,7 @@ __global__ void __launch_bounds__(kThreads) vae_f2(VaeArgs a) {
                                      a.hp->seed_lo, a.hp->seed_hi);
     ep = normal_from_bits(bits.x, bits.y);
     zz = valid ? mu + ep * sd : 0.f;
-    kld = valid ? 1.f + lv - mu * mu - sd * sd : 0.f;
+    kld = valid ? fb_fwd(kl_sum_plain(mu, lv, sd), fb) : 0.f;
     zt[r][c] = zz;
   }
   kld = wave_sum(kld);
@@ -547,6 +548,7 @@ __global__ void __launch_bounds__(kThreads) vae_b2(VaeArgs a, int nrow, int nw3,
   __syncthreads();
   STAMP(4, 1);
   const float beta = a.st->kl_t;  // the step's KL weight, written by F1 (an earlier launch)
+  const float fb = a.st->fb_t;    // ... and its free-bits floor
   float dmu = 0.f, dlv = 0.f;
   if (mine) {
     float dz = 0.f;
@@ -555,8 +557,11 @@ __global__ void __launch_bounds__(kThreads) vae_b2(VaeArgs a, int nrow, int nw3,
     if (valid) {
       const float sd = expf(0.5f * lv);
       // L = BCE + beta * (-0.5 sum(1 + lv - mu^2 - e^lv)), z = mu + eps*sd
-      dmu = dz + beta * mu;
-      dlv = 0.5f * dz * ep * sd + 0.5f * beta * (sd * sd - 1.f);
+      // (free bits: no KL part for an element F2 floored, same sum term as there)
+      const float ks = kl_sum_plain(mu, lv, sd);
+      const float be = fb_bwd(ks, fb, beta);
+      dmu = kl_dmu(dz, be, mu);
+      dlv = kl_dlv(dz, ep, sd, be);
     }
     dml[r][c] = dmu;
     dml[r][a.Z + c] = dlv;

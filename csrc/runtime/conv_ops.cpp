@@ -27,7 +27,7 @@ int mdt_gather_rows(const float* X, const int* idx, const void* st, int B, int M
 int mdt_reparam(const float* mulv, float* eps, void* z16, float* z32, int B, int Z, const void* st, const void* hp,
                 unsigned stream, float* kld_part, hipStream_t s);
 int mdt_reparam_bwd(const float* dz, const float* mulv, const float* eps, float* dmulv, void* dmulv16, int B, int Z,
-                    const float* klw, hipStream_t s);
+                    const float* klw, const float* fbw, hipStream_t s);
 int mdt_bce_logits(const float* logits, const float* X, const int* rows, int B, int P, void* dlog16, float* recon,
                    float* part, float* gpart, hipStream_t s);
 int mdt_conv_loss_finalize(const float* bce_part, int nb, const float* kld_part, int nk, void* st, const void* hp,
@@ -61,7 +61,8 @@ int mdt_combine_reparam(const float* slab, int ks, const float* bias, float* mul
                         int B, int Z, const void* st, const void* hp, unsigned stream, float* kld_part, hipStream_t s);
 int mdt_combine_reparam_blocks(int ks, int B, int Z);
 int mdt_combine_reparam_bwd(const float* slab, int ks, const float* mulv, const float* eps, float* dmulv,
-                            void* dmulv16, float* dz, int B, int Z, const float* klw, hipStream_t s);
+                            void* dmulv16, float* dz, int B, int Z, const float* klw, const float* fbw,
+                            hipStream_t s);
 int mdt_job_wgrad(mdt::JobBlob* j, const void* G16, const void* X, int x_is_f32, mdt::ConvDesc d, float* out);
 int mdt_job_thin_conv(mdt::JobBlob* j, const void* X, int x_is_f32, const float* Wf, mdt::ConvDesc d,
                       const float* bias, int relu, void* y16, const void* omask, float* colsum, const int* idx,
@@ -350,6 +351,15 @@ const float* kl_weight_ptr(const at::Tensor& hparams, const c10::optional<at::Te
   return reinterpret_cast<const float*>(static_cast<const char*>(hparams.data_ptr()) + offsetof(HParams, kl_beta));
 }
 
+// ... and of its free-bits floor: TrainState.fb_t (0 in an eval state) or, with
+// no state, HParams.free_bits. Only address arithmetic: kl_weight_ptr, called
+// for the same launch, validates both buffers before anything runs.
+const float* free_bits_ptr(const at::Tensor& hparams, const c10::optional<at::Tensor>& state) {
+  if (state.has_value() && state->defined())
+    return reinterpret_cast<const float*>(static_cast<const char*>(state->data_ptr()) + offsetof(TrainState, fb_t));
+  return reinterpret_cast<const float*>(static_cast<const char*>(hparams.data_ptr()) + offsetof(HParams, free_bits));
+}
+
 void reparam_bwd(const at::Tensor& dz, const at::Tensor& mulv, const at::Tensor& eps, at::Tensor dmulv,
                  const c10::optional<at::Tensor>& dmulv16, int64_t B, int64_t Z, const at::Tensor& hparams,
                  const c10::optional<at::Tensor>& state) {
@@ -360,7 +370,8 @@ void reparam_bwd(const at::Tensor& dz, const at::Tensor& mulv, const at::Tensor&
   check_buf(dmulv, torch::kFloat32, B * 2 * Z, dz, "reparam_bwd", "dmulv");
   check_buf(dmulv16, torch::kBFloat16, B * 2 * Z, dz, "reparam_bwd", "dmulv16");
   rc(mdt_reparam_bwd(dz.data_ptr<float>(), mulv.data_ptr<float>(), eps.data_ptr<float>(), dmulv.data_ptr<float>(),
-                     const_cast<void*>(opt_ptr(dmulv16)), (int)B, (int)Z, kl_weight_ptr(hparams, state), cur()),
+                     const_cast<void*>(opt_ptr(dmulv16)), (int)B, (int)Z, kl_weight_ptr(hparams, state),
+                     free_bits_ptr(hparams, state), cur()),
      "reparam_bwd");
 }
 
@@ -841,7 +852,7 @@ void combine_reparam_bwd(const at::Tensor& ws, int64_t ks, const at::Tensor& mul
   check_buf(dz, torch::kFloat32, B * Z, ws, "combine_reparam_bwd", "dz");
   rc(mdt_combine_reparam_bwd(ws.data_ptr<float>(), (int)ks, mulv.data_ptr<float>(), eps.data_ptr<float>(),
                              dmulv.data_ptr<float>(), const_cast<void*>(opt_ptr(dmulv16)), (float*)opt_ptr(dz), (int)B,
-                             (int)Z, kl_weight_ptr(hparams, state), cur()),
+                             (int)Z, kl_weight_ptr(hparams, state), free_bits_ptr(hparams, state), cur()),
      "combine_reparam_bwd");
 }
 

@@ -67,17 +67,20 @@ class MlpCpuStep {
     dmulv_ = torch::empty({B, 2 * Z}, f);
     dh1_ = torch::empty({B, H}, f);
     b2_ = torch::empty({2 * Z}, f);
+    floored_ = torch::zeros({B, Z}, torch::kUInt8);
   }
 
   // Forward + loss + backward of M rows X[idx[row0 + i]]; gradients into the
-  // arena views. Returns the loss (BCE sum + beta * KLD).
+  // arena views. Returns the loss (BCE sum + beta * KLD). free_bits: the per-sample,
+  // per-dimension KL floor of kernels/common.h (fb_fwd / fb_bwd), 0 = none.
   double forward_backward(const std::vector<at::Tensor>& w, std::vector<at::Tensor> g, const at::Tensor& X,
                           const at::Tensor& idx, int64_t row0, int64_t M, int64_t seed, int64_t stream, int64_t step,
-                          double beta, bool backward) {
+                          double beta, bool backward, double free_bits) {
     TORCH_CHECK(w.size() == 10 && g.size() == 10, "weights/grads: fc1.w fc1.b fc21.w fc21.b fc22.w fc22.b fc3.w fc3.b fc4.w fc4.b");
     TORCH_CHECK(M >= 1 && M <= B_ && X.dim() == 2 && X.size(1) == D_ && X.scalar_type() == torch::kFloat32 &&
                 X.is_contiguous() && idx.scalar_type() == torch::kInt32 && row0 >= 0 && row0 + M <= idx.numel(),
                 "MlpCpuStep: bad batch");
+    TORCH_CHECK_VALUE(std::isfinite(free_bits) && free_bits >= 0.0, "free_bits must be finite and >= 0, got ", free_bits);
     const int64_t D = D_, H = H_, Z = Z_;
     auto x = x_.narrow(0, 0, M), h1 = h1_.narrow(0, 0, M), mulv = mulv_.narrow(0, 0, M), z = z_.narrow(0, 0, M);
     auto h3 = h3_.narrow(0, 0, M), t = t_.narrow(0, 0, M), dh3 = dh3_.narrow(0, 0, M), dz = dz_.narrow(0, 0, M);
@@ -106,6 +109,8 @@ class MlpCpuStep {
     const uint32_t slo = (uint32_t)((uint64_t)step & 0xffffffffu), shi = (uint32_t)((uint64_t)step >> 32);
     const uint32_t k0 = (uint32_t)((uint64_t)seed & 0xffffffffu), k1 = (uint32_t)((uint64_t)seed >> 32);
     double kld = 0.0;
+    const float flo = (float)free_bits;
+    uint8_t* fl = floored_.data_ptr<uint8_t>();  // the backward reads the forward's decision, not a recomputed one
     for (int64_t i = 0; i < M; ++i) {
       for (int64_t c = 0; c < Z; ++c) {
         const Ph r = philox10(Ph{(uint32_t)(i * Z + c), (uint32_t)stream, slo, shi}, k0, k1);
@@ -114,7 +119,10 @@ class MlpCpuStep {
         const float sd = std::exp(0.5f * lv);
         ep[i * Z + c] = e;
         zp[i * Z + c] = mu + e * sd;
-        kld += (double)(1.f + lv - mu * mu - sd * sd);
+        const float s = 1.f + lv - mu * mu - sd * sd;
+        const bool floored = flo > 0.f && -0.5f * s < flo;
+        fl[i * Z + c] = floored;
+        kld += (double)(floored ? -2.f * flo : s);
       }
     }
     kld *= -0.5;
@@ -149,8 +157,9 @@ class MlpCpuStep {
       for (int64_t c = 0; c < Z; ++c) {
         const float mu = mv[i * 2 * Z + c], sd = std::exp(0.5f * mv[i * 2 * Z + Z + c]);
         const float d = dzp[i * Z + c];
-        dm[i * 2 * Z + c] = d + fb * mu;
-        dm[i * 2 * Z + Z + c] = 0.5f * d * ep[i * Z + c] * sd + 0.5f * fb * (sd * sd - 1.f);
+        const float be = fl[i * Z + c] ? 0.f : fb;  // a floored element has no KL gradient
+        dm[i * 2 * Z + c] = d + be * mu;
+        dm[i * 2 * Z + Z + c] = 0.5f * d * ep[i * Z + c] * sd + 0.5f * be * (sd * sd - 1.f);
       }
     }
     at::mm_out(G2, dmulv.t(), h1);
@@ -217,7 +226,7 @@ class MlpCpuStep {
   }
 
   int64_t B_, D_, H_, Z_, last_m_ = 0;
-  at::Tensor x_, h1_, mulv_, eps_, z_, h3_, t_, dh3_, dz_, dmulv_, dh1_, b2_;
+  at::Tensor x_, h1_, mulv_, eps_, z_, h3_, t_, dh3_, dz_, dmulv_, dh1_, b2_, floored_;
 };
 
 void bind_cpu(pybind11::module& m) {
@@ -226,7 +235,8 @@ void bind_cpu(pybind11::module& m) {
       .def(py::init<int64_t, int64_t, int64_t, int64_t>(), py::arg("B"), py::arg("D"), py::arg("H"), py::arg("Z"))
       .def("forward_backward", &MlpCpuStep::forward_backward, py::arg("weights"), py::arg("grads"), py::arg("X"),
            py::arg("idx"), py::arg("row0"), py::arg("M"), py::arg("seed"), py::arg("stream"), py::arg("step"),
-           py::arg("beta"), py::arg("backward") = true, py::call_guard<py::gil_scoped_release>())
+           py::arg("beta"), py::arg("backward") = true, py::arg("free_bits") = 0.0,
+           py::call_guard<py::gil_scoped_release>())
       .def("recon", &MlpCpuStep::recon)
       .def_static("adam", &MlpCpuStep::adam, py::arg("P"), py::arg("G"), py::arg("M"), py::arg("V"), py::arg("step"),
                   py::arg("lr"), py::arg("beta1"), py::arg("beta2"), py::arg("eps"), py::arg("weight_decay"),

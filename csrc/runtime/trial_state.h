@@ -62,7 +62,8 @@ class TrialStateBuf {
   }
   void set_hparams(double lr, double b1, double b2, double eps, double wd, double kl_beta, double gs, int64_t seed,
                    bool decoupled, int64_t lr_warmup = 0, int64_t lr_decay = 0, int64_t lr_decay_steps = 0,
-                   double lr_min_ratio = 0.0, int64_t kl_anneal = 0) {
+                   double lr_min_ratio = 0.0, int64_t kl_anneal = 0, double free_bits = 0.0) {
+    TORCH_CHECK_VALUE(std::isfinite(free_bits) && free_bits >= 0.0, "free_bits must be finite and >= 0, got ", free_bits);
     HParams h;
     std::memset(&h, 0, sizeof(h));
     h.lr = (float)lr; h.beta1 = (float)b1; h.beta2 = (float)b2; h.eps = (float)eps; h.weight_decay = (float)wd;
@@ -70,6 +71,7 @@ class TrialStateBuf {
     h.seed_lo = (uint32_t)((uint64_t)seed & 0xffffffffu); h.seed_hi = (uint32_t)((uint64_t)seed >> 32);
     h.lr_d = lr; h.beta1_d = b1; h.beta2_d = b2;
     sched_fill(h, kl_beta, lr_warmup, lr_decay, lr_decay_steps, lr_min_ratio, kl_anneal);
+    h.free_bits = (float)free_bits;
     hp_ = h;
     const bool changed = b1 != b1_ || b2 != b2_;
     b1_ = b1; b2_ = b2;
@@ -100,13 +102,14 @@ class TrialStateBuf {
     sched_seed(s, hp_, step, eval);
   }
   void reset_loss(bool eval) { (eval ? eval_state : train_state).narrow(0, offsetof(TrainState, epoch_loss), 16).zero_(); }
-  // step, cursor, nbatches, epoch_loss, epoch_count, lr, kl_beta
+  // step, cursor, nbatches, epoch_loss, epoch_count, lr, kl_beta, free_bits
   std::vector<double> read_state(bool eval) {
     auto cpu = (eval ? eval_state : train_state).narrow(0, 0, offsetof(TrainState, loss_hist)).to(torch::kCPU);
     TrainState h;
     std::memcpy(&h, cpu.data_ptr(), offsetof(TrainState, loss_hist));
-    // + the effective lr and KL weight of the last completed step (what its kernels used)
-    return {(double)h.step, (double)h.cursor, (double)h.nbatches, h.epoch_loss, h.epoch_count, h.lr_t, (double)h.kl_t};
+    // + the effective lr, KL weight and free-bits floor of the last completed step (what its kernels used)
+    return {(double)h.step, (double)h.cursor, (double)h.nbatches, h.epoch_loss, h.epoch_count, h.lr_t, (double)h.kl_t,
+            (double)h.fb_t};
   }
   at::Tensor loss_history(bool eval) {  // CPU float tensor [kLossHist]
     return (eval ? eval_state : train_state)

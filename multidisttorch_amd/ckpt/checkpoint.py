@@ -23,6 +23,9 @@ with ``torch.load(weights_only=True)`` (never unpickles code):
   data         {"binarize": none | threshold | static | dynamic}: the likelihood
                the trial trains under (data/binarize.py). ``load_latest`` returns
                it (absent = none); the runner refuses a resume under another one
+  objective    {"free_bits": the trainer's KL floor in nats per latent element}:
+               returned by ``load_latest`` (absent = 0) and checked by the runner
+               in the same way
 Only group rank 0 writes (replicas are identical after the all-reduce);
 writes go to a temp file + atomic rename so a crash never leaves a torn file.
 """
@@ -59,6 +62,7 @@ def save_trial(ckpt_dir: str, trainer, spec, epoch: int, extra: Optional[dict] =
         "layout": [[n, int(o)] + [int(x) for x in s] for n, o, s in trainer.layout],
         "arch": trainer.model_meta(),
         "data": {"binarize": str(binarize)},
+        "objective": {"free_bits": float(trainer.hp.get("free_bits", 0.0))},
     }
     if extra:
         payload["extra"] = extra
@@ -105,4 +109,5 @@ def load_latest(ckpt_dir: str, group_id: int, trainer) -> Optional[dict]:
 
         trainer.set_schedule(Schedule(**ck["schedule"]))
     trainer.load_optimizer_state(ck["optimizer"])  # sets the step: the schedule continues from it
-    return dict(ck["progress"], path=path, trial=ck["trial"], binarize=(ck.get("data") or {}).get("binarize", "none"))
+    return dict(ck["progress"], path=path, trial=ck["trial"], binarize=(ck.get("data") or {}).get("binarize", "none"),
+                free_bits=float((ck.get("objective") or {}).get("free_bits", 0.0)))

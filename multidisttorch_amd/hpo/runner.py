@@ -78,6 +78,7 @@ class RunOptions:
     latent_report: bool = False            # active units + MI / TC / dimension-wise-KL split after the last epoch
     au_threshold: float = 0.01             # a dimension is active when Var_x(mu_d) exceeds this
     binarize: str = "none"                 # none | threshold | static | dynamic (data/binarize.py); one value per run
+    report_free_bits: bool = False         # some trial of the run sets --free-bits: the metrics carry every trial's value
 
 
 @dataclass
@@ -128,14 +129,16 @@ def _make_trainer(spec: TrialSpec, opts: RunOptions, device, group_rank: int, D:
 
         return MlpVaeTrainer(batch_size=opts.batch_size, D=D, device=device, backend=opts.backend,
                              seed=spec.seed, lr=spec.lr, kl_beta=spec.beta, rng_stream=group_rank,
-                             use_graphs=opts.use_graphs, graph_steps=opts.graph_steps, schedule=sched)
+                             use_graphs=opts.use_graphs, graph_steps=opts.graph_steps, schedule=sched,
+                             free_bits=spec.free_bits)
     if opts.model == "conv":
         from ..models.conv_vae import ConvVaeTrainer
 
         return ConvVaeTrainer(batch_size=opts.batch_size, image=opts.image_size,
                               z=32 if opts.image_size == 28 else 64, device=device, backend=opts.backend,
                               seed=spec.seed, lr=spec.lr, kl_beta=spec.beta, rng_stream=group_rank,
-                              use_graphs=opts.use_graphs, graph_steps=opts.graph_steps, schedule=sched)
+                              use_graphs=opts.use_graphs, graph_steps=opts.graph_steps, schedule=sched,
+                              free_bits=spec.free_bits)
     raise ValueError(f"unknown model {opts.model!r}")
 
 
@@ -166,6 +169,14 @@ def _check_resumed_binarize(prog, opts: RunOptions, group_id: int):
     if prog is not None and prog.get("binarize", "none") != opts.binarize:
         raise ValueError(f"trial {group_id}: checkpoint {prog['path']} was trained with --binarize "
                          f"{prog.get('binarize', 'none')}, this run asks for --binarize {opts.binarize}")
+
+
+def _check_resumed_free_bits(prog, spec: TrialSpec):
+    """A resumed trial keeps the objective it was trained under (an old
+    checkpoint without the record was trained without a floor)."""
+    if prog is not None and float(prog.get("free_bits", 0.0)) != float(spec.free_bits):
+        raise ValueError(f"trial {spec.group_id}: checkpoint {prog['path']} was trained with --free-bits "
+                         f"{prog.get('free_bits', 0.0)}, this run asks for --free-bits {spec.free_bits}")
 
 
 def _refresh_train(binarizer, trainer, epoch: int, opts: RunOptions, device):
@@ -421,6 +432,11 @@ def _latent_eval(trainer, test, opts: RunOptions, group, metrics, device, tag: s
     r["latent_s"] = round(time.perf_counter() - t, 6)
     print0(tag + "====> Test set latent: KL {:.4f} active {}/{} MI {:.4f} TC {:.4f} DWKL {:.4f}".format(
         r["kl"], r["active_units"], len(r["kl_per_dim"]), r["mi"], r["tc"], r["dwkl"]), process_group=group)
+    fb = float(trainer.hp.get("free_bits", 0.0))
+    if fb > 0:
+        # dimensions the floor holds up: their test-set mean KL (the true one) is below it
+        r["free_bits"] = fb
+        r["below_floor"] = sum(1 for v in r["kl_per_dim"] if v < fb)
     metrics.log(event="latent_eval", **r)
     return dict(latent=r)
 
@@ -472,6 +488,7 @@ def run_trial(spec: TrialSpec, group, opts: RunOptions, data=None, num_trials: O
             try:
                 prog = ckpt.load_latest(opts.ckpt_dir, spec.group_id, trainer)
                 _check_resumed_binarize(prog, opts, spec.group_id)
+                _check_resumed_free_bits(prog, spec)
             except Exception as e:  # noqa: BLE001 - re-raised below on every member
                 err = e
         if prog is not None:
@@ -608,7 +625,8 @@ def _run_epoch(trainer, epoch, n_shard, train, test, opts, group, rdir, shape, g
     metrics.log(epoch=epoch, train_loss_sum=train_loss, train_loss=train_loss / len(train),
                 test_loss=test_loss, epoch_train_s=t_train, samples=n_shard,
                 train_samples_per_s=n_shard / max(t_train, 1e-9), lr=st["lr"], kl_beta=st["kl_beta"],
-                lr_base=spec.lr, beta=spec.beta, **phases)
+                lr_base=spec.lr, beta=spec.beta, **({"free_bits": st["free_bits"]} if opts.report_free_bits else {}),
+                **phases)
     return train_loss, test_loss
 
 
@@ -647,6 +665,7 @@ def run_packed_trials(specs, group, opts: RunOptions, data=None, num_trials: Opt
         if opts.ckpt_dir and opts.resume:
             prog = ckpt.load_latest(opts.ckpt_dir, spec.group_id, trainer)
             _check_resumed_binarize(prog, opts, spec.group_id)
+            _check_resumed_free_bits(prog, spec)
             if prog is not None:
                 start = prog["epoch"] + 1
         idx = shard_indices(len(train), total, spec.group_id)  # packing extension: one shard per trial

@@ -39,7 +39,7 @@ from torch import nn
 from ..hpo.schedule import Schedule
 from ..ops import native
 from .iw import iw_log_weights
-from .mlp_vae import reference_adam_
+from .mlp_vae import free_bits_floor, reference_adam_
 from .trainer_base import EVAL_STREAM, VaeTrainerBase
 
 __all__ = ["Layer", "conv_vae_spec", "TorchConvVAE", "ConvVaeTrainer", "conv_layout", "check_latent_size"]
@@ -173,12 +173,14 @@ class TorchConvVAE(nn.Module):
         t = self.decode_logits(zz)
         return t, mu, lv
 
-    def loss(self, x, eps, beta: float = 1.0):
+    def loss(self, x, eps, beta: float = 1.0, free_bits: float = 0.0):
         t, mu, lv = self.forward(x, eps)
         xt = x.view(x.shape[0], self.image, self.image, self.channels).permute(0, 3, 1, 2)
         sp_pos = torch.clamp(t, min=0) + torch.log1p(torch.exp(-t.abs()))
         bce = (xt * torch.clamp(sp_pos - t, max=100.0) + (1 - xt) * torch.clamp(sp_pos, max=100.0)).sum()
-        kld = -0.5 * torch.sum(1 + lv - mu.pow(2) - lv.exp())
+        # free bits: floored elements are constants of the objective (no KL gradient through them)
+        ksum, _ = free_bits_floor(1 + lv - mu.pow(2) - lv.exp(), free_bits)
+        kld = -0.5 * torch.sum(ksum)
         return bce + beta * kld, t, mu, lv
 
     # weight mapping between torch modules and the kernel arena layout
@@ -228,10 +230,10 @@ class ConvVaeTrainer(VaeTrainerBase):
                  backend: Optional[str] = None, seed: int = 0, lr: float = 1e-3, kl_beta: float = 1.0,
                  betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0, decoupled_wd: bool = False,
                  rng_stream: int = 0, use_graphs: bool = True, graph_steps: int = 10, init_seed: Optional[int] = None,
-                 schedule: Optional[Schedule] = None):
+                 schedule: Optional[Schedule] = None, free_bits: float = 0.0):
         z = check_latent_size(z)
         super().__init__(batch_size, device, backend, seed, rng_stream, lr, kl_beta, betas, eps, weight_decay,
-                         decoupled_wd, use_graphs, graph_steps, schedule)
+                         decoupled_wd, use_graphs, graph_steps, schedule, free_bits)
         backend = self.backend
         self.image, self.channels, self.Z = image, channels, z
         self.D = image * image * channels
@@ -1320,7 +1322,7 @@ class ConvVaeTrainer(VaeTrainerBase):
         x, eps = self._torch_batch(X, idx, st["cursor"], M, self.rng_stream, st["step"])
         self.model.zero_grad(set_to_none=True)
         lr_t, kl_t = self._effective(st["step"] + 1)
-        loss, *_ = self.model.loss(x, eps, kl_t)
+        loss, *_ = self.model.loss(x, eps, kl_t, self.hp["free_bits"])
         loss.backward()
         with torch.no_grad():
             gv = self.named_grads()

@@ -39,9 +39,10 @@ class MlpVaeTrainer(VaeTrainerBase):
                  device=None, backend: Optional[str] = None, seed: int = 0, init_seed: Optional[int] = None,
                  lr: float = 1e-3, kl_beta: float = 1.0, betas=(0.9, 0.999), eps: float = 1e-8,
                  weight_decay: float = 0.0, decoupled_wd: bool = False, rng_stream: int = 0,
-                 use_graphs: bool = True, graph_steps: int = 10, schedule: Optional[Schedule] = None):
+                 use_graphs: bool = True, graph_steps: int = 10, schedule: Optional[Schedule] = None,
+                 free_bits: float = 0.0):
         super().__init__(batch_size, device, backend, seed, rng_stream, lr, kl_beta, betas, eps, weight_decay,
-                         decoupled_wd, use_graphs, graph_steps, schedule)
+                         decoupled_wd, use_graphs, graph_steps, schedule, free_bits)
         self.D, self.H, self.Z = D, H, Z
         self.layout, self.numel, self.split = arena_layout(D, H, Z)
         if self.backend == "hip":
@@ -135,10 +136,11 @@ class MlpVaeTrainer(VaeTrainerBase):
         cpu = self._cpu_native()
         if cpu is not None:
             loss = cpu.forward_backward(self._cpu_w, self._cpu_g, X, idx, st["cursor"] * self.B, M, self.seed,
-                                        self.rng_stream, st["step"], kl_t)
+                                        self.rng_stream, st["step"], kl_t, free_bits=h["free_bits"])
         else:
             x, eps = self._torch_batch(X, idx, st["cursor"], M, self.rng_stream, st["step"])
-            f = reference_step(self.named_parameters(), self.named_grads(), x, eps, kl_t)
+            f = reference_step(self.named_parameters(), self.named_grads(), x, eps, kl_t,
+                               free_bits=h["free_bits"])
             loss = None
         if self.reducer is not None:
             self.reducer.launch(1)

@@ -118,7 +118,25 @@ def _relu(pre, mask):
     return torch.relu(pre) if mask is None else pre * mask.to(pre.dtype)
 
 
-def reference_forward(v, x, eps, beta: float = 1.0, masks=None):
+def free_bits_floor(ksum, free_bits: float):
+    """Free bits, per sample and per dimension (csrc/kernels/common.h: fb_fwd):
+    ``ksum`` = 1 + lv - mu^2 - sd^2 = -2 kl_d with the terms of floored
+    elements (kl_d < free_bits) replaced by -2 free_bits -> (ksum, mask of the
+    floored elements). ``free_bits == 0`` floors nothing: (ksum itself, None)."""
+    if not free_bits > 0:
+        return ksum, None
+    floored = -0.5 * ksum < free_bits
+    return torch.where(floored, torch.full_like(ksum, -2.0 * free_bits), ksum), floored
+
+
+def free_bits_beta(beta, floored, like):
+    """The KL weight of each latent element's gradient: 0 where the forward
+    floored it (common.h: fb_bwd), in the dtype of ``like``; plain ``beta``
+    without a floor."""
+    return beta if floored is None else torch.where(floored, torch.zeros_like(like), torch.full_like(like, beta))
+
+
+def reference_forward(v, x, eps, beta: float = 1.0, masks=None, free_bits: float = 0.0):
     """Forward + loss pieces exactly as kernels F1-F3 compute them.
 
     ``masks=(m1, m3)`` optionally pins the ReLU masks (tests: a pre-activation
@@ -136,14 +154,15 @@ def reference_forward(v, x, eps, beta: float = 1.0, masks=None):
     t = h3 @ W4.t() + b4
     p = torch.sigmoid(t)
     bce = _bce_terms(t, x).sum()
-    kld = -0.5 * (1 + lv - mu * mu - sd * sd).sum()
+    ksum, floored = free_bits_floor(1 + lv - mu * mu - sd * sd, free_bits)
+    kld = -0.5 * ksum.sum()
     return dict(h1=h1, mulv=mulv, mu=mu, lv=lv, sd=sd, z=z, h3=h3, t=t, p=p,
-                bce=bce, kld=kld, loss=bce + beta * kld)
+                bce=bce, kld=kld, loss=bce + beta * kld, floored=floored)
 
 
-def reference_step(v, g, x, eps, beta: float = 1.0, masks=None):
+def reference_step(v, g, x, eps, beta: float = 1.0, masks=None, free_bits: float = 0.0):
     """Explicit backward (kernels B1-B3) writing into grad views ``g``. Returns fwd dict."""
-    f = reference_forward(v, x, eps, beta, masks)
+    f = reference_forward(v, x, eps, beta, masks, free_bits)
     W1, b1, W2, b2, W3, b3, W4, b4 = _w(v)
     Z = W3.shape[1]
     dlog = f["p"] - x
@@ -153,8 +172,9 @@ def reference_step(v, g, x, eps, beta: float = 1.0, masks=None):
     g["fc3.weight"].copy_(dh3.t() @ f["z"])
     g["fc3.bias"].copy_(dh3.sum(0))
     dz = dh3 @ W3
-    dmu = dz + beta * f["mu"]
-    dlv = 0.5 * dz * eps * f["sd"] + 0.5 * beta * (f["sd"] * f["sd"] - 1)
+    be = free_bits_beta(beta, f["floored"], f["mu"])  # free bits: no KL part where the forward floored the element
+    dmu = dz + be * f["mu"]
+    dlv = 0.5 * dz * eps * f["sd"] + 0.5 * be * (f["sd"] * f["sd"] - 1)
     dmulv = torch.cat([dmu, dlv], 1)
     gW2 = dmulv.t() @ f["h1"]
     gb2 = dmulv.sum(0)

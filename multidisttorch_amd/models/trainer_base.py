@@ -17,6 +17,7 @@ A subclass sets ``B``, ``Z``, ``layout``, ``numel``, the arenas and (hip)
 
 from __future__ import annotations
 
+import math
 import os
 from typing import Dict, Optional
 
@@ -29,16 +30,24 @@ from ..ops.philox import reparam_eps
 from .eval_graphs import GraphedEval, GraphedIwEval, GraphedLatentEval, capture_replayable
 from .mlp_vae import views
 
-__all__ = ["VaeTrainerBase", "LOSS_HIST", "EVAL_STREAM"]
+__all__ = ["VaeTrainerBase", "LOSS_HIST", "EVAL_STREAM", "check_free_bits"]
 
 EVAL_STREAM = 1 << 30
 LOSS_HIST = 4096  # per-step loss ring of a trial state (kLossHist, csrc/kernels/vae_mlp.h)
 
 
+def check_free_bits(v) -> float:
+    """The free-bits floor in nats per latent element: finite and >= 0."""
+    v = float(v)
+    if not (math.isfinite(v) and v >= 0.0):
+        raise ValueError(f"free_bits must be finite and >= 0, got {v}")
+    return v
+
+
 class VaeTrainerBase(GraphedEval, GraphedIwEval, GraphedLatentEval):
     def __init__(self, batch_size: int, device, backend: Optional[str], seed: int, rng_stream: int, lr: float,
                  kl_beta: float, betas, eps: float, weight_decay: float, decoupled_wd: bool, use_graphs: bool,
-                 graph_steps: int, schedule: Optional[Schedule]):
+                 graph_steps: int, schedule: Optional[Schedule], free_bits: float = 0.0):
         self.B = batch_size
         # lr warm-up / cosine decay and KL annealing (hpo/schedule.py); None = off.
         # On the hip backend the kernels evaluate it from the device step counter.
@@ -52,7 +61,7 @@ class VaeTrainerBase(GraphedEval, GraphedIwEval, GraphedLatentEval):
         self.backend = backend
         self.seed, self.rng_stream = int(seed), int(rng_stream)
         self.hp = dict(lr=lr, beta1=betas[0], beta2=betas[1], eps=eps, weight_decay=weight_decay,
-                       kl_beta=kl_beta, grad_scale=1.0)
+                       kl_beta=kl_beta, grad_scale=1.0, free_bits=check_free_bits(free_bits))
         self.decoupled_wd = decoupled_wd
         self.use_graphs = use_graphs and backend == "hip"
         self.graph_steps = max(1, int(graph_steps))
@@ -112,7 +121,7 @@ class VaeTrainerBase(GraphedEval, GraphedIwEval, GraphedLatentEval):
         for k, v in kw.items():
             if k not in self.hp:
                 raise KeyError(k)
-            self.hp[k] = float(v)
+            self.hp[k] = check_free_bits(v) if k == "free_bits" else float(v)
         self._push_hparams()
 
     def set_schedule(self, schedule: Optional[Schedule]):
@@ -126,7 +135,7 @@ class VaeTrainerBase(GraphedEval, GraphedIwEval, GraphedLatentEval):
             h = self.hp
             self.state.set_hparams(h["lr"], h["beta1"], h["beta2"], h["eps"], h["weight_decay"], h["kl_beta"],
                                    h["grad_scale"], self.seed, self.decoupled_wd,
-                                   **(self.schedule or Schedule()).native_args())
+                                   **(self.schedule or Schedule()).native_args(), free_bits=h["free_bits"])
 
     def _effective(self, t: int):
         """(lr_t, beta_t) of optimizer step t on the torch backend, as doubles:
@@ -167,11 +176,13 @@ class VaeTrainerBase(GraphedEval, GraphedIwEval, GraphedLatentEval):
         if self.state is not None:
             s = self.state.read_state(eval)
             return dict(step=int(s[0]), cursor=int(s[1]), nbatches=int(s[2]), epoch_loss=s[3],
-                        epoch_count=s[4], lr=s[5], kl_beta=s[6])
-        # lr / kl_beta: the effective values of the last completed step (eval: always the full ones)
+                        epoch_count=s[4], lr=s[5], kl_beta=s[6], free_bits=s[7])
+        # lr / kl_beta / free_bits: the effective values of the last completed step (eval: always the
+        # full lr and beta, and no floor)
         st = dict(self._st_eval if eval else self._st)
         lr, kl = (self.hp["lr"], self.hp["kl_beta"]) if eval else self._effective(st["step"])
         st["lr"], st["kl_beta"] = float(lr), float(np.float32(kl))
+        st["free_bits"] = 0.0 if eval else float(np.float32(self.hp["free_bits"]))
         return st
 
     def loss_history(self, eval: bool = False) -> np.ndarray:

@@ -10,7 +10,8 @@ epochs). Launch one process per GPU with any launcher the reference supports
 Extensions (opt-in, default output unchanged): ``--lr`` / ``--beta`` (scalar or
 comma list, one per trial), the per-trial schedules ``--lr-warmup`` / ``--lr-decay``
 / ``--lr-decay-steps`` / ``--lr-min-ratio`` / ``--kl-anneal`` (same form;
-multidisttorch_amd/hpo/schedule.py), ``--seed``, ``--ckpt-dir`` + ``--resume``,
+multidisttorch_amd/hpo/schedule.py), ``--free-bits`` (same form: a KL floor in nats
+per sample and latent dimension, training only), ``--seed``, ``--ckpt-dir`` + ``--resume``,
 ``--metrics-dir`` (JSONL + aggregate samples/s), ``--per-group-results``, ``--bucket-mb``,
 ``--no-graphs``, ``--backend {hip,torch}``, ``--synthetic/--real-data``,
 ``--trials-per-group T`` (T concurrent trials per single-rank group, one HIP
@@ -59,6 +60,9 @@ def parse_args(argv=None):
     parser.add_argument("--lr-min-ratio", type=str, default=None, help="cosine floor as a fraction of lr, in [0, 1]")
     parser.add_argument("--kl-anneal", type=str, default=None,
                         help="steps over which the KLD weight ramps linearly from 0 to --beta")
+    parser.add_argument("--free-bits", type=str, default=None,
+                        help="free bits: a floor in nats under each latent dimension's KL term of each sample "
+                             "(training objective only; 0 = off), comma list per trial")
     parser.add_argument("--seed", type=int, default=0, help="base seed (trial g uses seed+g)")
     parser.add_argument("--no-epoch-offset", action="store_true", help="all trials train --epochs epochs")
     parser.add_argument("--log-interval", type=int, default=10)
@@ -133,7 +137,8 @@ def main(argv=None):
                         epoch_offset=not args.no_epoch_offset, lr_warmups=parse_list(args.lr_warmup, int),
                         lr_decays=parse_list(args.lr_decay, lambda s: s.strip()),
                         lr_decay_steps=parse_list(args.lr_decay_steps, int),
-                        lr_min_ratios=parse_list(args.lr_min_ratio), kl_anneals=parse_list(args.kl_anneal, int))
+                        lr_min_ratios=parse_list(args.lr_min_ratio), kl_anneals=parse_list(args.kl_anneal, int),
+                        free_bits=args.free_bits)
     opts = RunOptions(batch_size=args.batch_size, log_interval=args.log_interval,
                       backend=args.backend, use_graphs=not args.no_graphs, graph_steps=args.graph_steps,
                       ckpt_dir=args.ckpt_dir, resume=args.resume, metrics_dir=args.metrics_dir,
@@ -143,7 +148,8 @@ def main(argv=None):
                       synthetic=False if args.real_data else (True if args.synthetic else None),
                       model=args.model, image_size=args.image_size, bucket_mb=parse_bucket_mb(args.bucket_mb),
                       profile=args.profile, iw_samples=max(0, args.iw_samples), latent_report=args.latent_report,
-                      au_threshold=args.au_threshold, binarize=args.binarize)
+                      au_threshold=args.au_threshold, binarize=args.binarize,
+                      report_free_bits=any(s.free_bits > 0 for s in specs))
     results = []
     member = False
     for group_id, group in enumerate(processes_groups):
@@ -185,6 +191,9 @@ def main(argv=None):
                    "failed_trials": sorted(failed)}
         if opts.binarize != "none":
             summary["binarize"] = opts.binarize  # the likelihood every score of this run is under
+        if opts.report_free_bits:
+            # the KL floor (nats) of every trial's training objective; test scores are the true ELBO terms
+            summary["free_bits"] = {str(s.group_id): s.free_bits for s in specs}
         if opts.iw_samples > 0:
             # per-image means over the test set; the lowest bound on -log p(x) is the best trial
             summary["iw_samples"] = opts.iw_samples
@@ -194,6 +203,9 @@ def main(argv=None):
             # per-image means over the test set (nats); active_units counts Var_x(mu_d) > --au-threshold
             summary["latent"] = {str(g): {k: (v[k] if k == "active_units" else round(v[k], 4)) for k in lat_keys}
                                  for g, v in sorted(latent.items())}
+            for g, v in latent.items():  # trials with a KL floor: the dimensions it holds up
+                if "below_floor" in v:
+                    summary["latent"][str(g)]["below_floor"] = v["below_floor"]
         if args.metrics_dir:
             os.makedirs(args.metrics_dir, exist_ok=True)
             with open(os.path.join(args.metrics_dir, "aggregate.json"), "w") as f:
