@@ -19,6 +19,7 @@ void bind_cpu(pybind11::module& m);
 void bind_iw(pybind11::module& m);
 void bind_latent(pybind11::module& m);
 void bind_data(pybind11::module& m);
+void bind_tc(pybind11::module& m);
 }  // namespace mdt
 
 PYBIND11_MODULE(_C, m) {
@@ -36,6 +37,7 @@ PYBIND11_MODULE(_C, m) {
   mdt::bind_iw(m);
   mdt::bind_latent(m);
   mdt::bind_data(m);
+  mdt::bind_tc(m);
 
   // the trial-state owner of both trainers (runtime/trial_state.h); kLossHist: the length of its loss rings
   m.attr("kLossHist") = (int64_t)mdt::kLossHist;
@@ -45,11 +47,12 @@ PYBIND11_MODULE(_C, m) {
            py::arg("eps"), py::arg("weight_decay"), py::arg("kl_beta"), py::arg("grad_scale"), py::arg("seed"),
            py::arg("decoupled_wd"), py::arg("lr_warmup_steps") = 0, py::arg("lr_decay") = 0,
            py::arg("lr_decay_steps") = 0, py::arg("lr_min_ratio") = 0.0, py::arg("kl_anneal_steps") = 0,
-           py::arg("free_bits") = 0.0)
+           py::arg("free_bits") = 0.0, py::arg("tc_weight") = 0.0)
       .def("set_cursor", &mdt::TrialStateBuf::set_cursor)
       .def("set_step", &mdt::TrialStateBuf::set_step)
       .def("reset_loss", &mdt::TrialStateBuf::reset_loss)
       .def("read_state", &mdt::TrialStateBuf::read_state)
+      .def("read_tc", &mdt::TrialStateBuf::read_tc)
       .def("loss_history", &mdt::TrialStateBuf::loss_history)
       .def_readonly("train_state", &mdt::TrialStateBuf::train_state)
       .def_readonly("eval_state", &mdt::TrialStateBuf::eval_state)
@@ -71,6 +74,7 @@ PYBIND11_MODULE(_C, m) {
       .def("act", &mdt::MlpVaeEngine::act)
       .def("decode", &mdt::MlpVaeEngine::decode)
       .def("set_stamps", &mdt::MlpVaeEngine::set_stamps)
+      .def("set_dmulv_add", &mdt::MlpVaeEngine::set_dmulv_add)
       .def("iw_begin", &mdt::MlpVaeEngine::iw_begin, py::arg("nbatches"))
       .def("iw_batch", &mdt::MlpVaeEngine::iw_batch, py::arg("X"), py::arg("idx"), py::arg("M"), py::arg("K"),
            py::arg("chunk"), py::arg("row_nll"), py::arg("row_neg_elbo"))

@@ -367,9 +367,7 @@ static void launch_pair(const LatentArgs* a, hipStream_t s) {
                      dim3(kLatRowTile), 0, s, *a);
 }
 
-extern "C" int mdt_latent_pair(const LatentArgs* a, hipStream_t s) {
-  const int rc = mdt_latent_check(a);
-  if (rc) return rc;
+static int launch_pair_zt(const LatentArgs* a, hipStream_t s) {
   switch (lat_zt(a->Z)) {
     case 4: launch_pair<4>(a, s); break;
     case 8: launch_pair<8>(a, s); break;
@@ -390,6 +388,23 @@ extern "C" int mdt_latent_pair(const LatentArgs* a, hipStream_t s) {
     default: return 1;
   }
   return (int)hipGetLastError();
+}
+
+extern "C" int mdt_latent_pair(const LatentArgs* a, hipStream_t s) {
+  const int rc = mdt_latent_check(a);
+  if (rc) return rc;
+  return launch_pair_zt(a, s);
+}
+
+// The pair kernel over operands the caller packed itself (vae_tc.hip): the
+// same domain, and only the buffers the kernel touches.
+extern "C" int mdt_latent_pair_operands(const LatentArgs* a, hipStream_t s) {
+  if (a->Z < 1 || a->Z > kLatMaxZ) return 1;
+  if (a->n < 1) return 2;
+  if ((unsigned long long)a->n * (unsigned long long)a->Z > (1ull << 32)) return 3;
+  if (a->splits < 1 || a->splits > kLatMaxSplits || a->splits > lat_cdiv(a->n, kLatJTile)) return 4;
+  if (!a->z || !a->pk || !a->acc_m || !a->acc_s) return 5;
+  return launch_pair_zt(a, s);
 }
 
 extern "C" int mdt_latent_report(const LatentArgs* a, hipStream_t s) {

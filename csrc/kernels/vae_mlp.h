@@ -41,6 +41,11 @@ struct TrainState {
   float fb_t;          // effective free-bits floor (nats per latent element) of the step: HParams.free_bits,
                        // 0 in eval states (eval reports the true KL, as it uses the full beta)
   float loss_hist[kLossHist];
+  // total-correlation penalty (vae_tc.hip), after the ring: every earlier field keeps its offset
+  float tc_t;          // effective weight of the step: tc_weight * f_kl(step), 0 in eval states
+  int32_t pad_;
+  double epoch_tc;     // running sum of tc_batch (unweighted) since the host reset it; epoch_loss and the
+                       // loss ring stay BCE + kl_t * KL
 };
 
 // Per-trial hyper-parameters, device-resident so a captured graph picks up
@@ -60,6 +65,8 @@ struct HParams {
   int32_t kl_anneal;              // A: KL weight ramps linearly over the first A steps
   // free bits: per-sample, per-dimension KL floor in nats (0 = off, see fb_fwd / fb_bwd in common.h)
   float free_bits;
+  // total-correlation penalty: weight of tc_batch in the objective (0 = off), ramped like the KL weight
+  float tc_weight;
 };
 
 constexpr int kLrDecayNone = 0, kLrDecayCosine = 1;
@@ -93,6 +100,9 @@ __host__ __device__ inline void sched_store(TrainState* st, const HParams& hp, l
   st->kl_t = (float)(hp.kl_beta_d * (on ? sched_kl_factor(hp, t) : 1.0));
   st->kl_next = (float)(hp.kl_beta_d * (on ? sched_kl_factor(hp, t + 1) : 1.0));
   st->fb_t = on ? hp.free_bits : 0.f;  // no schedule: the same for every t
+  // the KL anneal's ramp. Without a weight nothing is computed or stored: the word stays the 0 the host
+  // seeded (set_hparams re-seeds it through sched_seed), and the default step does no more than before
+  if (hp.tc_weight != 0.f) st->tc_t = on ? (float)((double)hp.tc_weight * sched_kl_factor(hp, t)) : 0.f;
 }
 
 #ifdef __HIPCC__
@@ -129,6 +139,9 @@ struct VaeArgs {
   long long oW1, ob1, oW2, ob2;   // arena offsets of the epilogue-updated tensors
   long long s_beg, s_end;         // arena range Adam-streamed by B3 (fc3, fc4)
   unsigned long long* stamps;     // optional phase timestamps (profiling builds of a run)
+  // optional [M, 2Z]: added to d[mu|lv] in B2 before they are stored and before the dh1 product (the
+  // total-correlation penalty's share, vae_tc.hip); null: B2 is bit for bit the step without it
+  const float* dmulv_add;
 };
 
 // stamps[((kernel*kStampBlocks + block)*8 + wave)*8 + slot] = s_memrealtime (100 MHz)

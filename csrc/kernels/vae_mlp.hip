@@ -521,6 +521,12 @@ __global__ void __launch_bounds__(kThreads) vae_b2(VaeArgs a, int nrow, int nw3,
     lv = a.mulv[(size_t)ic * Z2 + a.Z + c];
     ep = a.eps[(size_t)ic * a.Z + c];
   }
+  float am = 0.f, al = 0.f;  // the optional addend of d[mu|lv] (uniform branch: the pointer is a kernel argument)
+  if (a.dmulv_add && mine) {
+    const int ic = min(i, a.M - 1);
+    am = a.dmulv_add[(size_t)ic * Z2 + c];
+    al = a.dmulv_add[(size_t)ic * Z2 + a.Z + c];
+  }
   // phase 1: quarter sums of the dz slabs, float4 per (row, quad)
   float* part = red;  // [4][16][SWZ]
   {
@@ -562,6 +568,10 @@ __global__ void __launch_bounds__(kThreads) vae_b2(VaeArgs a, int nrow, int nw3,
       const float be = fb_bwd(ks, fb, beta);
       dmu = kl_dmu(dz, be, mu);
       dlv = kl_dlv(dz, ep, sd, be);
+      if (a.dmulv_add) {
+        dmu += am;
+        dlv += al;
+      }
     }
     dml[r][c] = dmu;
     dml[r][a.Z + c] = dlv;

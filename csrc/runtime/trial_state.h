@@ -47,6 +47,10 @@ inline void sched_seed(at::Tensor& state, const HParams& h, int64_t step, bool e
   auto cpu = torch::empty({(int64_t)(hi - lo)}, torch::kUInt8);
   std::memcpy(cpu.data_ptr(), reinterpret_cast<const char*>(img.get()) + lo, hi - lo);
   state.narrow(0, lo, hi - lo).copy_(cpu);
+  // ... and the total-correlation weight, which lives after the loss ring
+  auto tc = torch::empty({(int64_t)sizeof(float)}, torch::kUInt8);
+  std::memcpy(tc.data_ptr(), &img->tc_t, sizeof(float));  // 0 without a weight (the image is zero-initialised)
+  state.narrow(0, offsetof(TrainState, tc_t), sizeof(float)).copy_(tc);
 }
 
 class TrialStateBuf {
@@ -62,8 +66,10 @@ class TrialStateBuf {
   }
   void set_hparams(double lr, double b1, double b2, double eps, double wd, double kl_beta, double gs, int64_t seed,
                    bool decoupled, int64_t lr_warmup = 0, int64_t lr_decay = 0, int64_t lr_decay_steps = 0,
-                   double lr_min_ratio = 0.0, int64_t kl_anneal = 0, double free_bits = 0.0) {
+                   double lr_min_ratio = 0.0, int64_t kl_anneal = 0, double free_bits = 0.0,
+                   double tc_weight = 0.0) {
     TORCH_CHECK_VALUE(std::isfinite(free_bits) && free_bits >= 0.0, "free_bits must be finite and >= 0, got ", free_bits);
+    TORCH_CHECK_VALUE(std::isfinite(tc_weight) && tc_weight >= 0.0, "tc_weight must be finite and >= 0, got ", tc_weight);
     HParams h;
     std::memset(&h, 0, sizeof(h));
     h.lr = (float)lr; h.beta1 = (float)b1; h.beta2 = (float)b2; h.eps = (float)eps; h.weight_decay = (float)wd;
@@ -72,6 +78,7 @@ class TrialStateBuf {
     h.lr_d = lr; h.beta1_d = b1; h.beta2_d = b2;
     sched_fill(h, kl_beta, lr_warmup, lr_decay, lr_decay_steps, lr_min_ratio, kl_anneal);
     h.free_bits = (float)free_bits;
+    h.tc_weight = (float)tc_weight;
     hp_ = h;
     const bool changed = b1 != b1_ || b2 != b2_;
     b1_ = b1; b2_ = b2;
@@ -101,7 +108,11 @@ class TrialStateBuf {
     pows(s, step);
     sched_seed(s, hp_, step, eval);
   }
-  void reset_loss(bool eval) { (eval ? eval_state : train_state).narrow(0, offsetof(TrainState, epoch_loss), 16).zero_(); }
+  void reset_loss(bool eval) {
+    at::Tensor& s = eval ? eval_state : train_state;
+    s.narrow(0, offsetof(TrainState, epoch_loss), 16).zero_();
+    s.narrow(0, offsetof(TrainState, epoch_tc), 8).zero_();
+  }
   // step, cursor, nbatches, epoch_loss, epoch_count, lr, kl_beta, free_bits
   std::vector<double> read_state(bool eval) {
     auto cpu = (eval ? eval_state : train_state).narrow(0, 0, offsetof(TrainState, loss_hist)).to(torch::kCPU);
@@ -110,6 +121,14 @@ class TrialStateBuf {
     // + the effective lr, KL weight and free-bits floor of the last completed step (what its kernels used)
     return {(double)h.step, (double)h.cursor, (double)h.nbatches, h.epoch_loss, h.epoch_count, h.lr_t, (double)h.kl_t,
             (double)h.fb_t};
+  }
+  // total-correlation penalty: the effective weight of the last completed step and the running sum of tc_batch
+  std::vector<double> read_tc(bool eval) {
+    constexpr size_t lo = offsetof(TrainState, tc_t), n = sizeof(TrainState) - lo;
+    auto cpu = (eval ? eval_state : train_state).narrow(0, lo, n).to(torch::kCPU);
+    auto h = std::make_unique<TrainState>();
+    std::memcpy(reinterpret_cast<char*>(h.get()) + lo, cpu.data_ptr(), n);
+    return {(double)h->tc_t, h->epoch_tc};
   }
   at::Tensor loss_history(bool eval) {  // CPU float tensor [kLossHist]
     return (eval ? eval_state : train_state)

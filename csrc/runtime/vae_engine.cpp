@@ -193,8 +193,19 @@ void MlpVaeEngine::backward(const at::Tensor& X, const at::Tensor& idx, int64_t 
   VaeArgs a;
   fill_args(&a, X, idx, M, true, false, 0, false);
   a.fuse_adam = fuse_adam ? 1 : 0;
+  a.dmulv_add = dmulv_add_.defined() ? dmulv_add_.data_ptr<float>() : nullptr;
   check_rc(mdt_vae_backward(&a, c10::hip::getCurrentHIPStream().stream(), (int)part),
            "vae backward");
+}
+
+void MlpVaeEngine::set_dmulv_add(c10::optional<at::Tensor> t) {
+  if (!t.has_value() || !t->defined()) {
+    dmulv_add_ = at::Tensor();
+    return;
+  }
+  TORCH_CHECK(t->is_cuda() && t->scalar_type() == torch::kFloat32 && t->is_contiguous() && t->numel() >= B_ * 2 * Z_,
+              "set_dmulv_add: needs a contiguous CUDA float32 tensor of >= B*2Z elements");
+  dmulv_add_ = *t;
 }
 
 void MlpVaeEngine::adam() {

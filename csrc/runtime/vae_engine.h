@@ -59,6 +59,9 @@ class MlpVaeEngine {
   at::Tensor decode(const at::Tensor& z);  // sigmoid(fc4(relu(fc3 z))) -> [M, D]
   at::Tensor act(const std::string& name, int64_t M);
   void set_stamps(at::Tensor t) { stamps_ = t; }  // int64 [6*512*8*8] or undefined
+  // float32 [B, 2Z] that the backward's B2 adds to d[mu|lv] (the total-correlation penalty's share,
+  // csrc/kernels/vae_tc.hip), or None: B2 as without it
+  void set_dmulv_add(c10::optional<at::Tensor> t);
 
   // Importance-weighted log-likelihood pass (csrc/kernels/vae_iw.hip). It runs
   // on a device state of its own (iw_state); train_state / eval_state, their
@@ -96,7 +99,7 @@ class MlpVaeEngine {
   int64_t B_, D_, H_, Z_, total_, split_;
   int last_f2_blocks_ = 0, last_f3_blocks_ = 0;
   std::vector<LayoutEntry> layout_;
-  at::Tensor stamps_;
+  at::Tensor stamps_, dmulv_add_;
   at::Tensor iw_ws_, iw_rowbuf_;  // chunk workspace (h3 | eps | z | prior | bce) and [3][B] running row state
   int64_t iw_cap_ = 0, iw_nbatches_ = 0, latent_nbatches_ = 0;
   std::vector<std::pair<std::string, int64_t>> act_off_;

@@ -23,7 +23,8 @@ with ``torch.load(weights_only=True)`` (never unpickles code):
   data         {"binarize": none | threshold | static | dynamic}: the likelihood
                the trial trains under (data/binarize.py). ``load_latest`` returns
                it (absent = none); the runner refuses a resume under another one
-  objective    {"free_bits": the trainer's KL floor in nats per latent element}:
+  objective    {"free_bits": the trainer's KL floor in nats per latent element,
+               "tc_weight": the weight of its total-correlation penalty, when > 0}:
                returned by ``load_latest`` (absent = 0) and checked by the runner
                in the same way
 Only group rank 0 writes (replicas are identical after the all-reduce);
@@ -64,6 +65,8 @@ def save_trial(ckpt_dir: str, trainer, spec, epoch: int, extra: Optional[dict] =
         "data": {"binarize": str(binarize)},
         "objective": {"free_bits": float(trainer.hp.get("free_bits", 0.0))},
     }
+    if float(trainer.hp.get("tc_weight", 0.0)) > 0:  # recorded only where it is in force (absent = 0)
+        payload["objective"]["tc_weight"] = float(trainer.hp["tc_weight"])
     if extra:
         payload["extra"] = extra
     name = f"epoch-{epoch}.pt"
@@ -110,4 +113,5 @@ def load_latest(ckpt_dir: str, group_id: int, trainer) -> Optional[dict]:
         trainer.set_schedule(Schedule(**ck["schedule"]))
     trainer.load_optimizer_state(ck["optimizer"])  # sets the step: the schedule continues from it
     return dict(ck["progress"], path=path, trial=ck["trial"], binarize=(ck.get("data") or {}).get("binarize", "none"),
-                free_bits=float((ck.get("objective") or {}).get("free_bits", 0.0)))
+                free_bits=float((ck.get("objective") or {}).get("free_bits", 0.0)),
+                tc_weight=float((ck.get("objective") or {}).get("tc_weight", 0.0)))

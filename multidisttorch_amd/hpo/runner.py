@@ -79,6 +79,7 @@ class RunOptions:
     au_threshold: float = 0.01             # a dimension is active when Var_x(mu_d) exceeds this
     binarize: str = "none"                 # none | threshold | static | dynamic (data/binarize.py); one value per run
     report_free_bits: bool = False         # some trial of the run sets --free-bits: the metrics carry every trial's value
+    report_tc: bool = False                # some trial sets --tc-weight: the metrics carry train_tc and tc_weight
 
 
 @dataclass
@@ -130,7 +131,7 @@ def _make_trainer(spec: TrialSpec, opts: RunOptions, device, group_rank: int, D:
         return MlpVaeTrainer(batch_size=opts.batch_size, D=D, device=device, backend=opts.backend,
                              seed=spec.seed, lr=spec.lr, kl_beta=spec.beta, rng_stream=group_rank,
                              use_graphs=opts.use_graphs, graph_steps=opts.graph_steps, schedule=sched,
-                             free_bits=spec.free_bits)
+                             free_bits=spec.free_bits, tc_weight=spec.tc_weight)
     if opts.model == "conv":
         from ..models.conv_vae import ConvVaeTrainer
 
@@ -138,7 +139,7 @@ def _make_trainer(spec: TrialSpec, opts: RunOptions, device, group_rank: int, D:
                               z=32 if opts.image_size == 28 else 64, device=device, backend=opts.backend,
                               seed=spec.seed, lr=spec.lr, kl_beta=spec.beta, rng_stream=group_rank,
                               use_graphs=opts.use_graphs, graph_steps=opts.graph_steps, schedule=sched,
-                              free_bits=spec.free_bits)
+                              free_bits=spec.free_bits, tc_weight=spec.tc_weight)
     raise ValueError(f"unknown model {opts.model!r}")
 
 
@@ -177,6 +178,14 @@ def _check_resumed_free_bits(prog, spec: TrialSpec):
     if prog is not None and float(prog.get("free_bits", 0.0)) != float(spec.free_bits):
         raise ValueError(f"trial {spec.group_id}: checkpoint {prog['path']} was trained with --free-bits "
                          f"{prog.get('free_bits', 0.0)}, this run asks for --free-bits {spec.free_bits}")
+
+
+def _check_resumed_tc_weight(prog, spec: TrialSpec):
+    """... and the weight of its total-correlation penalty (an old checkpoint
+    without the record was trained without one)."""
+    if prog is not None and float(prog.get("tc_weight", 0.0)) != float(spec.tc_weight):
+        raise ValueError(f"trial {spec.group_id}: checkpoint {prog['path']} was trained with --tc-weight "
+                         f"{prog.get('tc_weight', 0.0)}, this run asks for --tc-weight {spec.tc_weight}")
 
 
 def _refresh_train(binarizer, trainer, epoch: int, opts: RunOptions, device):
@@ -489,6 +498,7 @@ def run_trial(spec: TrialSpec, group, opts: RunOptions, data=None, num_trials: O
                 prog = ckpt.load_latest(opts.ckpt_dir, spec.group_id, trainer)
                 _check_resumed_binarize(prog, opts, spec.group_id)
                 _check_resumed_free_bits(prog, spec)
+                _check_resumed_tc_weight(prog, spec)
             except Exception as e:  # noqa: BLE001 - re-raised below on every member
                 err = e
         if prog is not None:
@@ -626,6 +636,10 @@ def _run_epoch(trainer, epoch, n_shard, train, test, opts, group, rdir, shape, g
                 test_loss=test_loss, epoch_train_s=t_train, samples=n_shard,
                 train_samples_per_s=n_shard / max(t_train, 1e-9), lr=st["lr"], kl_beta=st["kl_beta"],
                 lr_base=spec.lr, beta=spec.beta, **({"free_bits": st["free_bits"]} if opts.report_free_bits else {}),
+                # train_tc: the epoch's sum of tc_batch (unweighted, models/tc.py) over the rows trained;
+                # tc_weight: the effective weight of the epoch's last step
+                **({"train_tc": st["epoch_tc"] / max(n_shard, 1), "tc_weight": st["tc_weight"]}
+                   if opts.report_tc else {}),
                 **phases)
     return train_loss, test_loss
 
@@ -666,6 +680,7 @@ def run_packed_trials(specs, group, opts: RunOptions, data=None, num_trials: Opt
             prog = ckpt.load_latest(opts.ckpt_dir, spec.group_id, trainer)
             _check_resumed_binarize(prog, opts, spec.group_id)
             _check_resumed_free_bits(prog, spec)
+            _check_resumed_tc_weight(prog, spec)
             if prog is not None:
                 start = prog["epoch"] + 1
         idx = shard_indices(len(train), total, spec.group_id)  # packing extension: one shard per trial

@@ -33,6 +33,8 @@ class TrialSpec:
     kl_anneal_steps: int = 0
     # free bits: KL floor in nats per sample and latent dimension, 0 = off (csrc/kernels/common.h)
     free_bits: float = 0.0
+    # total-correlation penalty: weight of the minibatch TC estimate in the objective, 0 = off (models/tc.py)
+    tc_weight: float = 0.0
 
     def to_dict(self):
         return asdict(self)
@@ -76,19 +78,24 @@ def build_specs(num_groups: int, epochs: int, lrs: Optional[Sequence[float]] = N
                 epoch_offset: bool = True, lr_warmups: Optional[Sequence[int]] = None,
                 lr_decays: Optional[Sequence[str]] = None, lr_decay_steps: Optional[Sequence[int]] = None,
                 lr_min_ratios: Optional[Sequence[float]] = None,
-                kl_anneals: Optional[Sequence[int]] = None, free_bits=None) -> List[TrialSpec]:
+                kl_anneals: Optional[Sequence[int]] = None, free_bits=None, tc_weight=None) -> List[TrialSpec]:
     """Per-group specs. A single value broadcasts; a list is indexed by group (cycled).
-    ``free_bits``: a scalar, a list or a comma list like ``--beta``; finite and >= 0."""
+    ``free_bits``, ``tc_weight``: a scalar, a list or a comma list like ``--beta``; finite and >= 0."""
     def pick(vals, g, default):
         return vals[g % len(vals)] if vals else default
 
-    if free_bits is None or isinstance(free_bits, str):
-        free_bits = parse_list(free_bits)
-    elif isinstance(free_bits, (int, float)):
-        free_bits = [free_bits]
-    for v in free_bits or []:
-        if not (math.isfinite(float(v)) and float(v) >= 0.0):
-            raise ValueError(f"free_bits must be finite and >= 0, got {v}")
+    def nonneg(vals, name):
+        if vals is None or isinstance(vals, str):
+            vals = parse_list(vals)
+        elif isinstance(vals, (int, float)):
+            vals = [vals]
+        for v in vals or []:
+            if not (math.isfinite(float(v)) and float(v) >= 0.0):
+                raise ValueError(f"{name} must be finite and >= 0, got {v}")
+        return vals
+
+    free_bits = nonneg(free_bits, "free_bits")
+    tc_weight = nonneg(tc_weight, "tc_weight")
     out = []
     for g in range(num_groups):
         lr = lrs[g % len(lrs)] if lrs else 1e-3
@@ -97,7 +104,8 @@ def build_specs(num_groups: int, epochs: int, lrs: Optional[Sequence[float]] = N
                          lr_warmup_steps=int(pick(lr_warmups, g, 0)), lr_decay=str(pick(lr_decays, g, "none")),
                          lr_decay_steps=int(pick(lr_decay_steps, g, 0)),
                          lr_min_ratio=float(pick(lr_min_ratios, g, 0.0)),
-                         kl_anneal_steps=int(pick(kl_anneals, g, 0)), free_bits=float(pick(free_bits, g, 0.0)))
+                         kl_anneal_steps=int(pick(kl_anneals, g, 0)), free_bits=float(pick(free_bits, g, 0.0)),
+                         tc_weight=float(pick(tc_weight, g, 0.0)))
         # bad values fail here, not in the middle of a run (T = 0 under cosine is resolved by the runner)
         spec.schedule(total_steps=spec.lr_warmup_steps + 1 if spec.lr_decay_steps == 0 else None)
         out.append(spec)

@@ -230,10 +230,10 @@ class ConvVaeTrainer(VaeTrainerBase):
                  backend: Optional[str] = None, seed: int = 0, lr: float = 1e-3, kl_beta: float = 1.0,
                  betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0, decoupled_wd: bool = False,
                  rng_stream: int = 0, use_graphs: bool = True, graph_steps: int = 10, init_seed: Optional[int] = None,
-                 schedule: Optional[Schedule] = None, free_bits: float = 0.0):
+                 schedule: Optional[Schedule] = None, free_bits: float = 0.0, tc_weight: float = 0.0):
         z = check_latent_size(z)
         super().__init__(batch_size, device, backend, seed, rng_stream, lr, kl_beta, betas, eps, weight_decay,
-                         decoupled_wd, use_graphs, graph_steps, schedule, free_bits)
+                         decoupled_wd, use_graphs, graph_steps, schedule, free_bits, tc_weight)
         backend = self.backend
         self.image, self.channels, self.Z = image, channels, z
         self.D = image * image * channels
@@ -270,8 +270,11 @@ class ConvVaeTrainer(VaeTrainerBase):
         # per-sample fused 28x28 step (csrc/kernels/conv28_fused.hip): forward,
         # backward-data, weight gradients and optimizer in 4 launches instead of
         # the layer-by-layer path's 15. MDT_CONV_F28=0 keeps the layer path.
+        # The fused step owns a sample end to end in one workgroup pair and cannot host
+        # a cross-sample term: a trainer with the total-correlation penalty trains on
+        # the layer path (which already serves 28x28 for z != 32).
         self.f28 = (backend == "hip" and image == 28 and channels == 1 and z == 32
-                    and os.getenv("MDT_CONV_F28", "1") != "0")
+                    and os.getenv("MDT_CONV_F28", "1") != "0" and not self.tc_on)
         self._plans28 = {}
         self.f28_skip_adam = False  # tests: leave the reduced gradients in `grads`, no update
         # forward and backward of the fused step in one launch (MDT_F28_MERGE=0: two)
@@ -497,6 +500,8 @@ class ConvVaeTrainer(VaeTrainerBase):
         self.dz = torch.zeros(B, zf, **f32)
         self.dmulv = torch.zeros(B, 2 * zf, **f32)
         self.dmulv16 = torch.zeros(B, 2 * zf, **bf)
+        if self.tc_on:
+            self._tc_alloc()
         self.logits = torch.zeros(B * self.D, **f32)
         self.recon = torch.zeros(B * self.D, **f32)
         self.dlog16 = torch.zeros(B * self.D, **bf)
@@ -777,6 +782,7 @@ class ConvVaeTrainer(VaeTrainerBase):
                                       state, hp, stream, self.kld_part)
                     if enc_only:
                         return
+                    self._tc_forward(M, train)
                     break
             self._layer_fwd(l, h, M, None if last else self.acts[l.name], self.mulv if last else None, p["ws"],
                             **(pro if last else {}))
@@ -785,6 +791,7 @@ class ConvVaeTrainer(VaeTrainerBase):
             if enc_only:
                 return
             C.reparam(self.mulv, self.eps, self.z16, None, M, self.Z, state, hp, stream, self.kld_part)
+            self._tc_forward(M, train)
         h = self.z16
         for l in dec:
             last = l is dec[-1]
@@ -809,6 +816,14 @@ class ConvVaeTrainer(VaeTrainerBase):
             h = self.acts[l.name]
         C.bce_logits(self.logits, self.xb, None, M, self.D, self.dlog16 if train else None,
                      self.recon if want_recon else None, self.bce_part, p["gpart"] if train else None)
+
+    def _tc_forward(self, M, training_step):
+        """Training step with the total-correlation penalty: its forward and
+        backward kernels (vae_tc.hip), which need only the step's mulv and eps;
+        the fold runs after the reparameterisation backward (``_backward_hip``)."""
+        if self.tc_on and training_step:
+            self.C.tc_penalty(self.mulv, self.eps, M, self.Z, self.tc_ws, self.tc_value,
+                              state=self.state.train_state, stage=1)
 
     def _run_group(self, fns):
         """Run independent launches ``fns`` (each ``f(job)``): recorded as jobs
@@ -897,6 +912,12 @@ class ConvVaeTrainer(VaeTrainerBase):
                     else:
                         after.append(lambda: C.reparam_bwd(self.dz, self.mulv, self.eps, self.dmulv, self.dmulv16,
                                                            M, self.Z, st.hparams, state=st.train_state))
+                    if self.tc_on:
+                        # the penalty's share, added in place to d[mu|lv] (bf16 copy rewritten) by the fold
+                        # kernel of vae_tc.hip; its forward and backward ran after the reparameterisation
+                        after.append(lambda: C.tc_penalty(self.mulv, self.eps, M, self.Z, self.tc_ws, self.tc_value,
+                                                          state=st.train_state, dmulv=self.dmulv,
+                                                          dmulv16=self.dmulv16, stage=2))
                     cso = p["colsum"][prev.name]
                     carry.append(lambda job, cso=cso: C.colsum(self.dmulv16, M, 2 * self.Z, p["rows_per"], cso,
                                                                job=job))
@@ -1322,8 +1343,17 @@ class ConvVaeTrainer(VaeTrainerBase):
         x, eps = self._torch_batch(X, idx, st["cursor"], M, self.rng_stream, st["step"])
         self.model.zero_grad(set_to_none=True)
         lr_t, kl_t = self._effective(st["step"] + 1)
-        loss, *_ = self.model.loss(x, eps, kl_t, self.hp["free_bits"])
-        loss.backward()
+        loss, _, mu, lv = self.model.loss(x, eps, kl_t, self.hp["free_bits"])
+        tc = 0.0
+        if self.tc_on:
+            # the objective also carries tc_t * tc_batch (models/tc.py); the recorded loss stays BCE + kl_t * KL
+            from .tc import tc_batch
+
+            tcb = tc_batch(mu, lv, eps)
+            tc = float(tcb.detach())
+            (loss + self._tc_effective(st["step"] + 1) * tcb).backward()
+        else:
+            loss.backward()
         with torch.no_grad():
             gv = self.named_grads()
             for k, v in self.model.grads_to_arena().items():
@@ -1335,7 +1365,7 @@ class ConvVaeTrainer(VaeTrainerBase):
             reference_adam_(self.params, self.grads, self.exp_avg, self.exp_avg_sq, st["step"] + 1, lr_t,
                             h["beta1"], h["beta2"], h["eps"], h["weight_decay"], h["grad_scale"], self.decoupled_wd)
             self.model.from_arena(self.named_parameters())
-        self._record(float(loss.detach()))
+        self._record(float(loss.detach()), tc=tc)
 
     # ----------------------------------------------------------- driver API
     def train_steps(self, n, M=None):

@@ -40,9 +40,9 @@ class MlpVaeTrainer(VaeTrainerBase):
                  lr: float = 1e-3, kl_beta: float = 1.0, betas=(0.9, 0.999), eps: float = 1e-8,
                  weight_decay: float = 0.0, decoupled_wd: bool = False, rng_stream: int = 0,
                  use_graphs: bool = True, graph_steps: int = 10, schedule: Optional[Schedule] = None,
-                 free_bits: float = 0.0):
+                 free_bits: float = 0.0, tc_weight: float = 0.0):
         super().__init__(batch_size, device, backend, seed, rng_stream, lr, kl_beta, betas, eps, weight_decay,
-                         decoupled_wd, use_graphs, graph_steps, schedule, free_bits)
+                         decoupled_wd, use_graphs, graph_steps, schedule, free_bits, tc_weight)
         self.D, self.H, self.Z = D, H, Z
         self.layout, self.numel, self.split = arena_layout(D, H, Z)
         if self.backend == "hip":
@@ -54,6 +54,10 @@ class MlpVaeTrainer(VaeTrainerBase):
                 "C++/Python arena layouts disagree"
             self.params, self.grads = self.engine.params, self.engine.grads
             self.exp_avg, self.exp_avg_sq = self.engine.exp_avg, self.engine.exp_avg_sq
+            if self.tc_on:
+                # the penalty's kernels write their share of d[mu|lv] here and B2 adds it (vae_tc.hip)
+                self._tc_alloc()
+                self.engine.set_dmulv_add(self.tc_add)
         else:
             self.engine = None
             z = lambda: torch.zeros(self.numel, dtype=torch.float32, device=self.device)
@@ -90,6 +94,7 @@ class MlpVaeTrainer(VaeTrainerBase):
         X, idx = self._data[0], self._data[1]
         e = self.engine
         e.forward(X, idx, M, True, False, self.rng_stream, False)
+        self._tc_step(M)
         early = self._overlap()
         if self.reducer is not None and hasattr(self.reducer, "set_inline"):
             self.reducer.set_inline(not early)
@@ -111,6 +116,15 @@ class MlpVaeTrainer(VaeTrainerBase):
             # Adam fused into the weight-gradient epilogues of B3
             e.backward(X, idx, M, 0, True)
 
+    def _tc_step(self, M: int):
+        """Between forward and backward of a training step: value and gradient
+        of tc_t * tc_batch from the step's mulv and eps (csrc/kernels/vae_tc.hip),
+        into the buffer B2 adds to d[mu|lv]. Nothing without the penalty."""
+        if self.tc_on:
+            e = self.engine
+            native.require().tc_penalty(e.act("mulv", M), e.act("eps", M), M, self.Z, self.tc_ws, self.tc_value,
+                                        state=self.state.train_state, add_out=self.tc_add)
+
     _CPU_ORDER = ("fc1.weight", "fc1.bias", "fc21.weight", "fc21.bias", "fc22.weight", "fc22.bias",
                   "fc3.weight", "fc3.bias", "fc4.weight", "fc4.bias")
 
@@ -118,8 +132,8 @@ class MlpVaeTrainer(VaeTrainerBase):
         """The fused native CPU step (csrc/runtime/cpu_mlp.cpp) when the torch
         backend runs on the host and the extension is built; None otherwise
         (stock torch ops, ``reference_step``)."""
-        if self.device.type != "cpu" or not native.available():
-            return None
+        if self.device.type != "cpu" or not native.available() or self.tc_on:
+            return None  # the total-correlation penalty runs on the stock-torch path
         if getattr(self, "_cpu", None) is None:
             self._cpu = native.require().MlpCpuStep(self.B, self.D, self.H, self.Z)
             v, g = self.named_parameters(), self.named_grads()
@@ -140,7 +154,8 @@ class MlpVaeTrainer(VaeTrainerBase):
         else:
             x, eps = self._torch_batch(X, idx, st["cursor"], M, self.rng_stream, st["step"])
             f = reference_step(self.named_parameters(), self.named_grads(), x, eps, kl_t,
-                               free_bits=h["free_bits"])
+                               free_bits=h["free_bits"],
+                               tc_t=self._tc_effective(st["step"] + 1) if self.tc_on else None)
             loss = None
         if self.reducer is not None:
             self.reducer.launch(1)
@@ -154,7 +169,7 @@ class MlpVaeTrainer(VaeTrainerBase):
                             lr_t, h["beta1"], h["beta2"], h["eps"], h["weight_decay"], h["grad_scale"],
                             self.decoupled_wd)
             loss = float(f["loss"])
-        self._record(loss)
+        self._record(loss, tc=float(f["tc_batch"]) if cpu is None and self.tc_on else 0.0)
 
     def model_meta(self) -> dict:
         """Architecture record stored in checkpoints and validated on load."""

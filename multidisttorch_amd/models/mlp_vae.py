@@ -160,8 +160,10 @@ def reference_forward(v, x, eps, beta: float = 1.0, masks=None, free_bits: float
                 bce=bce, kld=kld, loss=bce + beta * kld, floored=floored)
 
 
-def reference_step(v, g, x, eps, beta: float = 1.0, masks=None, free_bits: float = 0.0):
-    """Explicit backward (kernels B1-B3) writing into grad views ``g``. Returns fwd dict."""
+def reference_step(v, g, x, eps, beta: float = 1.0, masks=None, free_bits: float = 0.0, tc_t=None):
+    """Explicit backward (kernels B1-B3) writing into grad views ``g``. Returns fwd dict.
+    ``tc_t`` (not None): the objective also carries ``tc_t * tc_batch`` (models/tc.py);
+    ``f["tc_batch"]`` is its unweighted value, ``f["loss"]`` stays BCE + beta * KLD."""
     f = reference_forward(v, x, eps, beta, masks, free_bits)
     W1, b1, W2, b2, W3, b3, W4, b4 = _w(v)
     Z = W3.shape[1]
@@ -175,6 +177,12 @@ def reference_step(v, g, x, eps, beta: float = 1.0, masks=None, free_bits: float
     be = free_bits_beta(beta, f["floored"], f["mu"])  # free bits: no KL part where the forward floored the element
     dmu = dz + be * f["mu"]
     dlv = 0.5 * dz * eps * f["sd"] + 0.5 * be * (f["sd"] * f["sd"] - 1)
+    if tc_t is not None:
+        from .tc import tc_closed_form
+
+        f["tc_batch"], am, al = tc_closed_form(f["mu"], f["lv"], eps)
+        dmu = dmu + tc_t * am
+        dlv = dlv + tc_t * al
     dmulv = torch.cat([dmu, dlv], 1)
     gW2 = dmulv.t() @ f["h1"]
     gb2 = dmulv.sum(0)

@@ -29,6 +29,7 @@ from ..ops import native
 from ..ops.philox import reparam_eps
 from .eval_graphs import GraphedEval, GraphedIwEval, GraphedLatentEval, capture_replayable
 from .mlp_vae import views
+from .tc import check_tc_weight
 
 __all__ = ["VaeTrainerBase", "LOSS_HIST", "EVAL_STREAM", "check_free_bits"]
 
@@ -47,7 +48,7 @@ def check_free_bits(v) -> float:
 class VaeTrainerBase(GraphedEval, GraphedIwEval, GraphedLatentEval):
     def __init__(self, batch_size: int, device, backend: Optional[str], seed: int, rng_stream: int, lr: float,
                  kl_beta: float, betas, eps: float, weight_decay: float, decoupled_wd: bool, use_graphs: bool,
-                 graph_steps: int, schedule: Optional[Schedule], free_bits: float = 0.0):
+                 graph_steps: int, schedule: Optional[Schedule], free_bits: float = 0.0, tc_weight: float = 0.0):
         self.B = batch_size
         # lr warm-up / cosine decay and KL annealing (hpo/schedule.py); None = off.
         # On the hip backend the kernels evaluate it from the device step counter.
@@ -61,7 +62,12 @@ class VaeTrainerBase(GraphedEval, GraphedIwEval, GraphedLatentEval):
         self.backend = backend
         self.seed, self.rng_stream = int(seed), int(rng_stream)
         self.hp = dict(lr=lr, beta1=betas[0], beta2=betas[1], eps=eps, weight_decay=weight_decay,
-                       kl_beta=kl_beta, grad_scale=1.0, free_bits=check_free_bits(free_bits))
+                       kl_beta=kl_beta, grad_scale=1.0, free_bits=check_free_bits(free_bits),
+                       tc_weight=check_tc_weight(tc_weight))
+        # total-correlation penalty (models/tc.py): a trainer built with it launches the penalty's
+        # kernels in every training step (a weight of 0 then only zeroes their result); one built
+        # without cannot be given a weight later -- its launch list has no such kernels
+        self.tc_on = self.hp["tc_weight"] > 0
         self.decoupled_wd = decoupled_wd
         self.use_graphs = use_graphs and backend == "hip"
         self.graph_steps = max(1, int(graph_steps))
@@ -79,7 +85,7 @@ class VaeTrainerBase(GraphedEval, GraphedIwEval, GraphedLatentEval):
         if backend == "hip":
             assert native.require().kLossHist == LOSS_HIST, "C++/Python loss ring lengths disagree"
         else:
-            self._st = dict(step=0, cursor=0, nbatches=0, epoch_loss=0.0, epoch_count=0.0)
+            self._st = dict(step=0, cursor=0, nbatches=0, epoch_loss=0.0, epoch_count=0.0, epoch_tc=0.0)
             self._st_eval = dict(self._st)
             self._hist = np.zeros(LOSS_HIST, np.float32)
             self._hist_eval = np.zeros(LOSS_HIST, np.float32)
@@ -121,6 +127,11 @@ class VaeTrainerBase(GraphedEval, GraphedIwEval, GraphedLatentEval):
         for k, v in kw.items():
             if k not in self.hp:
                 raise KeyError(k)
+            if k == "tc_weight":
+                v = check_tc_weight(v)
+                if v > 0 and not self.tc_on:
+                    raise ValueError("tc_weight > 0 needs a trainer built with tc_weight > 0 "
+                                     "(the step's launch list differs)")
             self.hp[k] = check_free_bits(v) if k == "free_bits" else float(v)
         self._push_hparams()
 
@@ -135,7 +146,8 @@ class VaeTrainerBase(GraphedEval, GraphedIwEval, GraphedLatentEval):
             h = self.hp
             self.state.set_hparams(h["lr"], h["beta1"], h["beta2"], h["eps"], h["weight_decay"], h["kl_beta"],
                                    h["grad_scale"], self.seed, self.decoupled_wd,
-                                   **(self.schedule or Schedule()).native_args(), free_bits=h["free_bits"])
+                                   **(self.schedule or Schedule()).native_args(), free_bits=h["free_bits"],
+                                   tc_weight=h["tc_weight"])
 
     def _effective(self, t: int):
         """(lr_t, beta_t) of optimizer step t on the torch backend, as doubles:
@@ -144,6 +156,21 @@ class VaeTrainerBase(GraphedEval, GraphedIwEval, GraphedLatentEval):
         if s is None:
             return h["lr"], h["kl_beta"]
         return h["lr"] * s.lr_factor(t), h["kl_beta"] * s.kl_factor(t)
+
+    def _tc_effective(self, t: int) -> float:
+        """tc_t of optimizer step t on the torch backend: the float32 of
+        tc_weight * f_kl(t), as the device forms it (sched_store)."""
+        s, w = self.schedule, float(np.float32(self.hp["tc_weight"]))
+        return float(np.float32(w * (s.kl_factor(t) if s is not None else 1.0)))
+
+    def _tc_alloc(self):
+        """hip backend: the penalty's workspace for any M <= B, its value and
+        the buffer of its share of d[mu|lv] (csrc/kernels/vae_tc.hip)."""
+        C, dev = native.require(), self.device
+        n = max(C.tc_ws_numel(m, self.Z) for m in range(1, self.B + 1))
+        self.tc_ws = torch.zeros(n, dtype=torch.float32, device=dev)
+        self.tc_value = torch.zeros(1, dtype=torch.float64, device=dev)
+        self.tc_add = torch.zeros(self.B, 2 * self.Z, dtype=torch.float32, device=dev)
 
     # ------------------------------------------------------------------ state
     @property
@@ -170,19 +197,20 @@ class VaeTrainerBase(GraphedEval, GraphedIwEval, GraphedLatentEval):
             self.state.reset_loss(eval)
         else:
             st = self._st_eval if eval else self._st
-            st["epoch_loss"], st["epoch_count"] = 0.0, 0.0
+            st["epoch_loss"], st["epoch_count"], st["epoch_tc"] = 0.0, 0.0, 0.0
 
     def read_state(self, eval: bool = False) -> dict:
         if self.state is not None:
-            s = self.state.read_state(eval)
+            s, t = self.state.read_state(eval), self.state.read_tc(eval)
             return dict(step=int(s[0]), cursor=int(s[1]), nbatches=int(s[2]), epoch_loss=s[3],
-                        epoch_count=s[4], lr=s[5], kl_beta=s[6], free_bits=s[7])
-        # lr / kl_beta / free_bits: the effective values of the last completed step (eval: always the
-        # full lr and beta, and no floor)
+                        epoch_count=s[4], lr=s[5], kl_beta=s[6], free_bits=s[7], tc_weight=t[0], epoch_tc=t[1])
+        # lr / kl_beta / free_bits / tc_weight: the effective values of the last completed step (eval:
+        # always the full lr and beta, no floor and no penalty)
         st = dict(self._st_eval if eval else self._st)
         lr, kl = (self.hp["lr"], self.hp["kl_beta"]) if eval else self._effective(st["step"])
         st["lr"], st["kl_beta"] = float(lr), float(np.float32(kl))
         st["free_bits"] = 0.0 if eval else float(np.float32(self.hp["free_bits"]))
+        st["tc_weight"] = 0.0 if eval else self._tc_effective(st["step"])
         return st
 
     def loss_history(self, eval: bool = False) -> np.ndarray:
@@ -190,13 +218,14 @@ class VaeTrainerBase(GraphedEval, GraphedIwEval, GraphedLatentEval):
             return self.state.loss_history(eval).numpy()
         return (self._hist_eval if eval else self._hist).copy()
 
-    def _record(self, loss: float, eval: bool = False):
+    def _record(self, loss: float, eval: bool = False, tc: float = 0.0):
         """torch backend: what a step's kernels do to the device state -- the
         loss into its ring slot and the running sum, step and cursor advanced
         (the cursor wraps at nbatches)."""
         st, hist = (self._st_eval, self._hist_eval) if eval else (self._st, self._hist)
         hist[st["step"] % LOSS_HIST] = loss
         st["epoch_loss"] += loss
+        st["epoch_tc"] += tc  # tc_batch of the step, unweighted (models/tc.py); the loss stays BCE + kl_t * KL
         st["epoch_count"] += 1
         st["step"] += 1
         st["cursor"] += 1

@@ -1,0 +1,42 @@
+"""Worker of tests/multiproc/test_tc_penalty_multiproc.py: two replicas of one
+trial (a group of 2, gloo, torch backend) that train with the total-correlation
+penalty. Prints one line ``RESULT <json>`` per rank."""
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, ROOT)
+
+import torch  # noqa: E402
+import torch.distributed as dist  # noqa: E402
+
+
+def main():
+    from multidisttorch_amd.models.mlp_trainer import MlpVaeTrainer
+    from multidisttorch_amd.parallel.ddp import broadcast_params, make_arena_reducer
+    from multidisttorch_amd.runtime.bootstrap import global_barrier, setup_ddp, shutdown
+
+    ws, wr = setup_ddp(verbose=False)
+    pg = dist.new_group(list(range(ws)))
+    tr = MlpVaeTrainer(batch_size=32, D=64, H=32, Z=4, backend="torch", seed=3 + wr, rng_stream=wr,
+                       tc_weight=float(sys.argv[1]))
+    broadcast_params([tr.params], pg)
+    tr.attach_reducer(make_arena_reducer(pg, tr.grads, [0, tr.split, tr.numel]))
+    X = torch.rand(256, 64, generator=torch.Generator().manual_seed(9))
+    tr.bind_train_data(X, torch.arange(256, dtype=torch.int32))
+    tr.set_cursor(0, 8)
+    tr.train_steps(5)
+    p = tr.params.clone()
+    allp = [torch.zeros_like(p) for _ in range(ws)]
+    dist.all_gather(allp, p)
+    st = tr.read_state()
+    print("RESULT " + json.dumps(dict(rank=wr, equal=all(torch.equal(a, allp[0]) for a in allp), step=st["step"],
+                                      epoch_tc=st["epoch_tc"], tc_weight=st["tc_weight"],
+                                      psum=float(p.double().abs().sum()))), flush=True)
+    global_barrier()
+    shutdown()
+
+
+if __name__ == "__main__":
+    main()

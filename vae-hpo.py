@@ -38,7 +38,7 @@ from multidisttorch_amd.data.binarize import BINARIZE_CHOICES
 from multidisttorch_amd.hpo.runner import RunOptions, idle_rank, run_packed_trials, run_trial
 from multidisttorch_amd.hpo.trial import build_specs, parse_list
 from multidisttorch_amd.parallel.autotune import parse_bucket_mb
-from multidisttorch_amd.runtime.bootstrap import control_group
+from multidisttorch_amd.runtime.bootstrap import control_group, global_barrier, shutdown
 from multidisttorch_amd.runtime.faults import create_health_groups
 
 
@@ -63,6 +63,9 @@ def parse_args(argv=None):
     parser.add_argument("--free-bits", type=str, default=None,
                         help="free bits: a floor in nats under each latent dimension's KL term of each sample "
                              "(training objective only; 0 = off), comma list per trial")
+    parser.add_argument("--tc-weight", type=str, default=None,
+                        help="weight of the minibatch total-correlation penalty in the training objective "
+                             "(--beta 1 --tc-weight b-1 is beta-TCVAE; 0 = off), comma list per trial")
     parser.add_argument("--seed", type=int, default=0, help="base seed (trial g uses seed+g)")
     parser.add_argument("--no-epoch-offset", action="store_true", help="all trials train --epochs epochs")
     parser.add_argument("--log-interval", type=int, default=10)
@@ -138,7 +141,7 @@ def main(argv=None):
                         lr_decays=parse_list(args.lr_decay, lambda s: s.strip()),
                         lr_decay_steps=parse_list(args.lr_decay_steps, int),
                         lr_min_ratios=parse_list(args.lr_min_ratio), kl_anneals=parse_list(args.kl_anneal, int),
-                        free_bits=args.free_bits)
+                        free_bits=args.free_bits, tc_weight=args.tc_weight)
     opts = RunOptions(batch_size=args.batch_size, log_interval=args.log_interval,
                       backend=args.backend, use_graphs=not args.no_graphs, graph_steps=args.graph_steps,
                       ckpt_dir=args.ckpt_dir, resume=args.resume, metrics_dir=args.metrics_dir,
@@ -149,7 +152,8 @@ def main(argv=None):
                       model=args.model, image_size=args.image_size, bucket_mb=parse_bucket_mb(args.bucket_mb),
                       profile=args.profile, iw_samples=max(0, args.iw_samples), latent_report=args.latent_report,
                       au_threshold=args.au_threshold, binarize=args.binarize,
-                      report_free_bits=any(s.free_bits > 0 for s in specs))
+                      report_free_bits=any(s.free_bits > 0 for s in specs),
+                      report_tc=any(s.tc_weight > 0 for s in specs))
     results = []
     member = False
     for group_id, group in enumerate(processes_groups):
@@ -194,6 +198,9 @@ def main(argv=None):
         if opts.report_free_bits:
             # the KL floor (nats) of every trial's training objective; test scores are the true ELBO terms
             summary["free_bits"] = {str(s.group_id): s.free_bits for s in specs}
+        if opts.report_tc:
+            # the weight of every trial's total-correlation penalty; test scores are the true ELBO terms
+            summary["tc_weight"] = {str(s.group_id): s.tc_weight for s in specs}
         if opts.iw_samples > 0:
             # per-image means over the test set; the lowest bound on -log p(x) is the best trial
             summary["iw_samples"] = opts.iw_samples
@@ -211,7 +218,10 @@ def main(argv=None):
             with open(os.path.join(args.metrics_dir, "aggregate.json"), "w") as f:
                 json.dump(summary, f)
         print("MDT_AGGREGATE " + json.dumps(summary), flush=True)
-    dist.destroy_process_group()
+    # control-plane barrier, then teardown: no rank (an idle leftover one least of all) takes its process
+    # groups down while a peer still talks to it -- the gloo teardown race of docs/ROUND6.md, "Teardown"
+    global_barrier()
+    shutdown()
 
 
 if __name__ == "__main__":
