@@ -20,6 +20,7 @@ void bind_iw(pybind11::module& m);
 void bind_latent(pybind11::module& m);
 void bind_data(pybind11::module& m);
 void bind_tc(pybind11::module& m);
+void bind_ema(pybind11::module& m);
 }  // namespace mdt
 
 PYBIND11_MODULE(_C, m) {
@@ -38,6 +39,7 @@ PYBIND11_MODULE(_C, m) {
   mdt::bind_latent(m);
   mdt::bind_data(m);
   mdt::bind_tc(m);
+  mdt::bind_ema(m);
 
   // the trial-state owner of both trainers (runtime/trial_state.h); kLossHist: the length of its loss rings
   m.attr("kLossHist") = (int64_t)mdt::kLossHist;
@@ -47,7 +49,8 @@ PYBIND11_MODULE(_C, m) {
            py::arg("eps"), py::arg("weight_decay"), py::arg("kl_beta"), py::arg("grad_scale"), py::arg("seed"),
            py::arg("decoupled_wd"), py::arg("lr_warmup_steps") = 0, py::arg("lr_decay") = 0,
            py::arg("lr_decay_steps") = 0, py::arg("lr_min_ratio") = 0.0, py::arg("kl_anneal_steps") = 0,
-           py::arg("free_bits") = 0.0, py::arg("tc_weight") = 0.0)
+           py::arg("free_bits") = 0.0, py::arg("tc_weight") = 0.0,
+           py::arg("ema_decay") = 0.0)
       .def("set_cursor", &mdt::TrialStateBuf::set_cursor)
       .def("set_step", &mdt::TrialStateBuf::set_step)
       .def("reset_loss", &mdt::TrialStateBuf::reset_loss)

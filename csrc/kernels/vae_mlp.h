@@ -67,6 +67,9 @@ struct HParams {
   float free_bits;
   // total-correlation penalty: weight of tc_batch in the objective (0 = off), ramped like the KL weight
   float tc_weight;
+  // weight averaging (ema.hip): the decay of the parameter average, 0 = off; last, so every earlier
+  // field keeps its offset
+  double ema_decay;
 };
 
 constexpr int kLrDecayNone = 0, kLrDecayCosine = 1;

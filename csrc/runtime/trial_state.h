@@ -67,7 +67,9 @@ class TrialStateBuf {
   void set_hparams(double lr, double b1, double b2, double eps, double wd, double kl_beta, double gs, int64_t seed,
                    bool decoupled, int64_t lr_warmup = 0, int64_t lr_decay = 0, int64_t lr_decay_steps = 0,
                    double lr_min_ratio = 0.0, int64_t kl_anneal = 0, double free_bits = 0.0,
-                   double tc_weight = 0.0) {
+                   double tc_weight = 0.0, double ema_decay = 0.0) {
+    TORCH_CHECK_VALUE(std::isfinite(ema_decay) && ema_decay >= 0.0 && ema_decay < 1.0,
+                      "ema_decay must be in [0, 1), got ", ema_decay);
     TORCH_CHECK_VALUE(std::isfinite(free_bits) && free_bits >= 0.0, "free_bits must be finite and >= 0, got ", free_bits);
     TORCH_CHECK_VALUE(std::isfinite(tc_weight) && tc_weight >= 0.0, "tc_weight must be finite and >= 0, got ", tc_weight);
     HParams h;
@@ -79,6 +81,7 @@ class TrialStateBuf {
     sched_fill(h, kl_beta, lr_warmup, lr_decay, lr_decay_steps, lr_min_ratio, kl_anneal);
     h.free_bits = (float)free_bits;
     h.tc_weight = (float)tc_weight;
+    h.ema_decay = ema_decay;
     hp_ = h;
     const bool changed = b1 != b1_ || b2 != b2_;
     b1_ = b1; b2_ = b2;

@@ -8,7 +8,8 @@ Layout (beside the reference's ``results-{group_rank}/`` images):
 Each file holds only tensors and plain Python scalars/strings, so it loads
 with ``torch.load(weights_only=True)`` (never unpickles code):
   model        state_dict under the reference's parameter names (fc1.weight, ...)
-  optimizer    {"step", "exp_avg", "exp_avg_sq"} flat arenas (layout recorded)
+  optimizer    {"step", "exp_avg", "exp_avg_sq"} flat arenas (layout recorded), and
+               "ema", the weight average, of a trainer that keeps one
   trial        TrialSpec fields (group_id, epochs, lr, beta, seed, and the
                lr / KL-weight schedule fields as given)
   schedule     the trainer's resolved Schedule (hpo/schedule.py) or None; a
@@ -24,7 +25,9 @@ with ``torch.load(weights_only=True)`` (never unpickles code):
                the trial trains under (data/binarize.py). ``load_latest`` returns
                it (absent = none); the runner refuses a resume under another one
   objective    {"free_bits": the trainer's KL floor in nats per latent element,
-               "tc_weight": the weight of its total-correlation penalty, when > 0}:
+               "tc_weight": the weight of its total-correlation penalty, when > 0,
+               "ema_decay": the decay of its weight average, when > 0 (the average
+               itself is ``optimizer.ema``)}:
                returned by ``load_latest`` (absent = 0) and checked by the runner
                in the same way
 Only group rank 0 writes (replicas are identical after the all-reduce);
@@ -67,6 +70,10 @@ def save_trial(ckpt_dir: str, trainer, spec, epoch: int, extra: Optional[dict] =
     }
     if float(trainer.hp.get("tc_weight", 0.0)) > 0:  # recorded only where it is in force (absent = 0)
         payload["objective"]["tc_weight"] = float(trainer.hp["tc_weight"])
+    if float(trainer.hp.get("ema_decay", 0.0)) > 0:
+        payload["objective"]["ema_decay"] = float(trainer.hp["ema_decay"])
+    if opt.get("ema") is not None:
+        payload["optimizer"]["ema"] = opt["ema"]
     if extra:
         payload["extra"] = extra
     name = f"epoch-{epoch}.pt"
@@ -114,4 +121,5 @@ def load_latest(ckpt_dir: str, group_id: int, trainer) -> Optional[dict]:
     trainer.load_optimizer_state(ck["optimizer"])  # sets the step: the schedule continues from it
     return dict(ck["progress"], path=path, trial=ck["trial"], binarize=(ck.get("data") or {}).get("binarize", "none"),
                 free_bits=float((ck.get("objective") or {}).get("free_bits", 0.0)),
-                tc_weight=float((ck.get("objective") or {}).get("tc_weight", 0.0)))
+                tc_weight=float((ck.get("objective") or {}).get("tc_weight", 0.0)),
+                ema_decay=float((ck.get("objective") or {}).get("ema_decay", 0.0)))

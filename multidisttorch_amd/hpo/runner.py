@@ -80,6 +80,7 @@ class RunOptions:
     binarize: str = "none"                 # none | threshold | static | dynamic (data/binarize.py); one value per run
     report_free_bits: bool = False         # some trial of the run sets --free-bits: the metrics carry every trial's value
     report_tc: bool = False                # some trial sets --tc-weight: the metrics carry train_tc and tc_weight
+    report_ema: bool = False               # some trial sets --ema-decay: the metrics carry every trial's decay
 
 
 @dataclass
@@ -131,7 +132,7 @@ def _make_trainer(spec: TrialSpec, opts: RunOptions, device, group_rank: int, D:
         return MlpVaeTrainer(batch_size=opts.batch_size, D=D, device=device, backend=opts.backend,
                              seed=spec.seed, lr=spec.lr, kl_beta=spec.beta, rng_stream=group_rank,
                              use_graphs=opts.use_graphs, graph_steps=opts.graph_steps, schedule=sched,
-                             free_bits=spec.free_bits, tc_weight=spec.tc_weight)
+                             free_bits=spec.free_bits, tc_weight=spec.tc_weight, ema_decay=spec.ema_decay)
     if opts.model == "conv":
         from ..models.conv_vae import ConvVaeTrainer
 
@@ -139,7 +140,7 @@ def _make_trainer(spec: TrialSpec, opts: RunOptions, device, group_rank: int, D:
                               z=32 if opts.image_size == 28 else 64, device=device, backend=opts.backend,
                               seed=spec.seed, lr=spec.lr, kl_beta=spec.beta, rng_stream=group_rank,
                               use_graphs=opts.use_graphs, graph_steps=opts.graph_steps, schedule=sched,
-                              free_bits=spec.free_bits, tc_weight=spec.tc_weight)
+                              free_bits=spec.free_bits, tc_weight=spec.tc_weight, ema_decay=spec.ema_decay)
     raise ValueError(f"unknown model {opts.model!r}")
 
 
@@ -186,6 +187,24 @@ def _check_resumed_tc_weight(prog, spec: TrialSpec):
     if prog is not None and float(prog.get("tc_weight", 0.0)) != float(spec.tc_weight):
         raise ValueError(f"trial {spec.group_id}: checkpoint {prog['path']} was trained with --tc-weight "
                          f"{prog.get('tc_weight', 0.0)}, this run asks for --tc-weight {spec.tc_weight}")
+
+
+def _check_resumed_ema_decay(prog, spec: TrialSpec):
+    """... and the decay of its weight average (an old checkpoint without the
+    record kept none)."""
+    if prog is not None and float(prog.get("ema_decay", 0.0)) != float(spec.ema_decay):
+        raise ValueError(f"trial {spec.group_id}: checkpoint {prog['path']} was trained with --ema-decay "
+                         f"{prog.get('ema_decay', 0.0)}, this run asks for --ema-decay {spec.ema_decay}")
+
+
+def _raw_test_loss(trainer, test, device) -> float:
+    """Untimed, after a trial's last epoch: one test pass under the raw weights
+    of a trial whose scores are under the averaged ones (``test_loss_raw`` in
+    the aggregate: what averaging bought). Prints nothing."""
+    idx = torch.arange(len(test), dtype=torch.int32, device=test.data.device)
+    with trace.range("raw_test_eval"):
+        total, _ = trainer.evaluate(test.data, idx, want_first_recon=False)
+    return total / len(test)
 
 
 def _refresh_train(binarizer, trainer, epoch: int, opts: RunOptions, device):
@@ -390,7 +409,8 @@ def _train_epoch(trainer, epoch: int, n_shard: int, n_dataset: int, opts: RunOpt
 def _test_epoch(trainer, epoch: int, test, opts: RunOptions, group, rdir: Optional[str], shape,
                 tag: str = "") -> float:
     idx = torch.arange(len(test), dtype=torch.int32, device=test.data.device)
-    with trace.range(f"test_epoch_{epoch}"):
+    # averaged_weights(): every score of a trial with --ema-decay is under its weight average (a no-op without)
+    with trace.range(f"test_epoch_{epoch}"), trainer.averaged_weights():
         total, first = trainer.evaluate(test.data, idx, want_first_recon=rdir is not None)
     if rdir is not None and first is not None:
         m = first.shape[0]
@@ -413,7 +433,7 @@ def _iw_eval(trainer, test, opts: RunOptions, group, metrics, device, tag: str =
     K = int(opts.iw_samples)
     t = time.perf_counter()
     idx = torch.arange(len(test), dtype=torch.int32, device=test.data.device)
-    with trace.range("iw_eval"):
+    with trace.range("iw_eval"), trainer.averaged_weights():
         r = trainer.evaluate_iw(test.data, idx, K)
         if device.type == "cuda":
             torch.cuda.synchronize(device)
@@ -433,7 +453,7 @@ def _latent_eval(trainer, test, opts: RunOptions, group, metrics, device, tag: s
     the IW pass it runs after the trial's wall time was taken."""
     t = time.perf_counter()
     idx = torch.arange(len(test), dtype=torch.int32, device=test.data.device)
-    with trace.range("latent_eval"):
+    with trace.range("latent_eval"), trainer.averaged_weights():
         r = trainer.evaluate_latent(test.data, idx, au_threshold=opts.au_threshold)
         if device.type == "cuda":
             torch.cuda.synchronize(device)
@@ -473,6 +493,7 @@ def run_trial(spec: TrialSpec, group, opts: RunOptions, data=None, num_trials: O
         # DDP's _sync_module_states: replicas start from group rank 0's weights
         broadcast_params([trainer.params], group)
         trainer.refresh_weights()
+        trainer.reset_average()  # the average starts as the weights every replica now holds
         if opts.bucket_mb == "auto":
             idx0 = shard_indices(len(train), n_rep, spec.group_id)
             key = f"{opts.model}-{opts.image_size}-b{opts.batch_size}-n{trainer.numel}-s{gsize}"
@@ -499,6 +520,7 @@ def run_trial(spec: TrialSpec, group, opts: RunOptions, data=None, num_trials: O
                 _check_resumed_binarize(prog, opts, spec.group_id)
                 _check_resumed_free_bits(prog, spec)
                 _check_resumed_tc_weight(prog, spec)
+                _check_resumed_ema_decay(prog, spec)
             except Exception as e:  # noqa: BLE001 - re-raised below on every member
                 err = e
         if prog is not None:
@@ -515,7 +537,8 @@ def run_trial(spec: TrialSpec, group, opts: RunOptions, data=None, num_trials: O
                     raise err
                 raise RuntimeError(f"trial {spec.group_id}: group rank 0 could not load its checkpoint; "
                                    f"stopping every member")
-            broadcast_params([trainer.params, trainer.exp_avg, trainer.exp_avg_sq], group)
+            broadcast_params([trainer.params, trainer.exp_avg, trainer.exp_avg_sq] +
+                             ([trainer.ema] if trainer.ema_on else []), group)
             start_epoch = int(meta[1].item())
             sched = _schedule_from_words([int(v) for v in meta[3:].tolist()])
             if sched is not None:
@@ -591,6 +614,10 @@ def run_trial(spec: TrialSpec, group, opts: RunOptions, data=None, num_trials: O
         with guarded(f"trial {spec.group_id} latent pass (world rank {world_rank})", None,
                      lambda e: failure.setdefault("error", f"{type(e).__name__}: {e}")):
             extra = dict(extra, **_latent_eval(trainer, test, opts, group, metrics, device))
+    if spec.ema_decay > 0 and not failure:
+        with guarded(f"trial {spec.group_id} raw-weight test pass (world rank {world_rank})", None,
+                     lambda e: failure.setdefault("error", f"{type(e).__name__}: {e}")):
+            extra = dict(extra, test_loss_raw=_raw_test_loss(trainer, test, device))
     return TrialResult(spec.group_id, epochs_done, n_shard, epochs_done * n_shard, t1 - t0,
                        train_loss / len(train), test_loss, failed=bool(failure), error=failure.get("error", ""),
                        extra=extra)
@@ -619,7 +646,7 @@ def _run_epoch(trainer, epoch, n_shard, train, test, opts, group, rdir, shape, g
         test_loss = _test_epoch(trainer, epoch, test, opts, group, rdir, shape, tag=tag)
     t = _mark("eval_s", t)
     if rdir is not None:
-        with torch.no_grad(), trace.range(f"sample_{epoch}"):
+        with torch.no_grad(), trace.range(f"sample_{epoch}"), trainer.averaged_weights():
             sample = torch.randn(64, trainer.Z, generator=gen).to(device)
             sample = trainer.decode(sample).cpu()
             os.makedirs(rdir, exist_ok=True)
@@ -640,6 +667,7 @@ def _run_epoch(trainer, epoch, n_shard, train, test, opts, group, rdir, shape, g
                 # tc_weight: the effective weight of the epoch's last step
                 **({"train_tc": st["epoch_tc"] / max(n_shard, 1), "tc_weight": st["tc_weight"]}
                    if opts.report_tc else {}),
+                **({"ema_decay": spec.ema_decay} if opts.report_ema else {}),
                 **phases)
     return train_loss, test_loss
 
@@ -681,6 +709,7 @@ def run_packed_trials(specs, group, opts: RunOptions, data=None, num_trials: Opt
             _check_resumed_binarize(prog, opts, spec.group_id)
             _check_resumed_free_bits(prog, spec)
             _check_resumed_tc_weight(prog, spec)
+            _check_resumed_ema_decay(prog, spec)
             if prog is not None:
                 start = prog["epoch"] + 1
         idx = shard_indices(len(train), total, spec.group_id)  # packing extension: one shard per trial
@@ -749,6 +778,10 @@ def run_packed_trials(specs, group, opts: RunOptions, data=None, num_trials: Opt
                          lambda e, t=t: t["failure"].setdefault("error", f"{type(e).__name__}: {e}")):
                 t["extra"] = dict(t["extra"], **_latent_eval(t["trainer"], t["test"], opts, group, t["metrics"], device,
                                                              tag=f"(trial {t['spec'].group_id}) "))
+        if t["spec"].ema_decay > 0 and not t["failure"]:
+            with guarded(f"trial {t['spec'].group_id} raw-weight test pass (world rank {world_rank})", None,
+                         lambda e, t=t: t["failure"].setdefault("error", f"{type(e).__name__}: {e}")):
+                t["extra"] = dict(t["extra"], test_loss_raw=_raw_test_loss(t["trainer"], t["test"], device))
     return [TrialResult(t["spec"].group_id, t["done"], t["n_shard"], t["done"] * t["n_shard"], t1 - t0,
                         t["train_loss"] / len(train), t["test_loss"], failed=bool(t["failure"]),
                         error=t["failure"].get("error", ""), extra=t["extra"]) for t in tr]

@@ -35,6 +35,9 @@ class TrialSpec:
     free_bits: float = 0.0
     # total-correlation penalty: weight of the minibatch TC estimate in the objective, 0 = off (models/tc.py)
     tc_weight: float = 0.0
+    # weight averaging: decay of the parameter average every evaluation uses, in [0, 1), 0 = off
+    # (docs/KERNELS.md, "Weight averaging")
+    ema_decay: float = 0.0
 
     def to_dict(self):
         return asdict(self)
@@ -78,9 +81,11 @@ def build_specs(num_groups: int, epochs: int, lrs: Optional[Sequence[float]] = N
                 epoch_offset: bool = True, lr_warmups: Optional[Sequence[int]] = None,
                 lr_decays: Optional[Sequence[str]] = None, lr_decay_steps: Optional[Sequence[int]] = None,
                 lr_min_ratios: Optional[Sequence[float]] = None,
-                kl_anneals: Optional[Sequence[int]] = None, free_bits=None, tc_weight=None) -> List[TrialSpec]:
+                kl_anneals: Optional[Sequence[int]] = None, free_bits=None, tc_weight=None,
+                ema_decay=None) -> List[TrialSpec]:
     """Per-group specs. A single value broadcasts; a list is indexed by group (cycled).
-    ``free_bits``, ``tc_weight``: a scalar, a list or a comma list like ``--beta``; finite and >= 0."""
+    ``free_bits``, ``tc_weight``: a scalar, a list or a comma list like ``--beta``; finite and >= 0.
+    ``ema_decay``: the same forms; every value in [0, 1)."""
     def pick(vals, g, default):
         return vals[g % len(vals)] if vals else default
 
@@ -96,6 +101,10 @@ def build_specs(num_groups: int, epochs: int, lrs: Optional[Sequence[float]] = N
 
     free_bits = nonneg(free_bits, "free_bits")
     tc_weight = nonneg(tc_weight, "tc_weight")
+    ema_decay = nonneg(ema_decay, "ema_decay")
+    for v in ema_decay or []:
+        if not float(v) < 1.0:
+            raise ValueError(f"ema_decay must be in [0, 1), got {v}")
     out = []
     for g in range(num_groups):
         lr = lrs[g % len(lrs)] if lrs else 1e-3
@@ -105,7 +114,7 @@ def build_specs(num_groups: int, epochs: int, lrs: Optional[Sequence[float]] = N
                          lr_decay_steps=int(pick(lr_decay_steps, g, 0)),
                          lr_min_ratio=float(pick(lr_min_ratios, g, 0.0)),
                          kl_anneal_steps=int(pick(kl_anneals, g, 0)), free_bits=float(pick(free_bits, g, 0.0)),
-                         tc_weight=float(pick(tc_weight, g, 0.0)))
+                         tc_weight=float(pick(tc_weight, g, 0.0)), ema_decay=float(pick(ema_decay, g, 0.0)))
         # bad values fail here, not in the middle of a run (T = 0 under cosine is resolved by the runner)
         spec.schedule(total_steps=spec.lr_warmup_steps + 1 if spec.lr_decay_steps == 0 else None)
         out.append(spec)

@@ -230,10 +230,11 @@ class ConvVaeTrainer(VaeTrainerBase):
                  backend: Optional[str] = None, seed: int = 0, lr: float = 1e-3, kl_beta: float = 1.0,
                  betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0, decoupled_wd: bool = False,
                  rng_stream: int = 0, use_graphs: bool = True, graph_steps: int = 10, init_seed: Optional[int] = None,
-                 schedule: Optional[Schedule] = None, free_bits: float = 0.0, tc_weight: float = 0.0):
+                 schedule: Optional[Schedule] = None, free_bits: float = 0.0, tc_weight: float = 0.0,
+                 ema_decay: float = 0.0):
         z = check_latent_size(z)
         super().__init__(batch_size, device, backend, seed, rng_stream, lr, kl_beta, betas, eps, weight_decay,
-                         decoupled_wd, use_graphs, graph_steps, schedule, free_bits, tc_weight)
+                         decoupled_wd, use_graphs, graph_steps, schedule, free_bits, tc_weight, ema_decay)
         backend = self.backend
         self.image, self.channels, self.Z = image, channels, z
         self.D = image * image * channels
@@ -318,6 +319,7 @@ class ConvVaeTrainer(VaeTrainerBase):
             self.C = native.require()
             self.state = self.C.TrialState(self.device.index or 0)
             self._alloc_hip()
+        self._ema_alloc()
         self._push_hparams()
 
     # ----------------------------------------------------------- arenas
@@ -454,8 +456,24 @@ class ConvVaeTrainer(VaeTrainerBase):
         step (replica broadcast, checkpoint load)."""
         if self.backend == "hip":
             self._cast_weights()
+            self._wt_stale = False  # the cast is followed by every layer's transposed copy
         else:
             self.model.from_arena(self.named_parameters())
+
+    def _refresh_swapped(self):
+        """``averaged_weights()`` exchanged params and ema: ``refresh_weights()``
+        with the transposed copies a step keeps current (layers 1 .., as
+        ``_wtrans_layers`` in the step; the first layer's copy is never read and
+        stays as it was), so that after the context ``w16`` and ``w16t`` are
+        bitwise what they were before it."""
+        if self.backend != "hip":
+            self.refresh_weights()
+            return
+        h = self.state
+        self.C.adam_cast(self.params, self.grads, self.exp_avg, self.exp_avg_sq, self.w16, self.segs, self.nseg,
+                         h.train_state, h.hparams, False)
+        self._wtrans_layers(1, len(self.spec))
+        self._wt_stale = False
 
     # ----------------------------------------------------------- HIP path
     def _alloc_hip(self):
@@ -1065,6 +1083,12 @@ class ConvVaeTrainer(VaeTrainerBase):
         red.launch(k)
 
     def _step_hip(self, M):
+        # weight averaging: ema_update is the last launch of every step form -- the layer path's
+        # optimizer tail, the fused 28x28 step's finalize, adam_cast after a reducer, both comm-job tails
+        self._step_hip_raw(M)
+        self._ema_step_hip()
+
+    def _step_hip_raw(self, M):
         if self.f28:
             self._step28(M)
             return
@@ -1365,6 +1389,7 @@ class ConvVaeTrainer(VaeTrainerBase):
             reference_adam_(self.params, self.grads, self.exp_avg, self.exp_avg_sq, st["step"] + 1, lr_t,
                             h["beta1"], h["beta2"], h["eps"], h["weight_decay"], h["grad_scale"], self.decoupled_wd)
             self.model.from_arena(self.named_parameters())
+            self._ema_step_torch(st["step"] + 1)
         self._record(float(loss.detach()), tc=tc)
 
     # ----------------------------------------------------------- driver API

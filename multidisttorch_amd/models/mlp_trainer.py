@@ -40,9 +40,9 @@ class MlpVaeTrainer(VaeTrainerBase):
                  lr: float = 1e-3, kl_beta: float = 1.0, betas=(0.9, 0.999), eps: float = 1e-8,
                  weight_decay: float = 0.0, decoupled_wd: bool = False, rng_stream: int = 0,
                  use_graphs: bool = True, graph_steps: int = 10, schedule: Optional[Schedule] = None,
-                 free_bits: float = 0.0, tc_weight: float = 0.0):
+                 free_bits: float = 0.0, tc_weight: float = 0.0, ema_decay: float = 0.0):
         super().__init__(batch_size, device, backend, seed, rng_stream, lr, kl_beta, betas, eps, weight_decay,
-                         decoupled_wd, use_graphs, graph_steps, schedule, free_bits, tc_weight)
+                         decoupled_wd, use_graphs, graph_steps, schedule, free_bits, tc_weight, ema_decay)
         self.D, self.H, self.Z = D, H, Z
         self.layout, self.numel, self.split = arena_layout(D, H, Z)
         if self.backend == "hip":
@@ -66,6 +66,7 @@ class MlpVaeTrainer(VaeTrainerBase):
         host = torch.zeros(self.numel, dtype=torch.float32)
         init_params_(host, self.layout, g)
         self.params.copy_(host)
+        self._ema_alloc()
         self._push_hparams()
 
     def bucket_bounds(self, bucket_mb=None):
@@ -91,6 +92,10 @@ class MlpVaeTrainer(VaeTrainerBase):
         return overlap_pays(4 * (self.numel - self.split), self.SPLIT_COST_US[fam])
 
     def _step_hip(self, M: int):
+        self._step_hip_raw(M)
+        self._ema_step_hip()  # weight averaging: the last launch of the step, after either Adam form
+
+    def _step_hip_raw(self, M: int):
         X, idx = self._data[0], self._data[1]
         e = self.engine
         e.forward(X, idx, M, True, False, self.rng_stream, False)
@@ -169,6 +174,7 @@ class MlpVaeTrainer(VaeTrainerBase):
                             lr_t, h["beta1"], h["beta2"], h["eps"], h["weight_decay"], h["grad_scale"],
                             self.decoupled_wd)
             loss = float(f["loss"])
+        self._ema_step_torch(st["step"] + 1)
         self._record(loss, tc=float(f["tc_batch"]) if cpu is None and self.tc_on else 0.0)
 
     def model_meta(self) -> dict:

@@ -17,6 +17,7 @@ A subclass sets ``B``, ``Z``, ``layout``, ``numel``, the arenas and (hip)
 
 from __future__ import annotations
 
+import contextlib
 import math
 import os
 from typing import Dict, Optional
@@ -31,7 +32,7 @@ from .eval_graphs import GraphedEval, GraphedIwEval, GraphedLatentEval, capture_
 from .mlp_vae import views
 from .tc import check_tc_weight
 
-__all__ = ["VaeTrainerBase", "LOSS_HIST", "EVAL_STREAM", "check_free_bits"]
+__all__ = ["VaeTrainerBase", "LOSS_HIST", "EVAL_STREAM", "check_free_bits", "check_ema_decay", "ema_omd"]
 
 EVAL_STREAM = 1 << 30
 LOSS_HIST = 4096  # per-step loss ring of a trial state (kLossHist, csrc/kernels/vae_mlp.h)
@@ -45,10 +46,26 @@ def check_free_bits(v) -> float:
     return v
 
 
+def check_ema_decay(v) -> float:
+    """The decay of the weight average: in [0, 1), 0 = off."""
+    v = float(v)
+    if not (math.isfinite(v) and 0.0 <= v < 1.0):
+        raise ValueError(f"ema_decay must be in [0, 1), got {v}")
+    return v
+
+
+def ema_omd(decay: float, t: int) -> float:
+    """1 - d_t of optimizer step t (1-based) as the float32 every element is
+    multiplied by, d_t = min(decay, (1 + t) / (10 + t)) in double
+    (csrc/kernels/ema.h::ema_omd; docs/KERNELS.md, "Weight averaging")."""
+    return float(np.float32(1.0 - min(float(decay), (1.0 + t) / (10.0 + t))))
+
+
 class VaeTrainerBase(GraphedEval, GraphedIwEval, GraphedLatentEval):
     def __init__(self, batch_size: int, device, backend: Optional[str], seed: int, rng_stream: int, lr: float,
                  kl_beta: float, betas, eps: float, weight_decay: float, decoupled_wd: bool, use_graphs: bool,
-                 graph_steps: int, schedule: Optional[Schedule], free_bits: float = 0.0, tc_weight: float = 0.0):
+                 graph_steps: int, schedule: Optional[Schedule], free_bits: float = 0.0, tc_weight: float = 0.0,
+                 ema_decay: float = 0.0):
         self.B = batch_size
         # lr warm-up / cosine decay and KL annealing (hpo/schedule.py); None = off.
         # On the hip backend the kernels evaluate it from the device step counter.
@@ -63,11 +80,17 @@ class VaeTrainerBase(GraphedEval, GraphedIwEval, GraphedLatentEval):
         self.seed, self.rng_stream = int(seed), int(rng_stream)
         self.hp = dict(lr=lr, beta1=betas[0], beta2=betas[1], eps=eps, weight_decay=weight_decay,
                        kl_beta=kl_beta, grad_scale=1.0, free_bits=check_free_bits(free_bits),
-                       tc_weight=check_tc_weight(tc_weight))
+                       tc_weight=check_tc_weight(tc_weight), ema_decay=check_ema_decay(ema_decay))
         # total-correlation penalty (models/tc.py): a trainer built with it launches the penalty's
         # kernels in every training step (a weight of 0 then only zeroes their result); one built
         # without cannot be given a weight later -- its launch list has no such kernels
         self.tc_on = self.hp["tc_weight"] > 0
+        # weight averaging (docs/KERNELS.md, "Weight averaging"): a trainer built with a decay keeps
+        # ``self.ema``, a second parameter arena, and ends every training step with its update; one
+        # built without cannot be given a decay later -- its launch list has no such launch
+        self.ema_on = self.hp["ema_decay"] > 0
+        self.ema = None
+        self._averaged = False  # inside ``averaged_weights()``: params and ema are exchanged
         self.decoupled_wd = decoupled_wd
         self.use_graphs = use_graphs and backend == "hip"
         self.graph_steps = max(1, int(graph_steps))
@@ -103,9 +126,11 @@ class VaeTrainerBase(GraphedEval, GraphedIwEval, GraphedLatentEval):
 
     @torch.no_grad()
     def load_state_dict(self, sd: Dict[str, torch.Tensor]):
+        self._not_averaged("load_state_dict")
         for k, t in self.named_parameters().items():
             t.copy_(sd[k].to(t.device, torch.float32))
         self.refresh_weights()
+        self.reset_average()
 
     def refresh_weights(self):
         """Re-derive the compute copies of the weights after ``params`` changed
@@ -113,20 +138,124 @@ class VaeTrainerBase(GraphedEval, GraphedIwEval, GraphedLatentEval):
         where the params are the compute weights."""
 
     def optimizer_state(self) -> dict:
-        return {"step": self.step_count, "exp_avg": self.exp_avg.detach().cpu().clone(),
-                "exp_avg_sq": self.exp_avg_sq.detach().cpu().clone()}
+        self._not_averaged("optimizer_state")
+        st = {"step": self.step_count, "exp_avg": self.exp_avg.detach().cpu().clone(),
+              "exp_avg_sq": self.exp_avg_sq.detach().cpu().clone()}
+        if self.ema_on:
+            st["ema"] = self.ema.detach().cpu().clone()
+        return st
 
     @torch.no_grad()
     def load_optimizer_state(self, st: dict):
+        """Adam moments, the step and, when ``ema_on``, the weight average; a
+        state without one (a checkpoint of a run without averaging) sets the
+        average to the parameters as they are now."""
+        self._not_averaged("load_optimizer_state")
         self.exp_avg.copy_(st["exp_avg"])
         self.exp_avg_sq.copy_(st["exp_avg_sq"])
         self.set_step(int(st["step"]))
+        if self.ema_on:
+            if st.get("ema") is not None:
+                self.ema.copy_(st["ema"])
+            else:
+                self.reset_average()
+
+    # ------------------------------------------------------------------ weight averaging
+    def _ema_alloc(self):
+        """End of a subclass's construction (arenas exist, params initialised):
+        the average starts as the parameters."""
+        if self.ema_on:
+            self.ema = self.params.detach().clone()
+
+    @torch.no_grad()
+    def reset_average(self):
+        """e = p: the parameters were set from outside a step (construction,
+        ``load_state_dict``, the replica broadcast)."""
+        if self.ema_on and self.ema is not None:
+            self._not_averaged("reset_average")
+            self.ema.copy_(self.params)
+
+    def _not_averaged(self, what: str):
+        if self._averaged:
+            raise RuntimeError(f"{what} inside averaged_weights(): the parameter arena holds the average")
+
+    def ema_state_dict(self) -> Dict[str, torch.Tensor]:
+        """The averaged weights under the reference's parameter names (cpu
+        copies); the raw weights of a trainer without averaging."""
+        self._not_averaged("ema_state_dict")
+        src = self.ema if self.ema_on else self.params
+        return {k: v.detach().cpu().clone() for k, v in views(src, self.layout).items()}
+
+    @torch.no_grad()
+    def load_ema_state_dict(self, sd: Dict[str, torch.Tensor]):
+        if not self.ema_on:
+            raise ValueError("load_ema_state_dict needs a trainer built with ema_decay > 0")
+        self._not_averaged("load_ema_state_dict")
+        for k, t in views(self.ema, self.layout).items():
+            t.copy_(sd[k].to(t.device, torch.float32))
+
+    def _ema_step_hip(self):
+        """Last launch of every hip training step of an ``ema_on`` trainer
+        (csrc/kernels/ema.hip): the step's optimizer tail has advanced the step
+        and written the parameters."""
+        if self.ema_on:
+            native.require().ema_update(self.ema, self.params, self.numel, state=self.state.train_state,
+                                        hparams=self.state.hparams)
+
+    @torch.no_grad()
+    def _ema_step_torch(self, t: int):
+        """torch backends: the same rule after Adam of optimizer step t, one
+        multiply-add per element on the float32 difference ``p - e``. The
+        product is exact in float64, so the sum is rounded there and once more
+        to float32; ``e == p`` stays a bitwise fixed point."""
+        if self.ema_on:
+            omd = ema_omd(self.hp["ema_decay"], t)
+            d = (self.params - self.ema).double()
+            self.ema.copy_((self.ema.double() + omd * d).float())
+
+    def _swap_average(self):
+        if self.backend == "hip":
+            native.require().arena_swap(self.params, self.ema, self.numel)
+        else:
+            tmp = self.params.clone()
+            self.params.copy_(self.ema)
+            self.ema.copy_(tmp)
+        self._refresh_swapped()
+
+    def _refresh_swapped(self):
+        """The compute copies after ``params`` and ``ema`` were exchanged."""
+        self.refresh_weights()
+
+    @contextlib.contextmanager
+    def averaged_weights(self):
+        """Every compute copy of the weights is the averaged one inside the
+        block and the raw one again after it: the two arenas are exchanged in
+        place (``arena_swap``) and the derived copies refreshed, so no pointer
+        changes and captured eval / IW / latent graphs stay valid. No-op
+        without ``ema_on``. Nesting raises, and so does training inside."""
+        if self._averaged:
+            raise RuntimeError("averaged_weights() does not nest")
+        if not self.ema_on:
+            yield self
+            return
+        self._swap_average()
+        self._averaged = True
+        try:
+            yield self
+        finally:
+            self._averaged = False
+            self._swap_average()
 
     # ------------------------------------------------------------------ hparams
     def set_hparams(self, **kw):
         for k, v in kw.items():
             if k not in self.hp:
                 raise KeyError(k)
+            if k == "ema_decay":
+                v = check_ema_decay(v)
+                if v > 0 and not self.ema_on:
+                    raise ValueError("ema_decay > 0 needs a trainer built with ema_decay > 0 "
+                                     "(the step's launch list differs)")
             if k == "tc_weight":
                 v = check_tc_weight(v)
                 if v > 0 and not self.tc_on:
@@ -147,7 +276,7 @@ class VaeTrainerBase(GraphedEval, GraphedIwEval, GraphedLatentEval):
             self.state.set_hparams(h["lr"], h["beta1"], h["beta2"], h["eps"], h["weight_decay"], h["kl_beta"],
                                    h["grad_scale"], self.seed, self.decoupled_wd,
                                    **(self.schedule or Schedule()).native_args(), free_bits=h["free_bits"],
-                                   tc_weight=h["tc_weight"])
+                                   tc_weight=h["tc_weight"], ema_decay=h["ema_decay"])
 
     def _effective(self, t: int):
         """(lr_t, beta_t) of optimizer step t on the torch backend, as doubles:
@@ -290,6 +419,7 @@ class VaeTrainerBase(GraphedEval, GraphedIwEval, GraphedLatentEval):
         M = self.B if M is None else M
         if n <= 0:
             return
+        self._not_averaged("train_steps")
         if self.backend == "torch":
             for _ in range(n):
                 self._step_torch(M)
@@ -342,8 +472,8 @@ class VaeTrainerBase(GraphedEval, GraphedIwEval, GraphedLatentEval):
 
     def _capture(self, S: int, M: int):
         # the warm-up and captured launches advance the step counter / cursor / Adam moments
-        return capture_replayable((self.params, self.exp_avg, self.exp_avg_sq, self.state.train_state),
-                                  lambda: self._step_hip(M), S)
+        snap = (self.params, self.exp_avg, self.exp_avg_sq, self.state.train_state)
+        return capture_replayable(snap + ((self.ema,) if self.ema_on else ()), lambda: self._step_hip(M), S)
 
     # ------------------------------------------------------------------ eval
     def evaluate(self, X: torch.Tensor, idx: torch.Tensor, want_first_recon: bool = True):

@@ -66,6 +66,10 @@ def parse_args(argv=None):
     parser.add_argument("--tc-weight", type=str, default=None,
                         help="weight of the minibatch total-correlation penalty in the training objective "
                              "(--beta 1 --tc-weight b-1 is beta-TCVAE; 0 = off), comma list per trial")
+    parser.add_argument("--ema-decay", type=str, default=None,
+                        help="decay of an exponential moving average of the weights, in [0, 1); every evaluation "
+                             "(test loss, --iw-samples, --latent-report, samples) then uses the average "
+                             "(0 = off), comma list per trial")
     parser.add_argument("--seed", type=int, default=0, help="base seed (trial g uses seed+g)")
     parser.add_argument("--no-epoch-offset", action="store_true", help="all trials train --epochs epochs")
     parser.add_argument("--log-interval", type=int, default=10)
@@ -141,7 +145,7 @@ def main(argv=None):
                         lr_decays=parse_list(args.lr_decay, lambda s: s.strip()),
                         lr_decay_steps=parse_list(args.lr_decay_steps, int),
                         lr_min_ratios=parse_list(args.lr_min_ratio), kl_anneals=parse_list(args.kl_anneal, int),
-                        free_bits=args.free_bits, tc_weight=args.tc_weight)
+                        free_bits=args.free_bits, tc_weight=args.tc_weight, ema_decay=args.ema_decay)
     opts = RunOptions(batch_size=args.batch_size, log_interval=args.log_interval,
                       backend=args.backend, use_graphs=not args.no_graphs, graph_steps=args.graph_steps,
                       ckpt_dir=args.ckpt_dir, resume=args.resume, metrics_dir=args.metrics_dir,
@@ -153,7 +157,8 @@ def main(argv=None):
                       profile=args.profile, iw_samples=max(0, args.iw_samples), latent_report=args.latent_report,
                       au_threshold=args.au_threshold, binarize=args.binarize,
                       report_free_bits=any(s.free_bits > 0 for s in specs),
-                      report_tc=any(s.tc_weight > 0 for s in specs))
+                      report_tc=any(s.tc_weight > 0 for s in specs),
+                      report_ema=any(s.ema_decay > 0 for s in specs))
     results = []
     member = False
     for group_id, group in enumerate(processes_groups):
@@ -170,14 +175,19 @@ def main(argv=None):
     # aggregate samples/s: samples once per trial, max wall over ranks
     lat_keys = ("kl", "active_units", "mi", "tc", "dwkl")
     mine = [(r.group_id, r.samples, r.wall_s, r.failed) + ((r.extra.get("iw_nll"),) if opts.iw_samples > 0 else ()) +
-            ((r.extra.get("latent"),) if opts.latent_report else ())
+            ((r.extra.get("latent"),) if opts.latent_report else ()) +
+            ((r.extra.get("test_loss_raw"),) if opts.report_ema else ())
             for r in results]
     gathered = [None] * dist.get_world_size()
     dist.all_gather_object(gathered, mine, group=control_group())
     if dist.get_rank() == 0:
-        per_trial, wall, failed, iw_nll, latent = {}, 0.0, set(), {}, {}
+        per_trial, wall, failed, iw_nll, latent, raw = {}, 0.0, set(), {}, {}, {}
         for lst in gathered:
             for gid, samples, w, bad, *more in lst or []:
+                if opts.report_ema:
+                    v = more.pop()
+                    if v is not None:
+                        raw[gid] = v
                 iw = more[:1] if opts.iw_samples > 0 else []
                 lat = more[-1] if opts.latent_report else None
                 if iw and iw[0] is not None:
@@ -201,6 +211,11 @@ def main(argv=None):
         if opts.report_tc:
             # the weight of every trial's total-correlation penalty; test scores are the true ELBO terms
             summary["tc_weight"] = {str(s.group_id): s.tc_weight for s in specs}
+        if opts.report_ema:
+            # the decay of every trial's weight average; every score of a trial that sets one is under the
+            # averaged weights, and test_loss_raw is its last test loss under the raw ones (what averaging bought)
+            summary["ema_decay"] = {str(s.group_id): s.ema_decay for s in specs}
+            summary["test_loss_raw"] = {str(g): round(v, 4) for g, v in sorted(raw.items())}
         if opts.iw_samples > 0:
             # per-image means over the test set; the lowest bound on -log p(x) is the best trial
             summary["iw_samples"] = opts.iw_samples
