@@ -24,12 +24,10 @@ with ``torch.load(weights_only=True)`` (never unpickles code):
   data         {"binarize": none | threshold | static | dynamic}: the likelihood
                the trial trains under (data/binarize.py). ``load_latest`` returns
                it (absent = none); the runner refuses a resume under another one
-  objective    {"free_bits": the trainer's KL floor in nats per latent element,
-               "tc_weight": the weight of its total-correlation penalty, when > 0,
-               "ema_decay": the decay of its weight average, when > 0 (the average
-               itself is ``optimizer.ema``)}:
-               returned by ``load_latest`` (absent = 0) and checked by the runner
-               in the same way
+  objective    the trainer's knobs of hpo/objective.py by name: the KL floor always, the
+               penalty's weight and the decay of the weight average when > 0 (the average
+               itself is ``optimizer.ema``); returned by ``load_latest`` (absent = 0) and
+               checked by the runner in the same way
 Only group rank 0 writes (replicas are identical after the all-reduce);
 writes go to a temp file + atomic rename so a crash never leaves a torn file.
 """
@@ -40,6 +38,8 @@ import os
 from typing import Optional
 
 import torch
+
+from ..hpo.objective import KNOBS
 
 __all__ = ["trial_dir", "save_trial", "load_latest", "latest_path"]
 
@@ -66,12 +66,9 @@ def save_trial(ckpt_dir: str, trainer, spec, epoch: int, extra: Optional[dict] =
         "layout": [[n, int(o)] + [int(x) for x in s] for n, o, s in trainer.layout],
         "arch": trainer.model_meta(),
         "data": {"binarize": str(binarize)},
-        "objective": {"free_bits": float(trainer.hp.get("free_bits", 0.0))},
+        "objective": {k.name: float(trainer.hp.get(k.name, 0.0)) for k in KNOBS
+                      if k.always_saved or float(trainer.hp.get(k.name, 0.0)) > 0},
     }
-    if float(trainer.hp.get("tc_weight", 0.0)) > 0:  # recorded only where it is in force (absent = 0)
-        payload["objective"]["tc_weight"] = float(trainer.hp["tc_weight"])
-    if float(trainer.hp.get("ema_decay", 0.0)) > 0:
-        payload["objective"]["ema_decay"] = float(trainer.hp["ema_decay"])
     if opt.get("ema") is not None:
         payload["optimizer"]["ema"] = opt["ema"]
     if extra:
@@ -120,6 +117,4 @@ def load_latest(ckpt_dir: str, group_id: int, trainer) -> Optional[dict]:
         trainer.set_schedule(Schedule(**ck["schedule"]))
     trainer.load_optimizer_state(ck["optimizer"])  # sets the step: the schedule continues from it
     return dict(ck["progress"], path=path, trial=ck["trial"], binarize=(ck.get("data") or {}).get("binarize", "none"),
-                free_bits=float((ck.get("objective") or {}).get("free_bits", 0.0)),
-                tc_weight=float((ck.get("objective") or {}).get("tc_weight", 0.0)),
-                ema_decay=float((ck.get("objective") or {}).get("ema_decay", 0.0)))
+                **{k.name: float((ck.get("objective") or {}).get(k.name, 0.0)) for k in KNOBS})

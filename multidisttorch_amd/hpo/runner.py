@@ -46,6 +46,7 @@ from ..runtime.bootstrap import bound_device, global_barrier
 from ..runtime.faults import (InjectedFault, TrialCorrupted, TrialTimeout, agree_healthy, fault_step, group_timeout_s, guarded,
                               heartbeat_s, maybe_inject, trial_watch)
 from ..utils.images import flush_images, save_image_async
+from .objective import KNOBS, NAMES
 from .schedule import LR_DECAYS, Schedule
 from .trial import TrialSpec
 
@@ -78,9 +79,7 @@ class RunOptions:
     latent_report: bool = False            # active units + MI / TC / dimension-wise-KL split after the last epoch
     au_threshold: float = 0.01             # a dimension is active when Var_x(mu_d) exceeds this
     binarize: str = "none"                 # none | threshold | static | dynamic (data/binarize.py); one value per run
-    report_free_bits: bool = False         # some trial of the run sets --free-bits: the metrics carry every trial's value
-    report_tc: bool = False                # some trial sets --tc-weight: the metrics carry train_tc and tc_weight
-    report_ema: bool = False               # some trial sets --ema-decay: the metrics carry every trial's decay
+    report_objective: tuple = ()           # objective.reported(specs): knobs whose values the metrics carry
 
 
 @dataclass
@@ -126,21 +125,17 @@ def _make_trainer(spec: TrialSpec, opts: RunOptions, device, group_rank: int, D:
                   total_steps: Optional[int] = None):
     sched = spec.schedule(total_steps)
     sched = sched if sched.active else None
+    kw = dict(batch_size=opts.batch_size, device=device, backend=opts.backend, seed=spec.seed, lr=spec.lr,
+              kl_beta=spec.beta, rng_stream=group_rank, use_graphs=opts.use_graphs, graph_steps=opts.graph_steps,
+              schedule=sched, **spec.objective())
     if opts.model == "mlp":
         from ..models.mlp_trainer import MlpVaeTrainer
 
-        return MlpVaeTrainer(batch_size=opts.batch_size, D=D, device=device, backend=opts.backend,
-                             seed=spec.seed, lr=spec.lr, kl_beta=spec.beta, rng_stream=group_rank,
-                             use_graphs=opts.use_graphs, graph_steps=opts.graph_steps, schedule=sched,
-                             free_bits=spec.free_bits, tc_weight=spec.tc_weight, ema_decay=spec.ema_decay)
+        return MlpVaeTrainer(D=D, **kw)
     if opts.model == "conv":
         from ..models.conv_vae import ConvVaeTrainer
 
-        return ConvVaeTrainer(batch_size=opts.batch_size, image=opts.image_size,
-                              z=32 if opts.image_size == 28 else 64, device=device, backend=opts.backend,
-                              seed=spec.seed, lr=spec.lr, kl_beta=spec.beta, rng_stream=group_rank,
-                              use_graphs=opts.use_graphs, graph_steps=opts.graph_steps, schedule=sched,
-                              free_bits=spec.free_bits, tc_weight=spec.tc_weight, ema_decay=spec.ema_decay)
+        return ConvVaeTrainer(image=opts.image_size, z=32 if opts.image_size == 28 else 64, **kw)
     raise ValueError(f"unknown model {opts.model!r}")
 
 
@@ -154,57 +149,59 @@ def _load_data(opts: RunOptions, device):
     return train, test
 
 
-def _binarizers(spec: TrialSpec, opts: RunOptions, train, test, idx):
-    """``--binarize``: (train Binarizer over the trial's shard, the test set as
-    an ImageSet of its fixed binarized rows), or (None, test) when off. The
-    test rows are drawn here, once; the train rows at the top of every epoch
-    (``_refresh_train``). Every trial holds its own buffers."""
-    if opts.binarize == "none":
-        return None, test
-    bt = Binarizer(opts.binarize, spec.seed, test.data, torch.arange(len(test), dtype=torch.int32), 1)
-    bt.refresh(0)
-    return (Binarizer(opts.binarize, spec.seed, train.data, idx, 0),
-            ImageSet(bt.data, test.shape, test.synthetic, test.name))
+def _check_resumed(prog, spec: TrialSpec, opts: RunOptions):
+    """A resumed trial keeps the likelihood (``--binarize``) and the objective (every knob of
+    hpo/objective.py) it was trained under; an old checkpoint without the record: none, and 0."""
+    asked = [("--binarize", "binarize", "none", opts.binarize)]
+    asked += [(k.flag, k.name, 0.0, getattr(spec, k.name)) for k in KNOBS]
+    for flag, key, default, want in asked if prog is not None else []:
+        had = prog.get(key, default)
+        if had != want:
+            raise ValueError(f"trial {spec.group_id}: checkpoint {prog['path']} was trained with {flag} "
+                             f"{had}, this run asks for {flag} {want}")
 
 
-def _check_resumed_binarize(prog, opts: RunOptions, group_id: int):
-    if prog is not None and prog.get("binarize", "none") != opts.binarize:
-        raise ValueError(f"trial {group_id}: checkpoint {prog['path']} was trained with --binarize "
-                         f"{prog.get('binarize', 'none')}, this run asks for --binarize {opts.binarize}")
+def _resume(trainer, spec: TrialSpec, opts: RunOptions, group=None, announce: bool = False):
+    """``--resume``: the trial's newest checkpoint restored into ``trainer``, refused if it was
+    trained under something else -> (its progress record or None, the epoch to start from)."""
+    prog = ckpt.load_latest(opts.ckpt_dir, spec.group_id, trainer) if opts.ckpt_dir and opts.resume else None
+    if prog is None:
+        return None, 1
+    if announce:  # (run_trial: printed once the checkpoint is loaded, refused or not)
+        print0(f"resumed trial {spec.group_id} from {prog['path']} (epoch {prog['epoch']})", process_group=group)
+    _check_resumed(prog, spec, opts)
+    return prog, prog["epoch"] + 1
 
 
-def _check_resumed_free_bits(prog, spec: TrialSpec):
-    """A resumed trial keeps the objective it was trained under (an old
-    checkpoint without the record was trained without a floor)."""
-    if prog is not None and float(prog.get("free_bits", 0.0)) != float(spec.free_bits):
-        raise ValueError(f"trial {spec.group_id}: checkpoint {prog['path']} was trained with --free-bits "
-                         f"{prog.get('free_bits', 0.0)}, this run asks for --free-bits {spec.free_bits}")
+def _bind_data(trainer, spec: TrialSpec, opts: RunOptions, train, test, idx):
+    """Bind the trial's shard ``idx`` of the training rows and do the set-up that precedes the
+    timer -> (the shard's Binarizer or None, the test set every pass of the trial reads). With
+    ``--binarize`` the trainer reads the binarizer's compact buffer (redrawn in place at the top
+    of every epoch, ``_refresh_train``) and every test pass the binarized test rows, drawn here
+    once; every trial holds its own buffers."""
+    binarizer = None
+    if opts.binarize != "none":
+        bt = Binarizer(opts.binarize, spec.seed, test.data, torch.arange(len(test), dtype=torch.int32), 1)
+        bt.refresh(0)
+        test = ImageSet(bt.data, test.shape, test.synthetic, test.name)
+        binarizer = Binarizer(opts.binarize, spec.seed, train.data, idx, 0)
+        trainer.bind_train_data(binarizer.data, binarizer.index())
+    else:
+        trainer.bind_train_data(train.data, idx)
+    # capture the step graphs and the test-set eval graphs and load the decode kernels now, like the
+    # reference's model/DDP construction before its timer starts (vae-hpo.py:159)
+    trainer.prepare([opts.batch_size, idx.numel() % opts.batch_size], test.data if opts.eval_each_epoch else None)
+    return binarizer, test
 
 
-def _check_resumed_tc_weight(prog, spec: TrialSpec):
-    """... and the weight of its total-correlation penalty (an old checkpoint
-    without the record was trained without one)."""
-    if prog is not None and float(prog.get("tc_weight", 0.0)) != float(spec.tc_weight):
-        raise ValueError(f"trial {spec.group_id}: checkpoint {prog['path']} was trained with --tc-weight "
-                         f"{prog.get('tc_weight', 0.0)}, this run asks for --tc-weight {spec.tc_weight}")
-
-
-def _check_resumed_ema_decay(prog, spec: TrialSpec):
-    """... and the decay of its weight average (an old checkpoint without the
-    record kept none)."""
-    if prog is not None and float(prog.get("ema_decay", 0.0)) != float(spec.ema_decay):
-        raise ValueError(f"trial {spec.group_id}: checkpoint {prog['path']} was trained with --ema-decay "
-                         f"{prog.get('ema_decay', 0.0)}, this run asks for --ema-decay {spec.ema_decay}")
-
-
-def _raw_test_loss(trainer, test, device) -> float:
+def _raw_test_eval(trainer, test, opts: RunOptions, group, metrics, device, tag: str = "") -> dict:
     """Untimed, after a trial's last epoch: one test pass under the raw weights
     of a trial whose scores are under the averaged ones (``test_loss_raw`` in
-    the aggregate: what averaging bought). Prints nothing."""
+    the aggregate: what averaging bought). Prints and logs nothing."""
     idx = torch.arange(len(test), dtype=torch.int32, device=test.data.device)
     with trace.range("raw_test_eval"):
         total, _ = trainer.evaluate(test.data, idx, want_first_recon=False)
-    return total / len(test)
+    return dict(test_loss_raw=total / len(test))
 
 
 def _refresh_train(binarizer, trainer, epoch: int, opts: RunOptions, device):
@@ -470,6 +467,26 @@ def _latent_eval(trainer, test, opts: RunOptions, group, metrics, device, tag: s
     return dict(latent=r)
 
 
+# after a trial's last epoch and its wall time, in this order: (label, enabled(spec, opts), pass -> part of extra)
+_AFTER_TRIAL = (
+    ("IW pass", lambda spec, opts: opts.iw_samples > 0, _iw_eval),
+    ("latent pass", lambda spec, opts: opts.latent_report, _latent_eval),
+    ("raw-weight test pass", lambda spec, opts: spec.ema_decay > 0, _raw_test_eval),
+)
+
+
+def _after_trial(trainer, spec: TrialSpec, test, opts: RunOptions, group, metrics, device, failure: dict,
+                 world_rank: int, tag: str = "") -> dict:
+    """-> ``extra`` of a trial that has not failed; a pass that raises fails it and ends the list."""
+    extra = {}
+    for label, enabled, run in _AFTER_TRIAL:
+        if enabled(spec, opts) and not failure:
+            with guarded(f"trial {spec.group_id} {label} (world rank {world_rank})", None,
+                         lambda e: failure.setdefault("error", f"{type(e).__name__}: {e}")):
+                extra.update(run(trainer, test, opts, group, metrics, device, tag=tag))
+    return extra
+
+
 def run_trial(spec: TrialSpec, group, opts: RunOptions, data=None, num_trials: Optional[int] = None) -> TrialResult:
     """Train one trial on the ranks of ``group`` (this rank is a member)."""
     check_mode(opts.binarize)
@@ -487,7 +504,9 @@ def run_trial(spec: TrialSpec, group, opts: RunOptions, data=None, num_trials: O
         print(f"[mdt] trial {spec.group_id}: train data {train.name} ({'synthetic' if train.synthetic else 'IDX'}, "
               f"{len(train)} x {tuple(train.shape)})", file=sys.stderr, flush=True)
     D = int(train.data.shape[1])
-    total_steps = _total_steps(spec, opts, shard_indices(len(train), n_rep, spec.group_id).numel())
+    idx = shard_indices(len(train), n_rep, spec.group_id)
+    n_shard = idx.numel()
+    total_steps = _total_steps(spec, opts, n_shard)
     trainer = _make_trainer(spec, opts, device, grank, D, total_steps)
     if gsize > 1:
         # DDP's _sync_module_states: replicas start from group rank 0's weights
@@ -495,37 +514,27 @@ def run_trial(spec: TrialSpec, group, opts: RunOptions, data=None, num_trials: O
         trainer.refresh_weights()
         trainer.reset_average()  # the average starts as the weights every replica now holds
         if opts.bucket_mb == "auto":
-            idx0 = shard_indices(len(train), n_rep, spec.group_id)
             key = f"{opts.model}-{opts.image_size}-b{opts.batch_size}-n{trainer.numel}-s{gsize}"
             bounds, kind, timings = autotune_comm(
-                lambda: _make_trainer(spec, opts, device, grank, D, total_steps), group, train.data, idx0, key=key)
+                lambda: _make_trainer(spec, opts, device, grank, D, total_steps), group, train.data, idx, key=key)
             print0(f"bucket autotune (group of {gsize}): {timings} -> {kind or 'default'} {bounds}",
                    process_group=group)
         else:
             bounds, kind = trainer.bucket_bounds(opts.bucket_mb), None
         trainer.attach_reducer(make_arena_reducer(group, trainer.grads, bounds, kind=kind,
                                                   comm_jobs=getattr(trainer, "comm_jobs", False)))
-    start_epoch = 1
+    prog, start_epoch = None, 1
     if opts.ckpt_dir and opts.resume:
-        # only group rank 0 writes checkpoints, so only it reads one; the
-        # replicas receive weights, Adam moments, the step counter and the
-        # epoch to resume from (no shared filesystem needed). Rank 0's load
-        # outcome goes first, so a load error (arch mismatch, corrupt file)
-        # raises on every member together instead of stranding the replicas
-        # in the parameter broadcast.
-        prog, err = None, None
+        # only group rank 0 writes checkpoints, so only it reads one; the replicas receive weights, Adam
+        # moments, the step counter and the epoch to resume from (no shared filesystem needed). Rank 0's
+        # load outcome goes first, so a load error (arch mismatch, corrupt file, another objective) raises
+        # on every member together instead of stranding the replicas in the parameter broadcast.
+        err = None
         if grank == 0:
             try:
-                prog = ckpt.load_latest(opts.ckpt_dir, spec.group_id, trainer)
-                _check_resumed_binarize(prog, opts, spec.group_id)
-                _check_resumed_free_bits(prog, spec)
-                _check_resumed_tc_weight(prog, spec)
-                _check_resumed_ema_decay(prog, spec)
+                prog, start_epoch = _resume(trainer, spec, opts, group, announce=True)
             except Exception as e:  # noqa: BLE001 - re-raised below on every member
                 err = e
-        if prog is not None:
-            start_epoch = prog["epoch"] + 1
-            print0(f"resumed trial {spec.group_id} from {prog['path']} (epoch {prog['epoch']})", process_group=group)
         if gsize > 1:
             # + the schedule rank 0's checkpoint restored (it wins over the command line on every member)
             meta = torch.tensor([0 if err is None else 1, start_epoch, trainer.step_count] +
@@ -548,20 +557,7 @@ def run_trial(spec: TrialSpec, group, opts: RunOptions, data=None, num_trials: O
         elif err is not None:
             raise err
     metrics = TrialMetrics(opts.metrics_dir, spec.group_id, enabled=(grank == 0))
-
-    idx = shard_indices(len(train), n_rep, spec.group_id)
-    n_shard = idx.numel()
-    # --binarize: the trainer reads the binarizer's compact buffer (rewritten in
-    # place every epoch) and every test pass reads the fixed binarized test set
-    binarizer, test = _binarizers(spec, opts, train, test, idx)
-    if binarizer is not None:
-        trainer.bind_train_data(binarizer.data, binarizer.index())
-    else:
-        trainer.bind_train_data(train.data, idx)
-    # capture the step graphs and the test-set eval graphs and load the
-    # decode kernels now, like the reference's model/DDP construction before
-    # its timer starts (vae-hpo.py:159)
-    trainer.prepare([opts.batch_size, n_shard % opts.batch_size], test.data if opts.eval_each_epoch else None)
+    binarizer, test = _bind_data(trainer, spec, opts, train, test, idx)
 
     # Parity with the reference's download barrier (vae-hpo.py:133-144).
     global_barrier()
@@ -605,22 +601,21 @@ def run_trial(spec: TrialSpec, group, opts: RunOptions, data=None, num_trials: O
     global_barrier()  # parity: vae-hpo.py:172 (waits for the slowest trial)
     t1 = time.time()
     print(world_rank, "Done. time: %f" % (t1 - t0), flush=True)
-    extra = {}
-    if opts.iw_samples > 0 and not failure:
-        with guarded(f"trial {spec.group_id} IW pass (world rank {world_rank})", None,
-                     lambda e: failure.setdefault("error", f"{type(e).__name__}: {e}")):
-            extra = _iw_eval(trainer, test, opts, group, metrics, device)
-    if opts.latent_report and not failure:
-        with guarded(f"trial {spec.group_id} latent pass (world rank {world_rank})", None,
-                     lambda e: failure.setdefault("error", f"{type(e).__name__}: {e}")):
-            extra = dict(extra, **_latent_eval(trainer, test, opts, group, metrics, device))
-    if spec.ema_decay > 0 and not failure:
-        with guarded(f"trial {spec.group_id} raw-weight test pass (world rank {world_rank})", None,
-                     lambda e: failure.setdefault("error", f"{type(e).__name__}: {e}")):
-            extra = dict(extra, test_loss_raw=_raw_test_loss(trainer, test, device))
+    extra = _after_trial(trainer, spec, test, opts, group, metrics, device, failure, world_rank)
     return TrialResult(spec.group_id, epochs_done, n_shard, epochs_done * n_shard, t1 - t0,
                        train_loss / len(train), test_loss, failed=bool(failure), error=failure.get("error", ""),
                        extra=extra)
+
+
+def _objective_metrics(st, spec: TrialSpec, opts: RunOptions, n_shard: int) -> dict:
+    """The knob part of an epoch's record: the value in force at the epoch's last step where the
+    kernels record one (``st = trainer.read_state()``), the value the trial was given otherwise."""
+    out = {}
+    for name in (n for n in NAMES if n in opts.report_objective):
+        if name == "tc_weight":  # + the epoch's sum of tc_batch (unweighted, models/tc.py) over the rows trained
+            out["train_tc"] = st["epoch_tc"] / max(n_shard, 1)
+        out[name] = st[name] if name in st else getattr(spec, name)
+    return out
 
 
 def _run_epoch(trainer, epoch, n_shard, train, test, opts, group, rdir, shape, gen, device, spec, grank, metrics,
@@ -662,13 +657,7 @@ def _run_epoch(trainer, epoch, n_shard, train, test, opts, group, rdir, shape, g
     metrics.log(epoch=epoch, train_loss_sum=train_loss, train_loss=train_loss / len(train),
                 test_loss=test_loss, epoch_train_s=t_train, samples=n_shard,
                 train_samples_per_s=n_shard / max(t_train, 1e-9), lr=st["lr"], kl_beta=st["kl_beta"],
-                lr_base=spec.lr, beta=spec.beta, **({"free_bits": st["free_bits"]} if opts.report_free_bits else {}),
-                # train_tc: the epoch's sum of tc_batch (unweighted, models/tc.py) over the rows trained;
-                # tc_weight: the effective weight of the epoch's last step
-                **({"train_tc": st["epoch_tc"] / max(n_shard, 1), "tc_weight": st["tc_weight"]}
-                   if opts.report_tc else {}),
-                **({"ema_decay": spec.ema_decay} if opts.report_ema else {}),
-                **phases)
+                lr_base=spec.lr, beta=spec.beta, **_objective_metrics(st, spec, opts, n_shard), **phases)
     return train_loss, test_loss
 
 
@@ -697,28 +686,14 @@ def run_packed_trials(specs, group, opts: RunOptions, data=None, num_trials: Opt
     shape = (1, opts.image_size, opts.image_size)
     tr = []
     for spec in specs:
-        trainer = _make_trainer(spec, opts, device, 0, D,
-                                _total_steps(spec, opts, shard_indices(len(train), total, spec.group_id).numel()))
+        idx = shard_indices(len(train), total, spec.group_id)  # packing extension: one shard per trial
+        trainer = _make_trainer(spec, opts, device, 0, D, _total_steps(spec, opts, idx.numel()))
         if len(specs) > 1 and hasattr(trainer, "f28_pair"):
             # packed trials fill the chip already; the one-workgroup-per-sample
             # step keeps their numerics independent of how the trials interleave
             trainer.f28_pair = False
-        start = 1
-        if opts.ckpt_dir and opts.resume:
-            prog = ckpt.load_latest(opts.ckpt_dir, spec.group_id, trainer)
-            _check_resumed_binarize(prog, opts, spec.group_id)
-            _check_resumed_free_bits(prog, spec)
-            _check_resumed_tc_weight(prog, spec)
-            _check_resumed_ema_decay(prog, spec)
-            if prog is not None:
-                start = prog["epoch"] + 1
-        idx = shard_indices(len(train), total, spec.group_id)  # packing extension: one shard per trial
-        binarizer, ttest = _binarizers(spec, opts, train, test, idx)  # --binarize: a buffer pair per trial
-        if binarizer is not None:
-            trainer.bind_train_data(binarizer.data, binarizer.index())
-        else:
-            trainer.bind_train_data(train.data, idx)
-        trainer.prepare([opts.batch_size, idx.numel() % opts.batch_size], ttest.data if opts.eval_each_epoch else None)
+        _, start = _resume(trainer, spec, opts)
+        binarizer, ttest = _bind_data(trainer, spec, opts, train, test, idx)  # --binarize: a buffer pair per trial
         rdir = (f"results-t{spec.group_id}-0" if opts.results else None)
         tr.append(dict(spec=spec, trainer=trainer, start=start, n_shard=idx.numel(), rdir=rdir,
                        stream=torch.cuda.Stream(device) if device.type == "cuda" else None,
@@ -767,21 +742,8 @@ def run_packed_trials(specs, group, opts: RunOptions, data=None, num_trials: Opt
     t1 = time.time()
     print(world_rank, "Done. time: %f" % (t1 - t0), flush=True)
     for t in tr:
-        t["extra"] = {}
-        if opts.iw_samples > 0 and not t["failure"]:
-            with guarded(f"trial {t['spec'].group_id} IW pass (world rank {world_rank})", None,
-                         lambda e, t=t: t["failure"].setdefault("error", f"{type(e).__name__}: {e}")):
-                t["extra"] = _iw_eval(t["trainer"], t["test"], opts, group, t["metrics"], device,
-                                      tag=f"(trial {t['spec'].group_id}) ")
-        if opts.latent_report and not t["failure"]:
-            with guarded(f"trial {t['spec'].group_id} latent pass (world rank {world_rank})", None,
-                         lambda e, t=t: t["failure"].setdefault("error", f"{type(e).__name__}: {e}")):
-                t["extra"] = dict(t["extra"], **_latent_eval(t["trainer"], t["test"], opts, group, t["metrics"], device,
-                                                             tag=f"(trial {t['spec'].group_id}) "))
-        if t["spec"].ema_decay > 0 and not t["failure"]:
-            with guarded(f"trial {t['spec'].group_id} raw-weight test pass (world rank {world_rank})", None,
-                         lambda e, t=t: t["failure"].setdefault("error", f"{type(e).__name__}: {e}")):
-                t["extra"] = dict(t["extra"], test_loss_raw=_raw_test_loss(t["trainer"], t["test"], device))
+        t["extra"] = _after_trial(t["trainer"], t["spec"], t["test"], opts, group, t["metrics"], device, t["failure"],
+                                  world_rank, tag=f"(trial {t['spec'].group_id}) ")
     return [TrialResult(t["spec"].group_id, t["done"], t["n_shard"], t["done"] * t["n_shard"], t1 - t0,
                         t["train_loss"] / len(train), t["test_loss"], failed=bool(t["failure"]),
                         error=t["failure"].get("error", ""), extra=t["extra"]) for t in tr]

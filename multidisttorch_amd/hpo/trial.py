@@ -12,6 +12,7 @@ import math
 from dataclasses import asdict, dataclass
 from typing import List, Optional, Sequence
 
+from . import objective
 from .schedule import Schedule
 
 __all__ = ["TrialSpec", "reference_schedule", "default_sweep", "parse_list", "build_specs"]
@@ -31,16 +32,17 @@ class TrialSpec:
     lr_decay_steps: int = 0
     lr_min_ratio: float = 0.0
     kl_anneal_steps: int = 0
-    # free bits: KL floor in nats per sample and latent dimension, 0 = off (csrc/kernels/common.h)
+    # the objective knobs, one field per row of hpo/objective.py (what each one is stands there), 0 = off
     free_bits: float = 0.0
-    # total-correlation penalty: weight of the minibatch TC estimate in the objective, 0 = off (models/tc.py)
     tc_weight: float = 0.0
-    # weight averaging: decay of the parameter average every evaluation uses, in [0, 1), 0 = off
-    # (docs/KERNELS.md, "Weight averaging")
     ema_decay: float = 0.0
 
     def to_dict(self):
         return asdict(self)
+
+    def objective(self) -> dict:
+        """The trial's objective knobs (hpo/objective.py) by name: the trainers' keyword arguments."""
+        return {n: getattr(self, n) for n in objective.NAMES}
 
     def schedule(self, total_steps: Optional[int] = None) -> Schedule:
         """The trial's ``Schedule``; ``total_steps`` (epochs x batches per epoch)
@@ -81,40 +83,30 @@ def build_specs(num_groups: int, epochs: int, lrs: Optional[Sequence[float]] = N
                 epoch_offset: bool = True, lr_warmups: Optional[Sequence[int]] = None,
                 lr_decays: Optional[Sequence[str]] = None, lr_decay_steps: Optional[Sequence[int]] = None,
                 lr_min_ratios: Optional[Sequence[float]] = None,
-                kl_anneals: Optional[Sequence[int]] = None, free_bits=None, tc_weight=None,
-                ema_decay=None) -> List[TrialSpec]:
+                kl_anneals: Optional[Sequence[int]] = None, **knobs) -> List[TrialSpec]:
     """Per-group specs. A single value broadcasts; a list is indexed by group (cycled).
-    ``free_bits``, ``tc_weight``: a scalar, a list or a comma list like ``--beta``; finite and >= 0.
-    ``ema_decay``: the same forms; every value in [0, 1)."""
+    ``knobs``: the objective knobs of hpo/objective.py by name (``free_bits=``, ``tc_weight=``,
+    ``ema_decay=``), each a scalar, a list or a comma list like ``--beta``, inside the knob's range."""
     def pick(vals, g, default):
         return vals[g % len(vals)] if vals else default
 
-    def nonneg(vals, name):
+    for name, vals in knobs.items():
+        if name not in objective.NAMES:
+            raise TypeError(f"build_specs() got an unexpected keyword argument {name!r}")
         if vals is None or isinstance(vals, str):
             vals = parse_list(vals)
         elif isinstance(vals, (int, float)):
             vals = [vals]
-        for v in vals or []:
-            if not (math.isfinite(float(v)) and float(v) >= 0.0):
-                raise ValueError(f"{name} must be finite and >= 0, got {v}")
-        return vals
-
-    free_bits = nonneg(free_bits, "free_bits")
-    tc_weight = nonneg(tc_weight, "tc_weight")
-    ema_decay = nonneg(ema_decay, "ema_decay")
-    for v in ema_decay or []:
-        if not float(v) < 1.0:
-            raise ValueError(f"ema_decay must be in [0, 1), got {v}")
+        knobs[name] = [objective.check(name, v) for v in vals or []]
     out = []
     for g in range(num_groups):
-        lr = lrs[g % len(lrs)] if lrs else 1e-3
-        b = betas[g % len(betas)] if betas else 1.0
-        spec = TrialSpec(g, epochs + (g if epoch_offset else 0), float(lr), float(b), seed + g,
+        spec = TrialSpec(g, epochs + (g if epoch_offset else 0), float(pick(lrs, g, 1e-3)),
+                         float(pick(betas, g, 1.0)), seed + g,
                          lr_warmup_steps=int(pick(lr_warmups, g, 0)), lr_decay=str(pick(lr_decays, g, "none")),
                          lr_decay_steps=int(pick(lr_decay_steps, g, 0)),
                          lr_min_ratio=float(pick(lr_min_ratios, g, 0.0)),
-                         kl_anneal_steps=int(pick(kl_anneals, g, 0)), free_bits=float(pick(free_bits, g, 0.0)),
-                         tc_weight=float(pick(tc_weight, g, 0.0)), ema_decay=float(pick(ema_decay, g, 0.0)))
+                         kl_anneal_steps=int(pick(kl_anneals, g, 0)),
+                         **{name: pick(vals, g, 0.0) for name, vals in knobs.items()})
         # bad values fail here, not in the middle of a run (T = 0 under cosine is resolved by the runner)
         spec.schedule(total_steps=spec.lr_warmup_steps + 1 if spec.lr_decay_steps == 0 else None)
         out.append(spec)

@@ -234,7 +234,8 @@ class ConvVaeTrainer(VaeTrainerBase):
                  ema_decay: float = 0.0):
         z = check_latent_size(z)
         super().__init__(batch_size, device, backend, seed, rng_stream, lr, kl_beta, betas, eps, weight_decay,
-                         decoupled_wd, use_graphs, graph_steps, schedule, free_bits, tc_weight, ema_decay)
+                         decoupled_wd, use_graphs, graph_steps, schedule,
+                         dict(free_bits=free_bits, tc_weight=tc_weight, ema_decay=ema_decay))
         backend = self.backend
         self.image, self.channels, self.Z = image, channels, z
         self.D = image * image * channels

@@ -42,7 +42,8 @@ class MlpVaeTrainer(VaeTrainerBase):
                  use_graphs: bool = True, graph_steps: int = 10, schedule: Optional[Schedule] = None,
                  free_bits: float = 0.0, tc_weight: float = 0.0, ema_decay: float = 0.0):
         super().__init__(batch_size, device, backend, seed, rng_stream, lr, kl_beta, betas, eps, weight_decay,
-                         decoupled_wd, use_graphs, graph_steps, schedule, free_bits, tc_weight, ema_decay)
+                         decoupled_wd, use_graphs, graph_steps, schedule,
+                         dict(free_bits=free_bits, tc_weight=tc_weight, ema_decay=ema_decay))
         self.D, self.H, self.Z = D, H, Z
         self.layout, self.numel, self.split = arena_layout(D, H, Z)
         if self.backend == "hip":

@@ -30,22 +30,19 @@ which is what csrc/kernels/vae_tc.hip computes (times ``tc_t``).
 
 from __future__ import annotations
 
+import functools
 import math
 import warnings
 
 import torch
 
+from ..hpo import objective
 from . import latent
 
 __all__ = ["check_tc_weight", "tc_batch", "tc_closed_form"]
 
 
-def check_tc_weight(v) -> float:
-    """The weight of the total-correlation penalty: finite and >= 0."""
-    v = float(v)
-    if not (math.isfinite(v) and v >= 0.0):
-        raise ValueError(f"tc_weight must be finite and >= 0, got {v}")
-    return v
+check_tc_weight = functools.partial(objective.check, "tc_weight")  # the penalty's weight: finite and >= 0
 
 
 def tc_batch(mu: torch.Tensor, lv: torch.Tensor, eps: torch.Tensor) -> torch.Tensor:

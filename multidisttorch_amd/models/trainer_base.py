@@ -18,19 +18,19 @@ A subclass sets ``B``, ``Z``, ``layout``, ``numel``, the arenas and (hip)
 from __future__ import annotations
 
 import contextlib
-import math
+import functools
 import os
 from typing import Dict, Optional
 
 import numpy as np
 import torch
 
+from ..hpo import objective
 from ..hpo.schedule import Schedule
 from ..ops import native
 from ..ops.philox import reparam_eps
 from .eval_graphs import GraphedEval, GraphedIwEval, GraphedLatentEval, capture_replayable
 from .mlp_vae import views
-from .tc import check_tc_weight
 
 __all__ = ["VaeTrainerBase", "LOSS_HIST", "EVAL_STREAM", "check_free_bits", "check_ema_decay", "ema_omd"]
 
@@ -38,20 +38,8 @@ EVAL_STREAM = 1 << 30
 LOSS_HIST = 4096  # per-step loss ring of a trial state (kLossHist, csrc/kernels/vae_mlp.h)
 
 
-def check_free_bits(v) -> float:
-    """The free-bits floor in nats per latent element: finite and >= 0."""
-    v = float(v)
-    if not (math.isfinite(v) and v >= 0.0):
-        raise ValueError(f"free_bits must be finite and >= 0, got {v}")
-    return v
-
-
-def check_ema_decay(v) -> float:
-    """The decay of the weight average: in [0, 1), 0 = off."""
-    v = float(v)
-    if not (math.isfinite(v) and 0.0 <= v < 1.0):
-        raise ValueError(f"ema_decay must be in [0, 1), got {v}")
-    return v
+check_free_bits = functools.partial(objective.check, "free_bits")  # the floor in nats per latent element
+check_ema_decay = functools.partial(objective.check, "ema_decay")  # the decay of the weight average, 0 = off
 
 
 def ema_omd(decay: float, t: int) -> float:
@@ -64,8 +52,7 @@ def ema_omd(decay: float, t: int) -> float:
 class VaeTrainerBase(GraphedEval, GraphedIwEval, GraphedLatentEval):
     def __init__(self, batch_size: int, device, backend: Optional[str], seed: int, rng_stream: int, lr: float,
                  kl_beta: float, betas, eps: float, weight_decay: float, decoupled_wd: bool, use_graphs: bool,
-                 graph_steps: int, schedule: Optional[Schedule], free_bits: float = 0.0, tc_weight: float = 0.0,
-                 ema_decay: float = 0.0):
+                 graph_steps: int, schedule: Optional[Schedule], knobs: Optional[dict] = None):
         self.B = batch_size
         # lr warm-up / cosine decay and KL annealing (hpo/schedule.py); None = off.
         # On the hip backend the kernels evaluate it from the device step counter.
@@ -79,16 +66,15 @@ class VaeTrainerBase(GraphedEval, GraphedIwEval, GraphedLatentEval):
         self.backend = backend
         self.seed, self.rng_stream = int(seed), int(rng_stream)
         self.hp = dict(lr=lr, beta1=betas[0], beta2=betas[1], eps=eps, weight_decay=weight_decay,
-                       kl_beta=kl_beta, grad_scale=1.0, free_bits=check_free_bits(free_bits),
-                       tc_weight=check_tc_weight(tc_weight), ema_decay=check_ema_decay(ema_decay))
-        # total-correlation penalty (models/tc.py): a trainer built with it launches the penalty's
-        # kernels in every training step (a weight of 0 then only zeroes their result); one built
-        # without cannot be given a weight later -- its launch list has no such kernels
-        self.tc_on = self.hp["tc_weight"] > 0
-        # weight averaging (docs/KERNELS.md, "Weight averaging"): a trainer built with a decay keeps
-        # ``self.ema``, a second parameter arena, and ends every training step with its update; one
-        # built without cannot be given a decay later -- its launch list has no such launch
-        self.ema_on = self.hp["ema_decay"] > 0
+                       kl_beta=kl_beta, grad_scale=1.0,
+                       **{n: objective.check(n, (knobs or {}).get(n, 0.0)) for n in objective.NAMES})
+        # the structural knobs (hpo/objective.py) the trainer is built with: its step launches their kernels (a
+        # value of 0 later only zeroes their effect); one built without cannot be given a value later
+        self._built = {n for n in objective.NAMES if objective.BY_NAME[n].structural and self.hp[n] > 0}
+        # total-correlation penalty (models/tc.py): the penalty's kernels in every training step
+        self.tc_on = "tc_weight" in self._built
+        # weight averaging (docs/KERNELS.md): ``self.ema``, a second arena, updated by every step's last launch
+        self.ema_on = "ema_decay" in self._built
         self.ema = None
         self._averaged = False  # inside ``averaged_weights()``: params and ema are exchanged
         self.decoupled_wd = decoupled_wd
@@ -251,17 +237,7 @@ class VaeTrainerBase(GraphedEval, GraphedIwEval, GraphedLatentEval):
         for k, v in kw.items():
             if k not in self.hp:
                 raise KeyError(k)
-            if k == "ema_decay":
-                v = check_ema_decay(v)
-                if v > 0 and not self.ema_on:
-                    raise ValueError("ema_decay > 0 needs a trainer built with ema_decay > 0 "
-                                     "(the step's launch list differs)")
-            if k == "tc_weight":
-                v = check_tc_weight(v)
-                if v > 0 and not self.tc_on:
-                    raise ValueError("tc_weight > 0 needs a trainer built with tc_weight > 0 "
-                                     "(the step's launch list differs)")
-            self.hp[k] = check_free_bits(v) if k == "free_bits" else float(v)
+            self.hp[k] = objective.check(k, v, self._built) if k in objective.BY_NAME else float(v)
         self._push_hparams()
 
     def set_schedule(self, schedule: Optional[Schedule]):
@@ -275,8 +251,8 @@ class VaeTrainerBase(GraphedEval, GraphedIwEval, GraphedLatentEval):
             h = self.hp
             self.state.set_hparams(h["lr"], h["beta1"], h["beta2"], h["eps"], h["weight_decay"], h["kl_beta"],
                                    h["grad_scale"], self.seed, self.decoupled_wd,
-                                   **(self.schedule or Schedule()).native_args(), free_bits=h["free_bits"],
-                                   tc_weight=h["tc_weight"], ema_decay=h["ema_decay"])
+                                   **(self.schedule or Schedule()).native_args(),
+                                   **{n: h[n] for n in objective.NAMES})
 
     def _effective(self, t: int):
         """(lr_t, beta_t) of optimizer step t on the torch backend, as doubles:

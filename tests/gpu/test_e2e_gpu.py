@@ -107,6 +107,43 @@ def test_vae_hpo_conv128_gpu(tmp_path):
     assert (tmp_path / "results-0" / "reconstruction_1.png").exists()
 
 
+@pytest.mark.parametrize("model", ["mlp", "conv"])
+def test_single_and_packed_paths_agree_on_one_trial_gpu(model, tmp_path, capsys):
+    """``run_trial`` and ``run_packed_trials`` on one trial with every objective
+    knob, the IW pass and the latent report, hip backend, in this process (conv
+    at 28x28 with ``tc_weight > 0``: the layer path). 40 rows at batch 16: two
+    full batches and a tail of 8.
+
+    Both paths build the trainer from the same spec, bind the same shard and
+    replay the same captured step graphs on the same seed and rng stream; with
+    one packed trial ``f28_pair`` stays as built. The one difference is the
+    stream the packed path enqueues its epoch on, which changes no kernel's
+    arithmetic, so the results agree bitwise, as they did before the two entry
+    points shared their helpers."""
+    import math
+
+    from tests import lifecycle_cases as lc
+
+    r = lc.run_both(model, "hip", tmp_path)
+    a, b = r["single"], r["packed"]
+    for x in (a, b):
+        res = x["result"]
+        assert not res.failed, res.error
+        assert (res.epochs, res.shard, res.samples) == (1, lc.N_TRAIN, lc.N_TRAIN)
+        assert set(x["extra"]) == {"iw_nll", "iw_neg_elbo", "iw_samples", "latent", "test_loss_raw"}
+        assert all(math.isfinite(x["extra"][k]) for k in ("iw_nll", "iw_neg_elbo", "test_loss_raw"))
+        assert all(math.isfinite(x["extra"]["latent"][k]) for k in ("kl", "mi", "tc", "dwkl"))
+        assert math.isfinite(res.final_train_loss) and math.isfinite(res.final_test_loss)
+        assert x["ckpt"]["objective"] == lc.KNOBS and "ema" in x["ckpt"]["optimizer"]
+    print("single", a["result"], "\npacked", b["result"])
+    assert a["extra"] == b["extra"]
+    assert a["result"].final_train_loss == b["result"].final_train_loss
+    assert a["result"].final_test_loss == b["result"].final_test_loss
+    assert a["events"] == b["events"]
+    assert lc.same_nested(a["ckpt"], b["ckpt"])   # parameters, Adam moments and the weight average, bitwise
+    capsys.readouterr()
+
+
 def test_bench_trial_packing():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "50", "--warmup", "10",
                         "--trials-per-gpu", "2"],

@@ -223,11 +223,11 @@ def test_checkpoint_fields_resume_and_the_refused_resume(tmp_path, native_ext):
     b.train_steps(3)
     assert torch.equal(b.params, straight.params) and torch.equal(b.ema, straight.ema)
     # the runner refuses another value
-    runner._check_resumed_ema_decay(prog, spec)
-    runner._check_resumed_ema_decay(None, spec)
+    runner._check_resumed(prog, spec, runner.RunOptions())
+    runner._check_resumed(None, spec, runner.RunOptions())
     other = build_specs(1, 2, ema_decay=0.99)[0]
     with pytest.raises(ValueError, match=r"was trained with --ema-decay 0\.9, this run asks for --ema-decay 0\.99"):
-        runner._check_resumed_ema_decay(prog, other)
+        runner._check_resumed(prog, other, runner.RunOptions())
     # a checkpoint of a run without averaging: no fields, loads as 0, and an averaging trainer starts at e = p
     plain = _mlp()
     plain.train_steps(3)
@@ -240,5 +240,5 @@ def test_checkpoint_fields_resume_and_the_refused_resume(tmp_path, native_ext):
     prog0 = ckpt.load_latest(str(tmp_path / "ck0"), 0, c)
     assert prog0["ema_decay"] == 0.0 and torch.equal(c.ema, c.params) and torch.equal(c.params, plain.params)
     with pytest.raises(ValueError, match="was trained with --ema-decay 0.0"):
-        runner._check_resumed_ema_decay(prog0, spec)
+        runner._check_resumed(prog0, spec, runner.RunOptions())
     assert math.isfinite(float(c.ema.abs().sum()))

@@ -347,8 +347,8 @@ def test_metrics_carry_the_floor_only_when_asked(data, tmp_path, capsys):
     rec = [json.loads(l) for l in open(md / "trial-0.jsonl")]
     assert rec and all("free_bits" not in r for r in rec)
     md2 = tmp_path / "m2"
-    res = run_trial(_spec(1, 0.05), None, _opts(metrics_dir=str(md2), report_free_bits=True, latent_report=True),
-                    data=data)
+    res = run_trial(_spec(1, 0.05), None,
+                    _opts(metrics_dir=str(md2), report_objective=("free_bits",), latent_report=True), data=data)
     rec = [json.loads(l) for l in open(md2 / "trial-0.jsonl")]
     ep = [r for r in rec if "epoch" in r]
     assert ep and all(r["free_bits"] == float(np.float32(0.05)) for r in ep)
@@ -358,7 +358,8 @@ def test_metrics_carry_the_floor_only_when_asked(data, tmp_path, capsys):
     assert res.extra["latent"]["below_floor"] == lat["below_floor"]
     # a trial without a floor in the same run reports its 0 and no below_floor
     md3 = tmp_path / "m3"
-    run_trial(_spec(1, 0.0), None, _opts(metrics_dir=str(md3), report_free_bits=True, latent_report=True), data=data)
+    run_trial(_spec(1, 0.0), None, _opts(metrics_dir=str(md3), report_objective=("free_bits",), latent_report=True),
+              data=data)
     rec = [json.loads(l) for l in open(md3 / "trial-0.jsonl")]
     assert all(r["free_bits"] == 0.0 for r in rec if "epoch" in r)
     assert "below_floor" not in [r for r in rec if r.get("event") == "latent_eval"][0]

@@ -11,7 +11,9 @@ Extensions (opt-in, default output unchanged): ``--lr`` / ``--beta`` (scalar or
 comma list, one per trial), the per-trial schedules ``--lr-warmup`` / ``--lr-decay``
 / ``--lr-decay-steps`` / ``--lr-min-ratio`` / ``--kl-anneal`` (same form;
 multidisttorch_amd/hpo/schedule.py), ``--free-bits`` (same form: a KL floor in nats
-per sample and latent dimension, training only), ``--seed``, ``--ckpt-dir`` + ``--resume``,
+per sample and latent dimension, training only), ``--tc-weight`` (same form: the weight
+of a minibatch total-correlation penalty in the training objective), ``--ema-decay`` (same
+form: the decay of a weight average that every evaluation then uses), ``--seed``, ``--ckpt-dir`` + ``--resume``,
 ``--metrics-dir`` (JSONL + aggregate samples/s), ``--per-group-results``, ``--bucket-mb``,
 ``--no-graphs``, ``--backend {hip,torch}``, ``--synthetic/--real-data``,
 ``--trials-per-group T`` (T concurrent trials per single-rank group, one HIP
@@ -35,6 +37,8 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from utils import *  # noqa: F401,F403  (reference-compatible API + re-exports)
 
 from multidisttorch_amd.data.binarize import BINARIZE_CHOICES
+from multidisttorch_amd.hpo import objective
+from multidisttorch_amd.hpo.aggregate import summarize, trial_record
 from multidisttorch_amd.hpo.runner import RunOptions, idle_rank, run_packed_trials, run_trial
 from multidisttorch_amd.hpo.trial import build_specs, parse_list
 from multidisttorch_amd.parallel.autotune import parse_bucket_mb
@@ -60,16 +64,8 @@ def parse_args(argv=None):
     parser.add_argument("--lr-min-ratio", type=str, default=None, help="cosine floor as a fraction of lr, in [0, 1]")
     parser.add_argument("--kl-anneal", type=str, default=None,
                         help="steps over which the KLD weight ramps linearly from 0 to --beta")
-    parser.add_argument("--free-bits", type=str, default=None,
-                        help="free bits: a floor in nats under each latent dimension's KL term of each sample "
-                             "(training objective only; 0 = off), comma list per trial")
-    parser.add_argument("--tc-weight", type=str, default=None,
-                        help="weight of the minibatch total-correlation penalty in the training objective "
-                             "(--beta 1 --tc-weight b-1 is beta-TCVAE; 0 = off), comma list per trial")
-    parser.add_argument("--ema-decay", type=str, default=None,
-                        help="decay of an exponential moving average of the weights, in [0, 1); every evaluation "
-                             "(test loss, --iw-samples, --latent-report, samples) then uses the average "
-                             "(0 = off), comma list per trial")
+    for knob in objective.KNOBS:  # --free-bits, --tc-weight, --ema-decay: the same form (hpo/objective.py)
+        parser.add_argument(knob.flag, type=str, default=None, help=knob.help)
     parser.add_argument("--seed", type=int, default=0, help="base seed (trial g uses seed+g)")
     parser.add_argument("--no-epoch-offset", action="store_true", help="all trials train --epochs epochs")
     parser.add_argument("--log-interval", type=int, default=10)
@@ -145,7 +141,7 @@ def main(argv=None):
                         lr_decays=parse_list(args.lr_decay, lambda s: s.strip()),
                         lr_decay_steps=parse_list(args.lr_decay_steps, int),
                         lr_min_ratios=parse_list(args.lr_min_ratio), kl_anneals=parse_list(args.kl_anneal, int),
-                        free_bits=args.free_bits, tc_weight=args.tc_weight, ema_decay=args.ema_decay)
+                        **{name: getattr(args, name) for name in objective.NAMES})
     opts = RunOptions(batch_size=args.batch_size, log_interval=args.log_interval,
                       backend=args.backend, use_graphs=not args.no_graphs, graph_steps=args.graph_steps,
                       ckpt_dir=args.ckpt_dir, resume=args.resume, metrics_dir=args.metrics_dir,
@@ -156,9 +152,7 @@ def main(argv=None):
                       model=args.model, image_size=args.image_size, bucket_mb=parse_bucket_mb(args.bucket_mb),
                       profile=args.profile, iw_samples=max(0, args.iw_samples), latent_report=args.latent_report,
                       au_threshold=args.au_threshold, binarize=args.binarize,
-                      report_free_bits=any(s.free_bits > 0 for s in specs),
-                      report_tc=any(s.tc_weight > 0 for s in specs),
-                      report_ema=any(s.ema_decay > 0 for s in specs))
+                      report_objective=objective.reported(specs))
     results = []
     member = False
     for group_id, group in enumerate(processes_groups):
@@ -172,62 +166,11 @@ def main(argv=None):
     if not member:
         idle_rank()
 
-    # aggregate samples/s: samples once per trial, max wall over ranks
-    lat_keys = ("kl", "active_units", "mi", "tc", "dwkl")
-    mine = [(r.group_id, r.samples, r.wall_s, r.failed) + ((r.extra.get("iw_nll"),) if opts.iw_samples > 0 else ()) +
-            ((r.extra.get("latent"),) if opts.latent_report else ()) +
-            ((r.extra.get("test_loss_raw"),) if opts.report_ema else ())
-            for r in results]
+    # aggregate samples/s: every rank's records of its trials, summarized on rank 0 (hpo/aggregate.py)
     gathered = [None] * dist.get_world_size()
-    dist.all_gather_object(gathered, mine, group=control_group())
+    dist.all_gather_object(gathered, [trial_record(r, opts) for r in results], group=control_group())
     if dist.get_rank() == 0:
-        per_trial, wall, failed, iw_nll, latent, raw = {}, 0.0, set(), {}, {}, {}
-        for lst in gathered:
-            for gid, samples, w, bad, *more in lst or []:
-                if opts.report_ema:
-                    v = more.pop()
-                    if v is not None:
-                        raw[gid] = v
-                iw = more[:1] if opts.iw_samples > 0 else []
-                lat = more[-1] if opts.latent_report else None
-                if iw and iw[0] is not None:
-                    iw_nll[gid] = iw[0]
-                if lat is not None:
-                    latent[gid] = lat
-                per_trial[gid] = min(per_trial.get(gid, samples), samples)
-                wall = max(wall, w)
-                if bad:
-                    failed.add(gid)
-        summary = {"metric": "aggregate VAE samples/sec across K concurrent HPO trials",
-                   "trials": len(per_trial), "samples": int(sum(per_trial.values())),
-                   "wall_s": round(wall, 4),
-                   "value": round(sum(per_trial.values()) / max(wall, 1e-9), 1), "unit": "samples/s",
-                   "failed_trials": sorted(failed)}
-        if opts.binarize != "none":
-            summary["binarize"] = opts.binarize  # the likelihood every score of this run is under
-        if opts.report_free_bits:
-            # the KL floor (nats) of every trial's training objective; test scores are the true ELBO terms
-            summary["free_bits"] = {str(s.group_id): s.free_bits for s in specs}
-        if opts.report_tc:
-            # the weight of every trial's total-correlation penalty; test scores are the true ELBO terms
-            summary["tc_weight"] = {str(s.group_id): s.tc_weight for s in specs}
-        if opts.report_ema:
-            # the decay of every trial's weight average; every score of a trial that sets one is under the
-            # averaged weights, and test_loss_raw is its last test loss under the raw ones (what averaging bought)
-            summary["ema_decay"] = {str(s.group_id): s.ema_decay for s in specs}
-            summary["test_loss_raw"] = {str(g): round(v, 4) for g, v in sorted(raw.items())}
-        if opts.iw_samples > 0:
-            # per-image means over the test set; the lowest bound on -log p(x) is the best trial
-            summary["iw_samples"] = opts.iw_samples
-            summary["iw_nll"] = {str(g): round(v, 4) for g, v in sorted(iw_nll.items())}
-            summary["best_trial_by_iw_nll"] = min(iw_nll, key=lambda g: (iw_nll[g], g)) if iw_nll else None
-        if opts.latent_report:
-            # per-image means over the test set (nats); active_units counts Var_x(mu_d) > --au-threshold
-            summary["latent"] = {str(g): {k: (v[k] if k == "active_units" else round(v[k], 4)) for k in lat_keys}
-                                 for g, v in sorted(latent.items())}
-            for g, v in latent.items():  # trials with a KL floor: the dimensions it holds up
-                if "below_floor" in v:
-                    summary["latent"][str(g)]["below_floor"] = v["below_floor"]
+        summary = summarize(gathered, specs, opts)
         if args.metrics_dir:
             os.makedirs(args.metrics_dir, exist_ok=True)
             with open(os.path.join(args.metrics_dir, "aggregate.json"), "w") as f:
