@@ -23,6 +23,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=6)
+    ap.add_argument("--no-epi", action="store_true",
+                    help="all units even when the trainer applies Adam in the Linear epilogues (MDT_F28_EPI_ADAM)")
     a = ap.parse_args()
     from multidisttorch_amd.data.datasets import synthetic_images
     from multidisttorch_amd.models.conv_vae import ConvVaeTrainer
@@ -36,9 +38,12 @@ def main():
     tr.train_steps(2)
     torch.cuda.synchronize()
     C, p, st = tr.C, tr._plan28(B), tr.state
+    if a.no_epi:
+        tr.f28_epi_adam = False
+    q = tr._epi_plan28(p) if tr.f28_epi_adam else None  # the unit list _step28's finalize runs
     j = C.Job()
-    C.grad_finalize(tr.params, tr.grads, tr.exp_avg, tr.exp_avg_sq, tr.w16, p["segs"], p["units"], p["nunits"],
-                    st.train_state, st.hparams, True, job=j)
+    C.grad_finalize(tr.params, tr.grads, tr.exp_avg, tr.exp_avg_sq, tr.w16, p["segs"], (q or p)["units"],
+                    (q or p)["nunits"], st.train_state, st.hparams, True, job=j)
     grid = j.nblk
     stamps = torch.zeros(2 * grid, dtype=torch.int64, device=dev)
     pack, g2 = C.pack_jobs_multi([j], stamps=stamps)
@@ -69,6 +74,8 @@ def main():
     print(f"  workgroup start us: median {np.median(np.stack(starts[1:])):.2f}  last {np.median(np.stack(starts[1:]).max(1)):.2f}")
     print(f"  first entry -> last exit us: {np.median(spans[1:]):.2f}")
     print(f"  event-timed launch us: {np.median(ev_us[1:]):.2f}")
+    if q:  # the two Linear weight segments have no units here: no per-layer ranges
+        return
     lu = p["layer_units"]
     for i, l in enumerate(tr.spec):
         u0, u1 = lu[i], lu[i + 1]

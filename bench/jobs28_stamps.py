@@ -24,6 +24,8 @@ def main():
     ap.add_argument("--steps", type=int, default=6)
     ap.add_argument("--json", default=None)
     ap.add_argument("--merged", action="store_true", help="the merged table: + gather + per-layer finalize jobs")
+    ap.add_argument("--no-epi", action="store_true",
+                    help="the plain table even when the trainer applies Adam in the Linear epilogues (MDT_F28_EPI_ADAM)")
     a = ap.parse_args()
     from multidisttorch_amd.data.datasets import synthetic_images
     from multidisttorch_amd.models.conv_vae import ConvVaeTrainer
@@ -44,7 +46,11 @@ def main():
         names += (["gather"] if tr.f28_prefetch else []) + ["fin_" + n for n in tr._FIN_ORDER28]
     else:
         tr.f28_fin_merge = False
-        jobs, wait = p["jobs"], []
+        if a.no_epi:
+            tr.f28_epi_adam = False
+        q = tr._epi_plan28(p) if tr.f28_epi_adam else None  # the table _step28 launches
+        jobs, wait = (q or p)["jobs"], []
+        print("table:", "Adam in the enc_head / dec_fc epilogues" if q else "plain")
     nblk = [j.nblk for j in jobs]
     grid0 = sum(nblk)
     stamps = torch.zeros(2 * grid0, dtype=torch.int64, device=dev)
@@ -53,7 +59,7 @@ def main():
     if a.merged:
         p[("merged", True, bool(tr.f28_prefetch))] = (pack.to(dev), grid, jobs, wait)
     else:
-        p["jobs_pack"], p["jobs_grid"] = pack.to(dev), grid
+        (q or p)["jobs_pack"], (q or p)["jobs_grid"] = pack.to(dev), grid
     runs = []
     for _ in range(a.steps):
         stamps.zero_()

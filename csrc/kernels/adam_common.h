@@ -42,6 +42,31 @@ __device__ __forceinline__ AdamC adam_consts_block(const TrainState* st, const H
   return *sh;
 }
 
+// The constants adam_consts_block will give AFTER the next step_advance, from
+// the state before it: for a launch that runs ahead of the advancing one and
+// hands them to an Adam epilogue inside it (the fused 28x28 step's f28_adamc;
+// the conv kernels' 1.f - beta weights). Every line mirrors step_advance +
+// sched_store + adam_consts_block above; the products are rounded as those
+// store them (no contraction into 1 - beta^t), so the two agree bit for bit
+// (tests/gpu/test_f28_epilogue_adam.py).
+__device__ __forceinline__ AdamC adam_consts_next(const TrainState* st, const HParams* hp) {
+#pragma clang fp contract(off)
+  const long long t = st->step + 1;
+  const double b1pow = st->b1pow * hp->beta1_d;
+  const double b2pow = st->b2pow * hp->beta2_d;
+  const bool on = st->sched_off == 0;
+  const double lr_t = hp->lr_d * (on ? sched_lr_factor(*hp, t) : 1.0);
+  const double bc1 = 1.0 - b1pow;
+  const double bc2 = 1.0 - b2pow;
+  AdamC c;
+  c.step_size = (float)(lr_t / bc1);
+  c.bc2s = (float)sqrt(bc2);
+  c.b1 = hp->beta1; c.b2 = hp->beta2; c.eps = hp->eps; c.wd = hp->weight_decay;
+  c.gs = hp->grad_scale; c.lr = (float)lr_t; c.decoupled = hp->decoupled_wd;
+  c.omb1 = 1.f - c.b1; c.omb2 = 1.f - c.b2;
+  return c;
+}
+
 // Same constants when the step state was advanced earlier IN THIS LAUNCH by
 // another workgroup (dependent jobs_multi_k launch): beta^t and lr_t through sc1 vector
 // loads, so neither this CU's L1 nor the scalar cache can serve an old copy.

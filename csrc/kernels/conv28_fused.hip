@@ -7,6 +7,7 @@
 //               resident in time runs the solo body), or grid M solo
 //
 // Bodies: conv28_fused.h (solo), conv28_pair.h (pairs).
+#include <stddef.h>
 #include <stdlib.h>
 
 #include "conv28_pair.h"
@@ -24,6 +25,33 @@ __global__ void __launch_bounds__(kThreads) f28_bwd_k(BwdArgs a) {
   bwd_body<BwdLayout, false>(a, lds, blockIdx.x);
 }
 
+// Hand-off of the step's Adam constants to the next launch (PairCtl.adamc,
+// null in eval launches): one thread of the workgroup that owns sample 0's
+// backward -- the solo body, or role 0 of its pair; exactly one per training
+// launch -- at its very end, where nothing else is live. Nothing writes
+// TrainState during this launch (the next one advances it), and the kernel
+// boundary publishes the buffer. The three pointers are re-read from the
+// kernel-argument segment through an address the compiler cannot match with
+// the entry loads: taken from fa / pc they stayed in SGPRs across the whole
+// kernel (98 -> 124 SGPR spills).
+struct StepKargs {
+  FwdArgs fa;
+  BwdArgs ba;
+  PairCtl pc;
+};
+__device__ __forceinline__ void adamc_handoff(int n) {
+  if (n != 0 || threadIdx.x != 0) return;
+  using kchar = const __attribute__((address_space(4))) char;
+  kchar* k = (kchar*)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(k));
+  using kptr = const __attribute__((address_space(4))) unsigned long long;
+  AdamC* out = (AdamC*)*(kptr*)(k + offsetof(StepKargs, pc) + offsetof(PairCtl, adamc));
+  if (!out) return;
+  const TrainState* st = (const TrainState*)*(kptr*)(k + offsetof(StepKargs, fa) + offsetof(FwdArgs, st));
+  const HParams* hp = (const HParams*)*(kptr*)(k + offsetof(StepKargs, fa) + offsetof(FwdArgs, hp));
+  *out = adam_consts_next(st, hp);
+}
+
 __global__ void __launch_bounds__(kThreads) f28_step_k(FwdArgs fa, BwdArgs ba, PairCtl pc) {
   __shared__ __attribute__((aligned(16))) uint8_t lds[StepLayout::LDS];
   if (pc.acquire) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
@@ -33,6 +61,7 @@ __global__ void __launch_bounds__(kThreads) f28_step_k(FwdArgs fa, BwdArgs ba, P
     if (!fa.train) return;  // eval: forward only
     lds_barrier();
     bwd_body<StepLayout, true>(ba, lds, n);
+    adamc_handoff(n);
     return;
   }
   // pairing (see conv28_pair.h): ticket at entry, the leader's solo claim
@@ -74,6 +103,7 @@ __global__ void __launch_bounds__(kThreads) f28_step_k(FwdArgs fa, BwdArgs ba, P
     if (!fa.train) return;  // eval: forward only
     lds_barrier();
     bwd_body<StepLayout, true>(ba, lds, n);
+    adamc_handoff(n);
     return;
   }
   if (pc.delay_us < 0 && mode == kModeRole1 && n == 0) {  // tests: a paired half that stalls (sweep timeout)
@@ -84,6 +114,7 @@ __global__ void __launch_bounds__(kThreads) f28_step_k(FwdArgs fa, BwdArgs ba, P
     lds_barrier();
   }
   pair_rest<StepLayout>(lds, n, mode == kModeRole1 ? 1 : 0);
+  if (mode == kModeRole0) adamc_handoff(n);
 }
 
 }  // namespace f28
@@ -215,7 +246,7 @@ int mdt_f28_forward_pair(const long long* p, const long long* pp, int B, int M, 
 // One launch per training step: forward then backward, two workgroups per
 // sample when `pair` (pp = pair table), else one.
 int mdt_f28_step(const long long* pf, const long long* pb, const long long* pp, int B, int M, unsigned stream,
-                 int pair, int delay_us, hipStream_t s) {
+                 int pair, int delay_us, float* adamc, hipStream_t s) {
   if (M <= 0 || M > B) return 1;
   f28::FwdArgs fa{};
   fill_fwd(fa, pf, B, stream, 1);
@@ -225,6 +256,7 @@ int mdt_f28_step(const long long* pf, const long long* pb, const long long* pp, 
   pc.M = M;
   pc.pair = pair ? 1 : 0;
   pc.delay_us = delay_us;
+  pc.adamc = reinterpret_cast<AdamC*>(adamc);  // 64 B, 16-B aligned (checked by the caller)
   static const int acq = [] {
     const char* e = getenv("MDT_F28_ACQ");
     return e && e[0] == '1' ? 1 : 0;

@@ -54,6 +54,8 @@ struct PairCtl {
                            //        < 0 sample 0's role-1 half stalls -delay_us after pairing (forces a
                            //        sweep timeout of its partner: `err` bit 0)
   int acquire;             // diagnostic (MDT_F28_ACQ=1): agent-scope acquire fence at kernel entry
+  AdamC* adamc;            // training launches, null = off: receives the Adam constants of the step the NEXT
+                           // launch advances to (adam_consts_next), for the Adam epilogues of that launch
 };
 
 // granule offsets inside one (sample, role) slab

@@ -115,6 +115,7 @@ enum JobKindBase : int {
   kJobWgrad = 2000,      // + cfg              (bf16, vector gathers)
   kJobWgradThin = 2050,  // + 20*f32 + cfg     (per-element gathers)
   kJobThinWgM = 2100,    // + f32               (MFMA single-channel weight gradient, conv_thin_wg.h)
+  kJobWgradAdam = 2200,  // + cfg (0, 1)       (kJobWgrad of one m-split with Adam in its epilogue)
   kJobThinConv = 3000,   // + CO + 100*f32
   kJobThinTconv = 4000,  // + CO
   kJobColsum = 5000,

@@ -4,6 +4,7 @@
 #pragma once
 #include <stdlib.h>
 
+#include "adam_common.h"
 #include "common.h"
 #include "conv_igemm.h"
 
@@ -602,10 +603,153 @@ __device__ __forceinline__ void wgrad_epilogue(const WgArgs& a, f32x4 (&acc)[TC:
 template <class TC>
 constexpr int wgrad_lds_bytes() { return 2 * (64 * TC::BM * 2 + 64 * TC::BN * 2); }
 
+// ------------------------------------------------- Adam in the epilogue ----
+// A weight gradient that runs ONE m-split holds the whole gradient element in
+// a register in its epilogue: its partial slab would only be added to zero by
+// the finalize launch. This form applies Adam there instead (the finalize's
+// 16-B arithmetic, grad_finalize_vec4: g = 0 + v keeps its sign of zero, the
+// same adam_update, the same bf16 copy) and writes no slab. The constants come
+// from a device buffer that an EARLIER launch filled (adam_consts_next): the
+// step state itself may be advanced by another job of this launch.
+struct WgAdamArgs {
+  WgArgs w;            // w.out unused
+  float *P, *Mo, *Vo;  // offset to the weight's arena segment: element (co, k') at co * K2 + k'
+  __bf16* w16;
+  const AdamC* c;
+};
+
+// MDT_WGA_HOIST=0 (A/B build): load p, m, v in the epilogue instead of ahead of the m-loop
+#ifndef MDT_WGA_HOIST
+#define MDT_WGA_HOIST 1
+#endif
+// MDT_WGA_SC1=0 (A/B build): plain stores of p, m, v and the bf16 copy
+#ifndef MDT_WGA_SC1
+#define MDT_WGA_SC1 1
+#endif
+
+// The lane's p, m, v at its epilogue positions (the 16-B form of wgrad_epilogue:
+// row lane >> 2 and columns 4 (lane & 3) .. + 3 of each 16x16 fragment). They
+// are known before the m-loop, so the loads are issued there and their round
+// trip hides behind it (3 x FM x FN x 4 VGPRs).
+template <class TC>
+struct WgAdamTile {
+  f32x4 p[TC::FM][TC::FN], m[TC::FM][TC::FN], v[TC::FM][TC::FN];
+
+  // element index of fragment (fm, fn) of this lane, -1 outside the weight
+  static __device__ __forceinline__ int index(const WgArgs& a, int ct, int nt, int w, int lane, int fm, int fn) {
+    const int wm = (w % (TC::WM * TC::WN)) / TC::WN, wn = w % TC::WN;
+    const int orow = ct * TC::BM + wm * (TC::BM / TC::WM) + fm * 16 + (lane >> 2);
+    const int kp = nt * TC::BN + wn * (TC::BN / TC::WN) + fn * 16 + 4 * (lane & 3);
+    return orow < a.d.CO && kp < a.K2 ? orow * a.K2 + kp : -1;
+  }
+  __device__ __forceinline__ void load(const WgAdamArgs& ad, int ct, int nt, int w, int lane) {
+    if (TC::KWS == 2 && w / (TC::WM * TC::WN) != 0) return;  // the k-half-1 waves store nothing
+#pragma unroll
+    for (int fm = 0; fm < TC::FM; ++fm)
+#pragma unroll
+      for (int fn = 0; fn < TC::FN; ++fn) {
+        const int e = index(ad.w, ct, nt, w, lane, fm, fn);
+        if (e >= 0) {
+          p[fm][fn] = *reinterpret_cast<const f32x4*>(ad.P + e);
+          m[fm][fn] = *reinterpret_cast<const f32x4*>(ad.Mo + e);
+          v[fm][fn] = *reinterpret_cast<const f32x4*>(ad.Vo + e);
+        }
+      }
+  }
+};
+
+// The k-half combine of wgrad_epilogue (KWS == 2): the k-half-1 waves hand their
+// accumulators to the k-half-0 waves through LDS (one workgroup barrier).
+template <class TC>
+__device__ __forceinline__ void wgrad_khalf_reduce(f32x4 (&acc)[TC::FM][TC::FN], uint8_t* lds, int w, int lane) {
+  constexpr int WM = TC::WM, WN = TC::WN, KWS = TC::KWS, FM = TC::FM, FN = TC::FN;
+  if constexpr (KWS == 2) {
+    const int wk = w / (WM * WN);
+    float* red = reinterpret_cast<float*>(lds);
+    const int slot = w % (WM * WN);
+    if (wk == 1) {
+#pragma unroll
+      for (int fm = 0; fm < FM; ++fm)
+#pragma unroll
+        for (int fn = 0; fn < FN; ++fn)
+          *reinterpret_cast<f32x4*>(red + (((slot * FM + fm) * FN + fn) * 64 + lane) * 4) = acc[fm][fn];
+    }
+    __syncthreads();
+    if (wk == 0) {
+#pragma unroll
+      for (int fm = 0; fm < FM; ++fm)
+#pragma unroll
+        for (int fn = 0; fn < FN; ++fn)
+          acc[fm][fn] += *reinterpret_cast<const f32x4*>(red + (((slot * FM + fm) * FN + fn) * 64 + lane) * 4);
+    }
+  }
+}
+
+template <class TC>
+__device__ __forceinline__ void wgrad_epilogue_adam(const WgAdamArgs& ad, f32x4 (&acc)[TC::FM][TC::FN],
+                                                    WgAdamTile<TC>& t, uint8_t* lds, int ct, int nt) {
+  constexpr int WM = TC::WM, WN = TC::WN, KWS = TC::KWS, FM = TC::FM, FN = TC::FN;
+  constexpr int STG = 4 * 16 * 20 * 4;  // the wave-private transpose tiles of wgrad_epilogue
+  static_assert(TC::RED_BYTES + STG + 64 <= wgrad_lds_bytes<TC>(), "Adam epilogue staging exceeds wgrad_lds_bytes");
+  const WgArgs& a = ad.w;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wk = w / (WM * WN);
+  // the constants once per workgroup, thread 0 into LDS (as adam_consts_block)
+  AdamC* cs = reinterpret_cast<AdamC*>(lds + TC::RED_BYTES + STG);
+  if (tid == 0) *cs = *ad.c;
+  wgrad_khalf_reduce<TC>(acc, lds, w, lane);
+  if constexpr (KWS == 1) __syncthreads();
+  if (KWS == 2 && wk != 0) return;
+  const AdamC c = *cs;
+  if (!MDT_WGA_HOIST) t.load(ad, ct, nt, w, lane);
+  float* stg = reinterpret_cast<float*>(lds + TC::RED_BYTES) + (w & 3) * 16 * 20;
+  const int bytes = a.d.CO * a.K2 * 4;
+  const __amdgpu_buffer_rsrc_t rp = __builtin_amdgcn_make_buffer_rsrc(ad.P, 0, bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rm = __builtin_amdgcn_make_buffer_rsrc(ad.Mo, 0, bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rv = __builtin_amdgcn_make_buffer_rsrc(ad.Vo, 0, bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(ad.w16, 0, bytes / 2, 0x00020000);
+  typedef unsigned uvec4 __attribute__((ext_vector_type(4)));
+  typedef unsigned uvec2 __attribute__((ext_vector_type(2)));
+  typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+  const int rr = lane >> 2, cq = lane & 3;
+#pragma unroll
+  for (int fm = 0; fm < FM; ++fm)
+#pragma unroll
+    for (int fn = 0; fn < FN; ++fn) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) stg[(4 * (lane >> 4) + r) * 20 + (lane & 15)] = acc[fm][fn][r];
+      __builtin_amdgcn_wave_barrier();
+      const f32x4 gv = *reinterpret_cast<const f32x4*>(stg + rr * 20 + 4 * cq);
+      __builtin_amdgcn_wave_barrier();
+      const int e = WgAdamTile<TC>::index(a, ct, nt, w, lane, fm, fn);
+      if (e < 0) continue;
+      const f32x4 g = f32x4{0.f, 0.f, 0.f, 0.f} + gv;  // slab_sum4 over one slab: z + v
+      f32x4 p = t.p[fm][fn], m = t.m[fm][fn], v = t.v[fm][fn];
+      bf16x4 h;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        float pj = p[j], mj = m[j], vj = v[j];
+        adam_update(pj, mj, vj, g[j], c);
+        p[j] = pj; m[j] = mj; v[j] = vj;
+        h[j] = (__bf16)pj;
+      }
+      // write-through (sc1) like the slab stores they replace: no dirty L2
+      // lines left for the end-of-kernel write-back
+      constexpr int aux = MDT_WGA_SC1 ? 16 /* sc1 */ : 0;
+      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(uvec4, p), rp, e * 4, 0, aux);
+      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(uvec4, m), rm, e * 4, 0, aux);
+      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(uvec4, v), rv, e * 4, 0, aux);
+      __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(uvec2, h), rw, e * 2, 0, aux);
+    }
+}
+
 // Block body of the weight-gradient GEMM (block `bid` of `nblk`); `lds` holds
-// wgrad_lds_bytes<TC>() bytes.
-template <typename XT, bool VEC, class TC>
-__device__ __forceinline__ void wgrad_body(const WgArgs& a, uint8_t* lds, int bid, int nblk) {
+// wgrad_lds_bytes<TC>() bytes. ADAM: `ad` (with a == ad->w, one m-split) and
+// the Adam epilogue above instead of the slab store.
+template <typename XT, bool VEC, class TC, bool ADAM = false>
+__device__ __forceinline__ void wgrad_body(const WgArgs& a, uint8_t* lds, int bid, int nblk,
+                                           const WgAdamArgs* ad = nullptr) {
   constexpr int BM = TC::BM, BN = TC::BN, WM = TC::WM, WN = TC::WN, KWS = TC::KWS, FM = TC::FM, FN = TC::FN;
   constexpr int CPR_A = BM / 8, A_RPP = 256 / CPR_A, A_CH = 64 / A_RPP;
   constexpr int CPR_B = BN / 8, B_RPP = 256 / CPR_B, B_CH = (64 + B_RPP - 1) / B_RPP;
@@ -734,6 +878,8 @@ __device__ __forceinline__ void wgrad_body(const WgArgs& a, uint8_t* lds, int bi
 #pragma unroll
   for (int p = 0; p < PF; ++p)
     if (mt0 + p < mt1) gload(mt0 + p, ra_s[p], rb_s[p], okm_s[p]);
+  [[maybe_unused]] WgAdamTile<TC> adt;
+  if constexpr (ADAM && MDT_WGA_HOIST) adt.load(*ad, ct, nt, w, lane);
   if (mt0 < mt1) sstore(0, ra_s[0], rb_s[0], okm_s[0]);
   __syncthreads();
   for (int mb = mt0; mb < mt1; mb += PF) {
@@ -750,7 +896,8 @@ __device__ __forceinline__ void wgrad_body(const WgArgs& a, uint8_t* lds, int bi
     }
   }
 
-  wgrad_epilogue<TC>(a, acc, lds, ct, nt, split);
+  if constexpr (ADAM) wgrad_epilogue_adam<TC>(*ad, acc, adt, lds, ct, nt);
+  else wgrad_epilogue<TC>(a, acc, lds, ct, nt, split);
 }
 
 template <typename XT, bool VEC, class TC>

@@ -223,6 +223,14 @@ __device__ __forceinline__ void run_multi_job(const JobBlob& j, uint8_t* lds, in
       run_wg_cfg<3, W3>(j, lds, lb) || run_wg_cfg<4, W4>(j, lds, lb) || run_wg_cfg<5, W5>(j, lds, lb))
     return;
   switch (j.kind) {
+    // single-split Linear weight gradients of the fused 28x28 step with Adam in
+    // their epilogue (conv_igemm_dev.h WgAdamArgs): the two tile shapes they plan to
+    case kJobWgradAdam:
+      wgrad_body<__bf16, true, W0, true>(job_args<WgAdamArgs>(j).w, lds, lb, j.nblk, &job_args<WgAdamArgs>(j));
+      break;
+    case kJobWgradAdam + 1:
+      wgrad_body<__bf16, true, W1, true>(job_args<WgAdamArgs>(j).w, lds, lb, j.nblk, &job_args<WgAdamArgs>(j));
+      break;
     case kJobLossStep: JLossStep::run(j, lds, lb); break;
     case kJobLoss: JLoss::run(j, lds, lb); break;
     case kJobFinalize:
@@ -344,6 +352,7 @@ __host__ inline bool multi_kind_ok(int k) {
   if (k >= kJobWgrad && k <= kJobWgrad + 5) return true;
   if (k >= kJobWgradThin && k <= kJobWgradThin + 5) return true;
   if (k >= kJobWgradThin + 20 && k <= kJobWgradThin + 25) return true;
+  if (k == kJobWgradAdam || k == kJobWgradAdam + 1) return true;
   return k == kJobLossStep || k == kJobLoss || k == kJobFinalize || k == kJobColsum || k == kJobComm ||
          k == kJobGather;
 }
@@ -560,6 +569,30 @@ int mdt_job_wgrad(JobBlob* j, const void* G16, const void* X, int x_is_f32, Conv
   else if (!q.thin) j->kind = x_is_f32 ? 0 : kJobWgrad + q.cfg;
   else j->kind = kJobWgradThin + (x_is_f32 ? 20 : 0) + q.cfg;
   j->nblk = q.cotiles * q.ktiles * q.nsplit;
+  put_args(j, a);
+  return 0;
+}
+
+// The weight gradient as a job that applies Adam in its epilogue and writes no
+// slab (jobs_multi_k only). P / Mo / Vo / w16 point at the weight's arena
+// segment; `adamc` at the AdamC an earlier launch stored (adam_consts_next).
+// Returns 1 when the layer has no such form: more than one m-split, a thin or
+// f32 input, a tile shape other than 64x64 / 64x32, rows not 16-B aligned.
+int mdt_job_wgrad_adam(JobBlob* j, const void* G16, const void* X, int x_is_f32, ConvDesc d, float* P, float* Mo,
+                       float* Vo, void* w16, const float* adamc) {
+  WgAdamArgs a{};
+  WgradPlan q;
+  if (!P || !Mo || !Vo || !w16 || !adamc || x_is_f32) return 1;
+  if (build_wgrad(G16, X, d, nullptr, &a.w, &q)) return 1;
+  if (q.thin || q.cfg < 0 || q.cfg > 1 || q.nsplit != 1 || (q.K2 & 3)) return 1;
+  if ((long long)d.CO * q.K2 >= (1ll << 28)) return 1;  // byte offsets in 32 bits
+  if (((uintptr_t)P | (uintptr_t)Mo | (uintptr_t)Vo) & 15 || ((uintptr_t)w16 & 7)) return 1;
+  a.P = P; a.Mo = Mo; a.Vo = Vo;
+  a.w16 = reinterpret_cast<__bf16*>(w16);
+  a.c = reinterpret_cast<const AdamC*>(adamc);
+  memset(j, 0, sizeof(*j));
+  j->kind = kJobWgradAdam + q.cfg;
+  j->nblk = q.cotiles * q.ktiles;
   put_args(j, a);
   return 0;
 }

@@ -64,6 +64,8 @@ int mdt_combine_reparam_bwd(const float* slab, int ks, const float* mulv, const 
                             void* dmulv16, float* dz, int B, int Z, const float* klw, const float* fbw,
                             hipStream_t s);
 int mdt_job_wgrad(mdt::JobBlob* j, const void* G16, const void* X, int x_is_f32, mdt::ConvDesc d, float* out);
+int mdt_job_wgrad_adam(mdt::JobBlob* j, const void* G16, const void* X, int x_is_f32, mdt::ConvDesc d, float* P,
+                       float* Mo, float* Vo, void* w16, const float* adamc);
 int mdt_job_thin_conv(mdt::JobBlob* j, const void* X, int x_is_f32, const float* Wf, mdt::ConvDesc d,
                       const float* bias, int relu, void* y16, const void* omask, float* colsum, const int* idx,
                       void* st, const void* hp, int B, float* xb);
@@ -79,7 +81,7 @@ int mdt_f28_forward(const long long* p, int B, int M, unsigned stream, int train
 int mdt_f28_forward_pair(const long long* p, const long long* pp, int B, int M, unsigned stream, hipStream_t s);
 int mdt_f28_backward(const long long* p, int M, const void* st, hipStream_t s);
 int mdt_f28_step(const long long* pf, const long long* pb, const long long* pp, int B, int M, unsigned stream,
-                 int pair, int delay_us, hipStream_t s);
+                 int pair, int delay_us, float* adamc, hipStream_t s);
 int mdt_f28_pair_words();
 int mdt_launch_job1(const mdt::JobBlob* j, hipStream_t s);
 }
@@ -218,7 +220,20 @@ void igemm(int64_t mode, const at::Tensor& A, const at::Tensor& B16, const std::
      "igemm");
 }
 
-void wgrad(const at::Tensor& G16, const at::Tensor& X, const std::vector<int64_t>& dv, at::Tensor out, Job* job) {
+// The 64-byte device buffer that hands one AdamC from the step kernel to the
+// Adam epilogues of the next launch.
+static float* adamc_ptr(const at::Tensor& t, int dev, const char* who) {
+  TORCH_CHECK(t.is_cuda() && t.get_device() == dev && t.is_contiguous() && t.scalar_type() == torch::kFloat32 &&
+                  t.numel() >= 16 && reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0,
+              who, ": adamc must be a contiguous 16-B aligned f32 tensor of >= 16 elements on the launch's device");
+  return t.data_ptr<float>();
+}
+
+// `adam` (jobs only) = [P, m, v, w16] arenas with `adam_off` the weight's arena
+// offset and `adamc` the constants buffer: the job applies Adam to the weight
+// in its epilogue instead of writing `out` (single m-split plans only).
+void wgrad(const at::Tensor& G16, const at::Tensor& X, const std::vector<int64_t>& dv, at::Tensor out, Job* job,
+           const std::vector<at::Tensor>& adam, int64_t adam_off, const c10::optional<at::Tensor>& adamc) {
   const ConvDesc d = desc(dv);
   check_bf16(G16, "G16");
   check_f32(out, "out");
@@ -230,6 +245,25 @@ void wgrad(const at::Tensor& G16, const at::Tensor& X, const std::vector<int64_t
   TORCH_CHECK(X.numel() >= (int64_t)d.N * d.H * d.W * d.C, "X too small");
   TORCH_CHECK(out.numel() >= (int64_t)info[6] * d.CO * d.KH * d.KW * d.C, "wgrad out too small for ", info[6],
               " partial slabs");
+  if (!adam.empty()) {
+    const int64_t numel = (int64_t)d.CO * d.KH * d.KW * d.C;
+    TORCH_CHECK(job != nullptr && !f32, "wgrad: the Adam epilogue exists for bf16 weight-gradient jobs only");
+    TORCH_CHECK(adam.size() == 4 && adamc.has_value() && adamc->defined(), "wgrad: adam = [P, m, v, w16] and adamc");
+    TORCH_CHECK(info[6] == 1, "wgrad: the Adam epilogue needs a single m-split plan, got ", info[6]);
+    TORCH_CHECK(adam_off >= 0 && adam_off % 4 == 0 && numel % 4 == 0, "wgrad: adam_off and the weight size must be multiples of 4");
+    const int dev = G16.get_device();
+    for (int i = 0; i < 4; ++i) {
+      TORCH_CHECK(adam[i].is_cuda() && adam[i].get_device() == dev && adam[i].is_contiguous() &&
+                      adam[i].scalar_type() == (i < 3 ? torch::kFloat32 : torch::kBFloat16) &&
+                      adam[i].numel() >= adam_off + numel && reinterpret_cast<uintptr_t>(adam[i].data_ptr()) % 16 == 0,
+                  "wgrad: adam[", i, "] must be a contiguous 16-B aligned arena holding the weight at adam_off");
+    }
+    rc(mdt_job_wgrad_adam(&job->main, G16.data_ptr(), X.data_ptr(), f32, d, adam[0].data_ptr<float>() + adam_off,
+                          adam[1].data_ptr<float>() + adam_off, adam[2].data_ptr<float>() + adam_off,
+                          static_cast<char*>(adam[3].data_ptr()) + 2 * adam_off, adamc_ptr(*adamc, dev, "wgrad")),
+       "job_wgrad_adam");
+    return;
+  }
   if (job) {
     rc(mdt_job_wgrad(&job->main, G16.data_ptr(), X.data_ptr(), f32, d, out.data_ptr<float>()), "job_wgrad");
     return;
@@ -637,10 +671,12 @@ void f28_backward(const std::vector<c10::optional<at::Tensor>>& t, int64_t M, co
 // Forward + backward of one training step in ONE launch (f28_step_k). With
 // `pair` (three tensors: exchange granules int64 [B][2][f28_pair_words()],
 // pairing words int32 [B], error word int32 [1], all zero-initialised) the
-// launch runs two workgroups per sample.
+// launch runs two workgroups per sample. `adamc` (optional, f32 [16]): receives
+// the Adam constants of the step that the following launch advances to, for
+// weight-gradient jobs that apply Adam in it (wgrad's `adam`).
 void f28_step(const std::vector<c10::optional<at::Tensor>>& tf, const std::vector<c10::optional<at::Tensor>>& tb,
               int64_t B, int64_t M, int64_t stream, const std::vector<c10::optional<at::Tensor>>& pair,
-              int64_t pair_delay_us) {
+              int64_t pair_delay_us, const c10::optional<at::Tensor>& adamc) {
   TORCH_CHECK(M > 0 && M <= B, "f28_step: bad M ", M, " for B ", B);
   f28_check_data(tf, B);
   const int dev = tf[0].has_value() ? (int)tf[0]->device().index() : 0;
@@ -648,8 +684,10 @@ void f28_step(const std::vector<c10::optional<at::Tensor>>& tf, const std::vecto
   const auto pb = f28_ptrs(tb, f28_bwd_slots(), M, dev);
   std::vector<long long> pp;
   if (!pair.empty()) pp = f28_pair_ptrs(pair, M, dev);
+  float* ac = nullptr;
+  if (adamc.has_value() && adamc->defined()) ac = adamc_ptr(*adamc, dev, "f28_step");
   rc(mdt_f28_step(pf.data(), pb.data(), pp.empty() ? nullptr : pp.data(), (int)B, (int)M, (unsigned)stream,
-                  pp.empty() ? 0 : 1, (int)pair_delay_us, cur()),
+                  pp.empty() ? 0 : 1, (int)pair_delay_us, ac, cur()),
      "f28_step");
 }
 
@@ -884,14 +922,15 @@ void bind_conv(pybind11::module& m) {
   m.def("f28_pair_words", &mdt_f28_pair_words);
   m.def("f28_step", &f28_step, py::arg("fwd_tensors"), py::arg("bwd_tensors"), py::arg("B"), py::arg("M"),
         py::arg("stream"), py::arg("pair") = std::vector<c10::optional<at::Tensor>>{},
-        py::arg("pair_delay_us") = 0);
+        py::arg("pair_delay_us") = 0, py::arg("adamc") = py::none());
   m.def("igemm", &igemm, py::arg("mode"), py::arg("A"), py::arg("B16"), py::arg("desc"), py::arg("bias"),
         py::arg("relu"), py::arg("y16"), py::arg("y32"), py::arg("omask") = py::none(),
         py::arg("colsum") = py::none(), py::arg("ws") = py::none(), py::arg("job") = py::none(),
         py::arg("combine") = true, py::arg("a_slab") = py::none(), py::arg("a_ks") = 0,
         py::arg("a_bias") = py::none(), py::arg("a_relu") = false, py::arg("a_out16") = py::none(),
         py::arg("fwd") = false);
-  m.def("wgrad", &wgrad, py::arg("G16"), py::arg("X"), py::arg("desc"), py::arg("out"), py::arg("job") = py::none());
+  m.def("wgrad", &wgrad, py::arg("G16"), py::arg("X"), py::arg("desc"), py::arg("out"), py::arg("job") = py::none(),
+        py::arg("adam") = std::vector<at::Tensor>{}, py::arg("adam_off") = 0, py::arg("adamc") = py::none());
   m.def("colsum", &colsum, py::arg("G16"), py::arg("M"), py::arg("N"), py::arg("rows_per"), py::arg("slab"),
         py::arg("job") = py::none());
   m.def("thin_conv", &thin_conv, py::arg("X"), py::arg("Wf"), py::arg("desc"), py::arg("bias"), py::arg("relu"),

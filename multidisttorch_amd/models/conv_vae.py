@@ -555,6 +555,14 @@ class ConvVaeTrainer(VaeTrainerBase):
             # producers' store drains slow the weight gradients 30-80 %,
             # profiles/r6_fin_merge), so off by default
             self.f28_fin_merge = os.getenv("MDT_F28_FIN_MERGE", "0") == "1"
+            # MDT_F28_EPI_ADAM=1: the two single-split Linear weight gradients
+            # (enc_head, dec_fc: 81 % of the parameters) apply Adam in their
+            # epilogues and write no partial slab; the finalize launch loses
+            # their units. The step kernel hands the step's Adam constants over
+            # in f28_adamc (adam_common.h adam_consts_next). Bitwise the
+            # two-launch tail (tests/gpu/test_f28_epilogue_adam.py)
+            self.f28_epi_adam = os.getenv("MDT_F28_EPI_ADAM", "1") != "0"
+            self.f28_adamc = torch.zeros(16, **f32)  # one AdamC (64 B), rewritten by every training launch
             words, self._dep_err_idx = self.C.jobs_dep_layout()
             self.f28_dep = torch.zeros(words, dtype=torch.int32, device=dev)  # counters, zero between launches
         self._cast_weights()
@@ -1177,8 +1185,43 @@ class ConvVaeTrainer(VaeTrainerBase):
                  nunits=len(units), layer_units=layer_units, first_dec=first_dec,
                  dec_pack=dec_pack.to(dev), dec_grid=dec_grid, enc_pack=enc_pack.to(dev), enc_grid=enc_grid)
         p["names"] = names
+        p["epi_src"] = (M, srcs, segs, units)  # _epi_plan28, built on first use
         self._plans28[M] = p
         return p
+
+    _EPI_ADAM28 = ("enc_head", "dec_fc")
+
+    def _epi_plan28(self, p):
+        """Second job table and finalize unit list of the fused 28x28 step
+        (built on first use, then cached in the plan): the Linear layers'
+        weight gradients as jobs that apply Adam in their epilogue, and the
+        finalize without those two weight segments (their biases and every
+        other layer stay). None when a layer's weight gradient runs more than
+        one m-split at this M (its slabs then need the finalize's reduction)."""
+        if "epi" not in p:
+            p["epi"] = self._build_epi_plan28(p, *p["epi_src"])
+        return p["epi"]
+
+    def _build_epi_plan28(self, p, M, srcs, segs, units):
+        C, dev = self.C, self.device
+        L = {l.name: l for l in self.spec}
+        seg_of = {l.name: 2 * i for i, l in enumerate(self.spec)}  # _seg_rows: weight, bias per layer
+        for n in self._EPI_ADAM28:
+            if p["slabs"][n + ".weight"][1] != 1 or segs[seg_of[n]][0] % 4 or segs[seg_of[n]][1] % 4:
+                return None
+        jobs = list(p["jobs"])
+        for n in self._EPI_ADAM28:
+            G, Xw = srcs[n]
+            j = C.Job()
+            C.wgrad(G, Xw, self._desc(L[n], M), p["slabs"][n + ".weight"][0], job=j,
+                    adam=[self.params, self.exp_avg, self.exp_avg_sq, self.w16], adam_off=segs[seg_of[n]][0],
+                    adamc=self.f28_adamc)
+            jobs[p["names"].index(n)] = j
+        skip = {seg_of[n] for n in self._EPI_ADAM28}
+        eunits = [u for u in units if u[0] not in skip]
+        pack, grid = C.pack_jobs_multi(jobs)
+        return dict(jobs=jobs, jobs_pack=pack.to(dev), jobs_grid=grid,
+                    units=C.make_grad_units(eunits, dev.index or 0), nunits=len(eunits))
 
     # finalize jobs of the merged launch, ordered by when their layer's weight
     # gradient completes (profiles/r6_jobs28: dec_fc 5.4, enc_head 5.8, enc1
@@ -1227,24 +1270,32 @@ class ConvVaeTrainer(VaeTrainerBase):
         """Fused 28x28 step: forward + backward-data (one launch: f28_step_k,
         or two with MDT_F28_MERGE=0) || weight gradients + loss/step ||
         finalize + Adam (DDP: finalize without Adam, bucket all-reduce, then
-        Adam + bf16 cast)."""
+        Adam + bf16 cast). Without a reducer the two Linear layers' weight
+        gradients apply Adam themselves (MDT_F28_EPI_ADAM, _epi_plan28) and
+        the finalize launch covers the rest."""
         C, p, st = self.C, self._plan28(M), self.state
+        red = self.reducer
+        # Adam in the Linear weight gradients' epilogues: chosen per call (tests
+        # flip the switches between steps of one trainer). Only then does the
+        # step kernel get the buffer to hand the step's Adam constants over in
+        epi = (self._epi_plan28(p) if self.f28_epi_adam and red is None and self.f28_merge
+               and not self.f28_fin_merge and not self.f28_skip_adam else None)
         if self.f28_merge:
             C.f28_step(p["fwd"], p["bwd"], self.B, M, self.rng_stream,
                        pair=[self.f28_xg, self.f28_pairw, self.f28_err] if self.f28_pair else [],
-                       pair_delay_us=self.f28_pair_delay_us)
+                       pair_delay_us=self.f28_pair_delay_us, **({"adamc": self.f28_adamc} if epi else {}))
         else:
             C.f28_forward(p["fwd"], self.B, M, self.rng_stream, True)
             C.f28_backward(p["bwd"], M, state=st.train_state)
-        red = self.reducer
         if red is None:
             if self.f28_fin_merge:
                 pack, grid, _, _ = self._merged_pack28(p)
                 C.launch_jobs_multi(pack, grid, dep=True)
                 return
-            C.launch_jobs_multi(p["jobs_pack"], p["jobs_grid"])
-            C.grad_finalize(self.params, self.grads, self.exp_avg, self.exp_avg_sq, self.w16, p["segs"], p["units"],
-                            p["nunits"], st.train_state, st.hparams, not self.f28_skip_adam,
+            q = epi or p
+            C.launch_jobs_multi(q["jobs_pack"], q["jobs_grid"])
+            C.grad_finalize(self.params, self.grads, self.exp_avg, self.exp_avg_sq, self.w16, p["segs"], q["units"],
+                            q["nunits"], st.train_state, st.hparams, not self.f28_skip_adam,
                             gather=([self._data[0], self._data[1], self.f28_xn, self.f28_xtag]
                                     if self.f28_prefetch else []), gather_B=self.B)
             return
