@@ -23,7 +23,6 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=6)
     ap.add_argument("--json", default=None)
-    ap.add_argument("--merged", action="store_true", help="the merged table: + gather + per-layer finalize jobs")
     ap.add_argument("--no-epi", action="store_true",
                     help="the plain table even when the trainer applies Adam in the Linear epilogues (MDT_F28_EPI_ADAM)")
     a = ap.parse_args()
@@ -40,26 +39,17 @@ def main():
     torch.cuda.synchronize()
     C, p = tr.C, tr._plan28(B)
     names = ["enc1", "enc2", "enc_head", "dec_fc", "dec1", "dec2", "loss"]
-    if a.merged:
-        tr.f28_fin_merge = True  # MDT_F28_FIN_MERGE's form for this trainer
-        _, _, jobs, wait = tr._merged_pack28(p)
-        names += (["gather"] if tr.f28_prefetch else []) + ["fin_" + n for n in tr._FIN_ORDER28]
-    else:
-        tr.f28_fin_merge = False
-        if a.no_epi:
-            tr.f28_epi_adam = False
-        q = tr._epi_plan28(p) if tr.f28_epi_adam else None  # the table _step28 launches
-        jobs, wait = (q or p)["jobs"], []
-        print("table:", "Adam in the enc_head / dec_fc epilogues" if q else "plain")
+    if a.no_epi:
+        tr.f28_epi_adam = False
+    q = tr._epi_plan28(p) if tr.f28_epi_adam else None  # the table _step28 launches
+    jobs = (q or p)["jobs"]
+    print("table:", "Adam in the enc_head / dec_fc epilogues" if q else "plain")
     nblk = [j.nblk for j in jobs]
     grid0 = sum(nblk)
     stamps = torch.zeros(2 * grid0, dtype=torch.int64, device=dev)
-    pack, grid = C.pack_jobs_multi(jobs, stamps=stamps, wait=wait, dep_ctr=tr.f28_dep if wait else None)
+    pack, grid = C.pack_jobs_multi(jobs, stamps=stamps)
     assert grid == grid0
-    if a.merged:
-        p[("merged", True, bool(tr.f28_prefetch))] = (pack.to(dev), grid, jobs, wait)
-    else:
-        (q or p)["jobs_pack"], (q or p)["jobs_grid"] = pack.to(dev), grid
+    (q or p)["jobs_pack"], (q or p)["jobs_grid"] = pack.to(dev), grid
     runs = []
     for _ in range(a.steps):
         stamps.zero_()

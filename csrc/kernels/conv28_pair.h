@@ -399,16 +399,8 @@ __device__ __forceinline__ void pair_rest(uint8_t* lds, int n, int r) {
 #pragma unroll
     for (int i = 0; i < 8; ++i) wr[0][i] = wh0[i];
     ld_rows(1, wr[1]);
-#ifdef MDT_F28_HALFW_EXP  // timing experiment only (wrong results): half the P3 / Q5 weight bytes
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      wr[2][i] = wr[0][i];
-      wr[3][i] = wr[1][i];
-    }
-#else
     ld_rows(2, wr[2]);
     ld_rows(3, wr[3]);
-#endif
     float d[8];
 #pragma unroll
     for (int c2 = 0; c2 < 4; ++c2)
@@ -822,13 +814,8 @@ __device__ __forceinline__ void pair_rest(uint8_t* lds, int n, int r) {
 #pragma unroll
     for (int e = 0; e < 8; ++e) acc[e] = 0.f;
     bf16x8 wh6[16];  // rows 16..31 of the group: with wh5, all 32 in flight at once
-#ifdef MDT_F28_HALFW_EXP
-#pragma unroll
-    for (int i = 0; i < 16; ++i) wh6[i] = wh5[i];
-#else
 #pragma unroll
     for (int i = 0; i < 16; ++i) wh6[i] = wh_ld(16 + i);
-#endif
     w2r.load(TB(kTW2));  // enc2 tap images: in flight during Q5
 #pragma unroll
     for (int i = 0; i < 32; ++i) {

@@ -267,14 +267,6 @@ __device__ __forceinline__ void dconv_body(const DcArgs& a, uint8_t* lds, int ti
   stage_barrier();
   dc_stamp(a.stamps, 1);
 
-#ifdef MDT_DC_STAGE_STAMPS  // per-stage timeline of the workgroup-leader wave (bench/dconv_stage_stamps.py)
-#define DC_SS(k)                                                                                          \
-  if (a.stamps && threadIdx.x == 0)                                                                        \
-    a.stamps[(size_t)gridDim.x * 8 + ((size_t)blockIdx.x * NSTAGE + st) * 4 + (k)] = __builtin_amdgcn_s_memrealtime();
-#else
-#define DC_SS(k)
-#endif
-#ifndef MDT_DC_STEP_AHEAD
   // Fragments of a whole hand-off group (HS stages) are loaded one group
   // ahead: each wave holds its NF = HS x KPW k-steps of group g in registers
   // (set `cur`) while it reads those of group g + 1 (set `nxt`). Per group:
@@ -294,18 +286,14 @@ __device__ __forceinline__ void dconv_body(const DcArgs& a, uint8_t* lds, int ti
   auto step = [&](int g, const bf16x8(&ca)[NF][FM], const bf16x8(&cb)[NF][FN], bf16x8(&na)[NF][FM],
                   bf16x8(&nb_)[NF][FN]) {
     const int st = g * HS;
-    DC_SS(0);
 #pragma unroll
     for (int i = 0; i < KH; ++i) mma(ca[i], cb[i]);
     __builtin_amdgcn_sched_barrier(0);
-    DC_SS(1);
     if (g + 1 < NG) {
       // issued: stages < min(NSTAGE, st + S); needed: stages < st + 2 HS
       const int ahead = (st + S < NSTAGE ? st + S : NSTAGE) - st - 2 * HS;
       dc_wait_stages<NBW, S - 1>(ahead);
-      DC_SS(2);
       stage_barrier();
-      DC_SS(3);
 #pragma unroll
       for (int h = 0; h < HS; ++h)
         if (st + h + S < NSTAGE) issue_stage(st + h + S);
@@ -322,69 +310,6 @@ __device__ __forceinline__ void dconv_body(const DcArgs& a, uint8_t* lds, int ti
     step(g, fa0, fb0, fa1, fb1);
     if (g + 1 < NG) step(g + 1, fa1, fb1, fa0, fb0);
   }
-#else
-  // Fragments are loaded one k-step ahead of the MFMAs that use them, so LDS
-  // latency hides under the previous step's MFMAs; the ring hand-off (wait for
-  // stage st+1, barrier, refill slot st % S with stage st+S) sits at the last
-  // k-step of a stage, after its fragments are already in registers.
-  // sched_barrier(0) pins that order: left alone, the scheduler sinks each
-  // fragment load next to its MFMA and every k-step waits out the full LDS
-  // latency (s_waitcnt lgkmcnt(0) right before each MFMA).
-  bf16x8 afA[FM], bfA[FN], afB[FM], bfB[FN];
-  if constexpr (CF::KS == 2) {
-    // group g: k-steps kg0, kg0 + 1 of every stage (two MFMA steps per stage and wave)
-    load_frags(0, kg0, afA, bfA);
-#pragma unroll 1
-    for (int st = 0; st < NSTAGE; ++st) {
-      load_frags(st, kg0 + 1, afB, bfB);
-      __builtin_amdgcn_sched_barrier(0);
-      mma(afA, bfA);
-      __builtin_amdgcn_sched_barrier(0);
-      if (st + 1 < NSTAGE) {
-        const int ahead = NSTAGE - 2 - st;
-        dc_wait_stages<NBW, S - 1>(ahead < S - 2 ? ahead : S - 2);
-        stage_barrier();
-        if (st + S < NSTAGE) issue_stage(st + S);
-        load_frags(st + 1, kg0, afA, bfA);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-      mma(afB, bfB);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  } else {
-  load_frags(0, 0, afA, bfA);
-#pragma unroll 1
-  for (int st = 0; st < NSTAGE; ++st) {
-    DC_SS(0);
-    load_frags(st, 1, afB, bfB);
-    __builtin_amdgcn_sched_barrier(0);
-    mma(afA, bfA);
-    __builtin_amdgcn_sched_barrier(0);
-    load_frags(st, 2, afA, bfA);
-    __builtin_amdgcn_sched_barrier(0);
-    mma(afB, bfB);
-    __builtin_amdgcn_sched_barrier(0);
-    load_frags(st, 3, afB, bfB);
-    __builtin_amdgcn_sched_barrier(0);
-    mma(afA, bfA);
-    __builtin_amdgcn_sched_barrier(0);
-    DC_SS(1);
-    if (st + 1 < NSTAGE) {
-      const int ahead = NSTAGE - 2 - st;
-      dc_wait_stages<NBW, S - 1>(ahead < S - 2 ? ahead : S - 2);
-      DC_SS(2);
-      stage_barrier();
-      DC_SS(3);
-      if (st + S < NSTAGE) issue_stage(st + S);
-      load_frags(st + 1, 0, afA, bfA);
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    mma(afB, bfB);
-    __builtin_amdgcn_sched_barrier(0);
-  }
-  }
-#endif
-#undef DC_SS
   dc_stamp(a.stamps, 2);
 
   // ---- epilogue, per 32-row slice: fragments -> wave-private LDS staging ->

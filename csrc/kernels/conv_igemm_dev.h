@@ -618,15 +618,6 @@ struct WgAdamArgs {
   const AdamC* c;
 };
 
-// MDT_WGA_HOIST=0 (A/B build): load p, m, v in the epilogue instead of ahead of the m-loop
-#ifndef MDT_WGA_HOIST
-#define MDT_WGA_HOIST 1
-#endif
-// MDT_WGA_SC1=0 (A/B build): plain stores of p, m, v and the bf16 copy
-#ifndef MDT_WGA_SC1
-#define MDT_WGA_SC1 1
-#endif
-
 // The lane's p, m, v at its epilogue positions (the 16-B form of wgrad_epilogue:
 // row lane >> 2 and columns 4 (lane & 3) .. + 3 of each 16x16 fragment). They
 // are known before the m-loop, so the loads are issued there and their round
@@ -702,7 +693,6 @@ __device__ __forceinline__ void wgrad_epilogue_adam(const WgAdamArgs& ad, f32x4 
   if constexpr (KWS == 1) __syncthreads();
   if (KWS == 2 && wk != 0) return;
   const AdamC c = *cs;
-  if (!MDT_WGA_HOIST) t.load(ad, ct, nt, w, lane);
   float* stg = reinterpret_cast<float*>(lds + TC::RED_BYTES) + (w & 3) * 16 * 20;
   const int bytes = a.d.CO * a.K2 * 4;
   const __amdgpu_buffer_rsrc_t rp = __builtin_amdgcn_make_buffer_rsrc(ad.P, 0, bytes, 0x00020000);
@@ -736,7 +726,7 @@ __device__ __forceinline__ void wgrad_epilogue_adam(const WgAdamArgs& ad, f32x4 
       }
       // write-through (sc1) like the slab stores they replace: no dirty L2
       // lines left for the end-of-kernel write-back
-      constexpr int aux = MDT_WGA_SC1 ? 16 /* sc1 */ : 0;
+      constexpr int aux = 16;  // sc1
       __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(uvec4, p), rp, e * 4, 0, aux);
       __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(uvec4, m), rm, e * 4, 0, aux);
       __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(uvec4, v), rv, e * 4, 0, aux);
@@ -879,7 +869,7 @@ __device__ __forceinline__ void wgrad_body(const WgArgs& a, uint8_t* lds, int bi
   for (int p = 0; p < PF; ++p)
     if (mt0 + p < mt1) gload(mt0 + p, ra_s[p], rb_s[p], okm_s[p]);
   [[maybe_unused]] WgAdamTile<TC> adt;
-  if constexpr (ADAM && MDT_WGA_HOIST) adt.load(*ad, ct, nt, w, lane);
+  if constexpr (ADAM) adt.load(*ad, ct, nt, w, lane);
   if (mt0 < mt1) sstore(0, ra_s[0], rb_s[0], okm_s[0]);
   __syncthreads();
   for (int mb = mt0; mb < mt1; mb += PF) {

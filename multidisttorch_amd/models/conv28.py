@@ -58,14 +58,6 @@ class Fused28Step:
         self.f28_xn = torch.zeros(B * self.D, **f32)
         self.f28_xtag = torch.full((B,), -1, dtype=torch.int32, device=dev)
         self.f28_prefetch = os.getenv("MDT_F28_PREFETCH", "1") != "0"
-        # MDT_F28_FIN_MERGE=1: finalize + Adam (and the prefetch gather)
-        # inside the weight-gradient launch, each layer's units released by
-        # in-launch counters as that layer's weight gradient completes
-        # (conv_jobs.hip JobPackN deps). Bitwise the two-launch tail but
-        # slower (0.079 vs 0.061 ms/step: the waiting workgroups and the
-        # producers' store drains slow the weight gradients 30-80 %,
-        # profiles/r6_fin_merge), so off by default
-        self.f28_fin_merge = os.getenv("MDT_F28_FIN_MERGE", "0") == "1"
         # MDT_F28_EPI_ADAM=1: the two single-split Linear weight gradients
         # (enc_head, dec_fc: 81 % of the parameters) apply Adam in their
         # epilogues and write no partial slab; the finalize launch loses
@@ -74,8 +66,6 @@ class Fused28Step:
         # two-launch tail (tests/gpu/test_f28_epilogue_adam.py)
         self.f28_epi_adam = os.getenv("MDT_F28_EPI_ADAM", "1") != "0"
         self.f28_adamc = torch.zeros(16, **f32)  # one AdamC (64 B), rewritten by every training launch
-        words, self._dep_err_idx = self.C.jobs_dep_layout()
-        self.f28_dep = torch.zeros(words, dtype=torch.int32, device=dev)  # counters, zero between launches
 
     def _invalidate_prefetch(self):
         """The host moved the cursor, the step or the data: rows the last
@@ -92,10 +82,6 @@ class Fused28Step:
         if err:
             msgs.append(f"fused 28x28 step: a paired-workgroup exchange timed out (f28_err={err}); "
                         f"the trial trained on incomplete partial sums")
-        derr = int(self.f28_dep[self._dep_err_idx].item())
-        if derr:
-            msgs.append(f"fused 28x28 step: a finalize job gave up waiting for job {derr - 1} of its launch; "
-                        f"the trial's update used incomplete weight gradients")
         return msgs
 
     def _plan28(self, M):
@@ -192,44 +178,6 @@ class Fused28Step:
         return dict(jobs=jobs, jobs_pack=pack.to(dev), jobs_grid=grid,
                     units=C.make_grad_units(eunits, dev.index or 0), nunits=len(eunits))
 
-    # finalize jobs of the merged launch, ordered by when their layer's weight
-    # gradient completes (profiles/r6_jobs28: dec_fc 5.4, enc_head 5.8, enc1
-    # 7.2, enc2 8.5, dec2 8.8, dec1 9.1 us into the launch)
-    _FIN_ORDER28 = ("dec_fc", "enc_head", "enc1", "enc2", "dec2", "dec1")
-
-    def _merged_pack28(self, p):
-        """One jobs_multi_k table for the whole optimizer tail of the fused
-        28x28 step: the six weight gradients and the loss/step job, then the
-        next-batch gather (waits for the loss job: it needs the advanced
-        cursor), then one finalize+Adam job per layer (waits for that layer's
-        weight gradient and for the loss job's advanced step). Each waiting
-        workgroup is released by in-launch counters (conv_jobs.hip JobPackN),
-        so a layer's update runs while later layers' gradients are still being
-        computed and the step loses a launch boundary. Bitwise the two-launch
-        form: the same bodies, the same per-element summation order."""
-        adam = not self.f28_skip_adam
-        key = ("merged", adam, bool(self.f28_prefetch))
-        hit = p.get(key)
-        if hit is not None:
-            return hit
-        C, st, names = self.C, self.state, p["names"]
-        jobs = list(p["jobs"])  # names order + loss/step
-        loss_i = len(names)
-        wait = [0] * len(jobs)
-        if self.f28_prefetch:
-            jobs.append(self._job(lambda j: C.gather_job(self._data[0], self._data[1], st.train_state, self.f28_xn,
-                                                         self.f28_xtag, self.B, j)))
-            wait.append(1 << loss_i)
-        lu = p["layer_units"]
-        for name in self._FIN_ORDER28:
-            i = self.spec.index(self.by_name[name])
-            jobs.append(self._job(lambda j: self._grad_finalize(p["segs"], p["units"], lu[i], lu[i + 1], adam,
-                                                                job=j, dep=True)))
-            wait.append((1 << names.index(name)) | (1 << loss_i))
-        pack, grid = C.pack_jobs_multi(jobs, wait=wait, dep_ctr=self.f28_dep)
-        hit = p[key] = (pack.to(self.device), grid, jobs, wait)
-        return hit
-
     def _step28(self, M):
         """Fused 28x28 step: forward + backward-data (one launch: f28_step_k,
         or two with MDT_F28_MERGE=0) || weight gradients + loss/step ||
@@ -243,7 +191,7 @@ class Fused28Step:
         # flip the switches between steps of one trainer). Only then does the
         # step kernel get the buffer to hand the step's Adam constants over in
         epi = (self._epi_plan28(p) if self.f28_epi_adam and red is None and self.f28_merge
-               and not self.f28_fin_merge and not self.f28_skip_adam else None)
+               and not self.f28_skip_adam else None)
         if self.f28_merge:
             C.f28_step(p["fwd"], p["bwd"], self.B, M, self.rng_stream,
                        pair=[self.f28_xg, self.f28_pairw, self.f28_err] if self.f28_pair else [],
@@ -252,10 +200,6 @@ class Fused28Step:
             C.f28_forward(p["fwd"], self.B, M, self.rng_stream, True)
             C.f28_backward(p["bwd"], M, state=st.train_state)
         if red is None:
-            if self.f28_fin_merge:
-                pack, grid, _, _ = self._merged_pack28(p)
-                C.launch_jobs_multi(pack, grid, dep=True)
-                return
             q = epi or p
             C.launch_jobs_multi(q["jobs_pack"], q["jobs_grid"])
             self._grad_finalize(p["segs"], q["units"], 0, q["nunits"], not self.f28_skip_adam,

@@ -315,6 +315,21 @@ def test_colsum(M, N, rows_per, native_ext):
     assert torch.equal(_tail_nan(slab, gy * N).view(gy, N), want)
 
 
+def test_multi_job_table_holds_eight_jobs(native_ext):
+    """jobs_multi_k reads eight job starts (kMaxMultiJobs): packing refuses a
+    ninth job, and a full table's grid is the sum of its jobs' workgroups."""
+    C = native_ext
+    G = torch.zeros(8 * 8, dtype=BF16, device=DEV)
+    slabs = [torch.zeros(8, device=DEV) for _ in range(9)]
+    jobs = [C.Job() for _ in range(9)]
+    for j, slab in zip(jobs, slabs):
+        C.colsum(G, 8, 8, 8, slab, job=j)   # the smallest shape: one workgroup
+    with pytest.raises(RuntimeError):
+        C.pack_jobs_multi(jobs)
+    _, grid = C.pack_jobs_multi(jobs[:8])
+    assert grid == sum(j.nblk for j in jobs[:8]) > 0
+
+
 # ---------------------------------------------------------------- adam_cast ----
 def _adam_bufs(total, seed=0):
     """P, G, m, v, w16 as logical views of buffers 4 elements longer (the guard tail), and the buffers."""

@@ -31,7 +31,7 @@ def _trainer(B, epi, **kw):
     kw.setdefault("schedule", Schedule(lr_warmup_steps=3, lr_decay="cosine", lr_decay_steps=60, lr_min_ratio=0.1))
     tr = ConvVaeTrainer(batch_size=B, image=28, device=torch.device("cuda"), backend="hip", seed=4, lr=2e-3,
                         betas=(0.85, 0.97), ema_decay=0.9, **kw)
-    assert tr.f28 and tr.f28_merge and not tr.f28_fin_merge
+    assert tr.f28 and tr.f28_merge
     tr.f28_epi_adam = epi
     return tr
 

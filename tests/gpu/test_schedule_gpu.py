@@ -87,16 +87,13 @@ def _three_way(make, s, steps, tail_M):
     return g, e, o
 
 
-@pytest.mark.parametrize("fin_merge,steps", [("0", 12), ("1", 6)])
-def test_fused28_warmup_anneal_bitwise(native_ext, monkeypatch, fin_merge, steps):
+def test_fused28_warmup_anneal_bitwise(native_ext):
     """The fused 28x28 step (its forward/backward run before the step is
-    advanced and use t = step + 1). MDT_F28_FIN_MERGE=1: Adam in the launch that
-    advances the step, lr_t through the agent-scope load."""
-    monkeypatch.setenv("MDT_F28_FIN_MERGE", fin_merge)
+    advanced and use t = step + 1)."""
     X, idx = _data(256, 784)
-    trs = _three_way(lambda **kw: _conv(X, idx, 32, **kw), WARM, steps, 13)
+    trs = _three_way(lambda **kw: _conv(X, idx, 32, **kw), WARM, 12, 13)
     for tr in trs:
-        assert tr.f28 and tr.f28_fin_merge == (fin_merge == "1")
+        assert tr.f28
         assert int(tr.f28_err.item()) == 0
 
 

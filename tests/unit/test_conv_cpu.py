@@ -74,12 +74,3 @@ def test_latent_size_outside_the_layer_path_domain_raises_at_construction():
     for z in (8, 24, np.int64(128)):
         tr = ConvVaeTrainer(batch_size=4, image=28, z=z, backend="torch", device="cpu", seed=0)
         assert tr.Z == z and tr.named_parameters()["dec_fc.weight"].shape[-1] == z
-
-
-def test_merged_tail_finalizes_every_28x28_layer_once():
-    # MDT_F28_FIN_MERGE's job table (ConvVaeTrainer._merged_pack28) has one
-    # finalize job per layer of the 28x28 model, released by that layer's
-    # weight-gradient job: the order list must name each layer exactly once
-    names = [l.name for l in conv_vae_spec(28)]
-    order = ConvVaeTrainer._FIN_ORDER28
-    assert sorted(order) == sorted(names) and len(order) == len(set(order))
