@@ -1126,8 +1126,7 @@ struct StepLayout {
   static constexpr int D1 = CSB + 32 * 197 * 4;  // bf16 [196][32] dec1 out (P7 input, Q1 mask)
   static constexpr int GA2F = D1;                //   bwd f32 [3136] (D1 dead after Q1)
   static constexpr int Bias = D1 + kFlat * 4;   // f32 [256] small biases (+ a zero chunk at kZero)
-  static constexpr int PTab = Bias + 1024;      // u64 [32] pointer table of the paired body (conv28_pair.h)
-  static constexpr int LDS = PTab + 256;
+  static constexpr int LDS = Bias + 1024;
   static_assert(W1 % 16 == 0 && X % 16 == 0 && G % 16 == 0 && A1 % 16 == 0 && A2 % 16 == 0 && D0 % 16 == 0 &&
                     Dummy % 16 == 0 && Bd % 16 == 0 && CSB % 16 == 0 && D1 % 16 == 0 && LDS <= 163840,
                 "step LDS map");

@@ -30,58 +30,47 @@ __global__ void __launch_bounds__(kThreads) f28_bwd_k(BwdArgs a) {
 // backward -- the solo body, or role 0 of its pair; exactly one per training
 // launch -- at its very end, where nothing else is live. Nothing writes
 // TrainState during this launch (the next one advances it), and the kernel
-// boundary publishes the buffer. The three pointers are re-read from the
-// kernel-argument segment through an address the compiler cannot match with
-// the entry loads: taken from fa / pc they stayed in SGPRs across the whole
-// kernel (98 -> 124 SGPR spills).
-struct StepKargs {
-  FwdArgs fa;
-  BwdArgs ba;
-  PairCtl pc;
-};
+// boundary publishes the buffer. The three pointers come from the
+// kernel-argument segment (kptr, conv28_pair.h): taken from fa / pc they
+// stayed in SGPRs across the whole kernel (98 -> 124 SGPR spills).
 __device__ __forceinline__ void adamc_handoff(int n) {
   if (n != 0 || threadIdx.x != 0) return;
-  using kchar = const __attribute__((address_space(4))) char;
-  kchar* k = (kchar*)__builtin_amdgcn_kernarg_segment_ptr();
-  asm volatile("" : "+s"(k));
-  using kptr = const __attribute__((address_space(4))) unsigned long long;
-  AdamC* out = (AdamC*)*(kptr*)(k + offsetof(StepKargs, pc) + offsetof(PairCtl, adamc));
+  AdamC* out = kptr<AdamC>(offsetof(StepKargs, pc.adamc));
   if (!out) return;
-  const TrainState* st = (const TrainState*)*(kptr*)(k + offsetof(StepKargs, fa) + offsetof(FwdArgs, st));
-  const HParams* hp = (const HParams*)*(kptr*)(k + offsetof(StepKargs, fa) + offsetof(FwdArgs, hp));
-  *out = adam_consts_next(st, hp);
+  *out = adam_consts_next(kptr<const TrainState>(offsetof(StepKargs, fa.st)),
+                          kptr<const HParams>(offsetof(StepKargs, fa.hp)));
 }
 
+static_assert(StepLayout::LDS == 161216, "probe.hip probe_ramp launches with the step kernel's LDS bytes");
+
+// The formal arguments serve the kernel's entry (pairing, P0, P1) only.
+// Everything after P1 -- the paired body and the one solo body -- reads the
+// argument segment where it needs a value, so no argument is live across the
+// kernel.
 __global__ void __launch_bounds__(kThreads) f28_step_k(FwdArgs fa, BwdArgs ba, PairCtl pc) {
   __shared__ __attribute__((aligned(16))) uint8_t lds[StepLayout::LDS];
   if (pc.acquire) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-  if (!pc.pair) {
-    const int n = blockIdx.x;
-    fwd_body<StepLayout>(fa, lds, n);
-    if (!fa.train) return;  // eval: forward only
-    lds_barrier();
-    bwd_body<StepLayout, true>(ba, lds, n);
-    adamc_handoff(n);
-    return;
-  }
   // pairing (see conv28_pair.h): ticket at entry, the leader's solo claim
-  // after P0 (its result is needed only after P1, which both forms share)
-  const int n = (int)blockIdx.x % pc.M;
+  // after P0 (its result is needed only after P1, which both forms share).
+  // A launch without pairs (grid M) enters the solo body the same way.
+  const bool pair = pc.pair != 0;
+  const int n = pair ? (int)blockIdx.x % pc.M : (int)blockIdx.x;
   g32i* word = (g32i*)(pc.pairw + n);
   int ticket = 0, seen = 1;
-  if (pc.delay_us > 0 && (int)blockIdx.x >= pc.M && threadIdx.x == 0) {  // tests: a partner that comes late
-    const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-    while (__builtin_amdgcn_s_memrealtime() - t0 < 100ull * (unsigned)pc.delay_us) __builtin_amdgcn_s_sleep(8);
+  if (pair) {
+    if (pc.delay_us > 0 && (int)blockIdx.x >= pc.M && threadIdx.x == 0) {  // tests: a partner that comes late
+      const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
+      while (__builtin_amdgcn_s_memrealtime() - t0 < 100ull * (unsigned)pc.delay_us) __builtin_amdgcn_s_sleep(8);
+    }
+    if (threadIdx.x == 0) ticket = __hip_atomic_fetch_add(word, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
-  if (threadIdx.x == 0) ticket = __hip_atomic_fetch_add(word, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  fill_ptab<StepLayout>(lds, fa, ba, pc, n);  // read by the paired body after P0's barrier
   fwd_p01<StepLayout>(fa, lds, n, [&] {
-    if (threadIdx.x == 0 && ticket == 0)
+    if (pair && threadIdx.x == 0 && ticket == 0)
       __hip_atomic_compare_exchange_strong(word, &seen, 3, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
                                            __HIP_MEMORY_SCOPE_AGENT);
   });
   int* mode_w = reinterpret_cast<int*>(lds + StepLayout::Scr + 124);  // Scr[31]: unused before P4
-  if (threadIdx.x == 0) {
+  if (pair && threadIdx.x == 0) {
     int mode;
     if (ticket == 0) {
       mode = seen == 1 ? kModeSolo : kModeRole0;  // CAS 1 -> 3 won: solo; saw 2: the partner is in
@@ -96,25 +85,31 @@ __global__ void __launch_bounds__(kThreads) f28_step_k(FwdArgs fa, BwdArgs ba, P
     if (fa.stamps) fa.stamps[blockIdx.x * 16 + 15] = (unsigned long long)mode;
   }
   lds_barrier();
-  const int mode = __builtin_amdgcn_readfirstlane(*mode_w);
+  const int mode = pair ? __builtin_amdgcn_readfirstlane(*mode_w) : (int)kModeSolo;
   if (mode == kModeExit) return;
-  if (mode == kModeSolo) {
-    fwd_rest<StepLayout>(fa, lds, n);
-    if (!fa.train) return;  // eval: forward only
-    lds_barrier();
-    bwd_body<StepLayout, true>(ba, lds, n);
-    adamc_handoff(n);
+  if (__builtin_expect(mode != kModeSolo, 1)) {
+    if (kval<int>(offsetof(StepKargs, pc.delay_us)) < 0 && mode == kModeRole1 && n == 0) {
+      // tests: a paired half that stalls (sweep timeout)
+      if (threadIdx.x == 0) {
+        const unsigned delay = (unsigned)-kval<int>(offsetof(StepKargs, pc.delay_us));
+        const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
+        while (__builtin_amdgcn_s_memrealtime() - t0 < 100ull * delay) __builtin_amdgcn_s_sleep(64);
+      }
+      lds_barrier();
+    }
+    pair_rest<StepLayout>(lds, n, mode == kModeRole1 ? 1 : 0);
+    if (mode == kModeRole0) adamc_handoff(n);
     return;
   }
-  if (pc.delay_us < 0 && mode == kModeRole1 && n == 0) {  // tests: a paired half that stalls (sweep timeout)
-    if (threadIdx.x == 0) {
-      const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-      while (__builtin_amdgcn_s_memrealtime() - t0 < 100ull * (unsigned)(-pc.delay_us)) __builtin_amdgcn_s_sleep(64);
-    }
-    lds_barrier();
-  }
-  pair_rest<StepLayout>(lds, n, mode == kModeRole1 ? 1 : 0);
-  if (mode == kModeRole0) adamc_handoff(n);
+  // The solo body (a launch without pairs, or a leader whose partner was not
+  // resident in time), after the paired path in the code. Its arguments are
+  // read through the segment too.
+  const StepKargs& ka = *(const StepKargs*)(const void*)kargs();
+  fwd_rest<StepLayout>(ka.fa, lds, n);
+  if (!ka.fa.train) return;  // eval: forward only
+  lds_barrier();
+  bwd_body<StepLayout, true>(ka.ba, lds, n);
+  adamc_handoff(n);
 }
 
 }  // namespace f28

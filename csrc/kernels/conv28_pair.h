@@ -39,6 +39,8 @@
 // come out per half, so db2_part is [2][M][64] and the finalize sums 2M rows;
 // everything else each half writes into its own part of the solo layout.
 #pragma once
+#include <stddef.h>
+
 #include "conv28_fused.h"
 
 namespace mdt {
@@ -65,16 +67,17 @@ constexpr unsigned long long kSpinTicks = 25000000ull;  // 0.25 s of s_memrealti
 
 enum : int { kModeSolo = 0, kModeRole0 = 1, kModeRole1 = 2, kModeExit = 3 };
 
-// Pointer table in LDS (StepLayout::PTab): the paired body takes every buffer
-// pointer from here, already offset to its sample, instead of from the kernel
-// arguments. Kept as arguments, the ~60 pointers of FwdArgs + BwdArgs did not
-// fit the 102 SGPRs: the compiler spilled them to VGPR lanes and reloaded a
-// 16-SGPR block (16 v_readlane) around every global store of an epilogue. A
-// table read costs one ds_read_b64 + two readfirstlane per pointer per phase.
-enum : int {
-  kTWh, kTWd, kTW3, kTW2, kTSt, kTHp, kTA2, kTMulv, kTEps, kTZ16, kTD0, kTD1, kTDlog, kTRecon, kTBce, kTKld,
-  kTDb4, kTStamp, kTGd1, kTDb3, kTGd0, kTDbd, kTDmulv, kTDmulv16, kTGa2, kTDb2, kTGa1, kTDb1, kTXg, kTErr,
-  kTInts, kTNum  // kTInts: M | stream << 16 ... packed below
+// The step kernel's argument segment. The paired body takes every buffer
+// pointer from here at the point of use (kptr below), not from the kernel's
+// formal arguments: kept as arguments, the ~60 pointers of FwdArgs + BwdArgs
+// did not fit the 102 SGPRs, and the compiler spilled them to VGPR lanes and
+// reloaded a 16-SGPR block (16 v_readlane) around every global store of an
+// epilogue. A re-read costs one scalar load from the (cached) segment and
+// keeps no SGPR live between phases.
+struct StepKargs {
+  FwdArgs fa;
+  BwdArgs ba;
+  PairCtl pc;
 };
 
 using g64 = __attribute__((address_space(1))) unsigned long long;
@@ -149,59 +152,35 @@ __device__ __forceinline__ void xget(unsigned long long* base, const int (&gi)[N
     }
 }
 
-template <class L, class T>
-__device__ __forceinline__ T* tab(const uint8_t* lds, int i) {
-  const unsigned long long v = reinterpret_cast<const unsigned long long*>(lds + L::PTab)[i];
-  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v), hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
+// Kernel-argument segment of the running kernel (f28_step_k: a StepKargs),
+// through an address the compiler cannot match with the entry loads of the
+// formal arguments: a value loaded through it is loaded where it is used
+// instead of living in SGPRs from the kernel's entry on.
+using kseg = const __attribute__((address_space(4))) char;
+__device__ __forceinline__ kseg* kargs() {
+  kseg* k = (kseg*)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(k));
+  return k;
+}
+
+// Scalar member at byte offset `off` of the segment.
+template <class T>
+__device__ __forceinline__ T kval(size_t off) {
+  return *(const __attribute__((address_space(4))) T*)(kargs() + off);
+}
+
+// Pointer member at byte offset `off`, advanced `stride` bytes per sample to
+// sample n; a null argument stays null (the bodies test the optional ones).
+template <class T>
+__device__ __forceinline__ T* kptr(size_t off, size_t stride = 0, int n = 0) {
+  const unsigned long long v = kval<unsigned long long>(off);
   // through a global-address-space pointer, so the accesses stay global_* (a
   // generic pointer would make them flat_*, which also count in lgkmcnt and
   // so hold every later LDS wait until the global access completes)
-  auto* g = (__attribute__((address_space(1))) T*)(((unsigned long long)hi << 32) | lo);
+  auto* g = (__attribute__((address_space(1))) T*)(v ? v + stride * (unsigned long long)n : 0ull);
   return (T*)g;
 }
-
-// Thread 0 writes the table for sample n (visible after P0's barrier).
-template <class L>
-__device__ __forceinline__ void fill_ptab(uint8_t* lds, const FwdArgs& a, const BwdArgs& b, const PairCtl& pc, int n) {
-  if (threadIdx.x != 0) return;
-  unsigned long long* t = reinterpret_cast<unsigned long long*>(lds + L::PTab);
-  auto at = [](const void* p, size_t bytes) {
-    return p ? (unsigned long long)(reinterpret_cast<const char*>(p) + bytes) : 0ull;
-  };
-  const size_t N = (size_t)n;
-  t[kTWh] = at(a.w.Wh, 0);
-  t[kTWd] = at(a.w.Wd, 0);
-  t[kTW3] = at(a.w.W3, 0);
-  t[kTW2] = at(a.w.W2, 0);
-  t[kTSt] = at(a.st, 0);
-  t[kTHp] = at(a.hp, 0);
-  t[kTA2] = at(a.a2, N * kFlat * 2);
-  t[kTMulv] = at(a.mulv, N * 64 * 4);
-  t[kTEps] = at(a.eps, N * 32 * 4);
-  t[kTZ16] = at(a.z16, N * 32 * 2);
-  t[kTD0] = at(a.d0, N * kFlat * 2);
-  t[kTD1] = at(a.d1, N * 6272 * 2);
-  t[kTDlog] = at(a.dlog, N * 784 * 4);
-  t[kTRecon] = at(a.recon, N * 784 * 4);
-  t[kTBce] = at(a.bce_part, N * 4);
-  t[kTKld] = at(a.kld_part, N * 4);
-  t[kTDb4] = at(a.db4_part, N * 4);
-  t[kTStamp] = at(a.stamps, (size_t)blockIdx.x * 16 * 8);
-  t[kTGd1] = at(b.gd1, N * 6272 * 2);
-  t[kTDb3] = at(b.db3_part, N * 32 * 4);
-  t[kTGd0] = at(b.gd0, N * kFlat * 2);
-  t[kTDbd] = at(b.dbd_part, N * kFlat * 4);
-  t[kTDmulv] = at(b.dmulv, N * 64 * 4);
-  t[kTDmulv16] = at(b.dmulv16, N * 64 * 2);
-  t[kTGa2] = at(b.ga2, N * kFlat * 2);
-  t[kTDb2] = at(b.db2_part, N * 64 * 4);
-  t[kTGa1] = at(b.ga1, N * 6272 * 2);
-  t[kTDb1] = at(b.db1_part, N * 32 * 4);
-  t[kTXg] = at(pc.xg, N * 2 * kXW * 8);
-  t[kTErr] = at(pc.err, 0);
-  t[kTInts] = (unsigned long long)(pc.M & 0xffff) | ((unsigned long long)(a.train ? 1 : 0) << 16) |
-              ((unsigned long long)a.stream << 32);
-}
+#define F28_KP(T, member, stride) kptr<T>(offsetof(StepKargs, member), (stride), n)
 
 __device__ __forceinline__ uint32_t fbits(float f) { return __builtin_bit_cast(uint32_t, f); }
 __device__ __forceinline__ float bitsf(uint32_t u) { return __builtin_bit_cast(float, u); }
@@ -335,25 +314,23 @@ __device__ __forceinline__ void pair_rest(uint8_t* lds, int n, int r) {
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  auto TB = [&](int i) { return tab<L, __bf16>(lds, i); };
-  auto TF = [&](int i) { return tab<L, float>(lds, i); };
-  const unsigned long long ints = reinterpret_cast<const unsigned long long*>(lds + L::PTab)[kTInts];
-  const int M = __builtin_amdgcn_readfirstlane((int)(ints & 0xffff));
-  const bool train = ((ints >> 16) & 1) != 0;
-  const uint32_t stream = __builtin_amdgcn_readfirstlane((uint32_t)(ints >> 32));
+  const bool train = kval<int>(offsetof(StepKargs, fa.train)) != 0;
+  auto stamps = [&] { return kptr<unsigned long long>(offsetof(StepKargs, fa.stamps), 16 * 8, (int)blockIdx.x); };
+  auto state = [&] { return F28_KP(const TrainState, fa.st, 0); };
   auto pstamp = [&](int k) {
     if (tid == 0) {
-      unsigned long long* st = tab<L, unsigned long long>(lds, kTStamp);
+      unsigned long long* st = stamps();
       if (st) st[k] = __builtin_amdgcn_s_memrealtime();
     }
   };
   const int p0 = r ? 24 : 0, p1 = r ? 49 : 24;  // own pixels of the 7x7 maps
   const int q0 = r ? 0 : 24, q1 = r ? 24 : 49;  // the partner's
   const int k0 = 64 * p0, klen = 64 * (p1 - p0);
-  const uint32_t tg = (uint32_t)tab<L, const TrainState>(lds, kTSt)->step * 8u;  // tags tg+1 .. tg+6 (never 0)
-  unsigned long long* xo = tab<L, unsigned long long>(lds, kTXg) + r * kXW;        // own slab (written)
-  unsigned long long* xi = tab<L, unsigned long long>(lds, kTXg) + (r ^ 1) * kXW;  // partner's (read, cleared)
-  unsigned* err = tab<L, unsigned>(lds, kTErr);
+  const uint32_t tg = (uint32_t)state()->step * 8u;  // tags tg+1 .. tg+6 (never 0)
+  unsigned long long* const xg = F28_KP(unsigned long long, pc.xg, 2 * kXW * 8);
+  unsigned long long* xo = xg + r * kXW;        // own slab (written)
+  unsigned long long* xi = xg + (r ^ 1) * kXW;  // partner's (read, cleared)
+  unsigned* err = F28_KP(unsigned, pc.err, 0);
   const float* Bias = reinterpret_cast<const float*>(lds + L::Bias);
   const uint8_t* Zero = lds + L::Bias + 4 * kZero;
   unsigned xcc;
@@ -362,19 +339,19 @@ __device__ __forceinline__ void pair_rest(uint8_t* lds, int n, int r) {
 
   pstamp(2);
   // P3's first two own-K weight rows per wave, in flight under P2
-  auto ld_rows = [&](int c2, bf16x8 (&v)[8]) {
+  auto ld_rows = [&](const __bf16* wh, int c2, bf16x8 (&v)[8]) {
 #pragma unroll
     for (int h = 0; h < 2; ++h)
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const int o = w + 16 * c2 + 8 * h, k = 512 * i + 8 * lane;
-        v[4 * h + i] = k < klen ? *reinterpret_cast<const bf16x8*>(TB(kTWh) + (size_t)o * kFlat + k0 + k) : zero8();
+        v[4 * h + i] = k < klen ? *reinterpret_cast<const bf16x8*>(wh + (size_t)o * kFlat + k0 + k) : zero8();
       }
   };
   bf16x8 wh0[8];
-  ld_rows(0, wh0);
+  ld_rows(F28_KP(const __bf16, fa.w.Wh, 0), 0, wh0);
   // ---- P2: enc2 on own pixels, ReLU
-  __bf16* const a2p = TB(kTA2);  // table reads hoisted above the epilogue's LDS stores (which may alias them)
+  __bf16* const a2p = F28_KP(__bf16, fa.a2, kFlat * 2);
   conv14to7_rows(A1s, Zero, p0, p1, [&](int j, int t) { return conv_bfrag(IMG, j, t, lane); },
                  [&](int, int col) { return Bias[kB2 + col]; }, [&](int p, int col, float v, float bias) {
     const __bf16 o = (__bf16)fmaxf(v + bias, 0.f);
@@ -398,9 +375,10 @@ __device__ __forceinline__ void pair_rest(uint8_t* lds, int n, int r) {
     bf16x8 wr[4][8];
 #pragma unroll
     for (int i = 0; i < 8; ++i) wr[0][i] = wh0[i];
-    ld_rows(1, wr[1]);
-    ld_rows(2, wr[2]);
-    ld_rows(3, wr[3]);
+    const __bf16* const wh = F28_KP(const __bf16, fa.w.Wh, 0);
+    ld_rows(wh, 1, wr[1]);
+    ld_rows(wh, 2, wr[2]);
+    ld_rows(wh, 3, wr[3]);
     float d[8];
 #pragma unroll
     for (int c2 = 0; c2 < 4; ++c2)
@@ -435,10 +413,10 @@ __device__ __forceinline__ void pair_rest(uint8_t* lds, int n, int r) {
     }
   }
   TapImageRegs w3r;
-  w3r.load(TB(kTW3));  // dec1 tap images: in flight during P4-P5
+  w3r.load(F28_KP(const __bf16, fa.w.W3, 0));  // dec1 tap images: in flight during P4-P5
   // P5's first dec_fc weight loads (own n-tiles t = 4 p0 + w + 8 i), in flight across P4
   const int t0 = 4 * p0, t1 = 4 * p1;
-  const __bf16* wp5 = TB(kTWd) + (size_t)(lane & 15) * 32 + 8 * (lane >> 4);
+  const __bf16* wp5 = F28_KP(const __bf16, fa.w.Wd, 0) + (size_t)(lane & 15) * 32 + 8 * (lane >> 4);
   auto wd5_ld = [&](int i) {
     const int t = t0 + w + 8 * i;
     return *reinterpret_cast<const bf16x8*>(wp5 + (size_t)(t < t1 ? t : t0) * 512);
@@ -456,10 +434,11 @@ __device__ __forceinline__ void pair_rest(uint8_t* lds, int n, int r) {
       const int c = tid;
       // eps first: it needs nothing from the partner, so it overlaps the X1 wait
       // (so does the load of the free-bits floor, issued with the step's)
-      const TrainState* stt = tab<L, const TrainState>(lds, kTSt);
+      const TrainState* stt = state();
       const unsigned long long stp = (unsigned long long)stt->step;
       const float fb = stt->fb_t;
-      const HParams* hp = tab<L, const HParams>(lds, kTHp);
+      const HParams* hp = F28_KP(const HParams, fa.hp, 0);
+      const uint32_t stream = kval<uint32_t>(offsetof(StepKargs, fa.stream));
       const u32x4 bits = philox4x32_10(u32x4{(uint32_t)(n * 32 + c), stream, (uint32_t)(stp & 0xffffffffu),
                                              (uint32_t)(stp >> 32)},
                                        hp->seed_lo, hp->seed_hi);
@@ -479,10 +458,11 @@ __device__ __forceinline__ void pair_rest(uint8_t* lds, int n, int r) {
       Zs[c] = (__bf16)zz;
       Eps[c] = ep;
       if (train && r == 0) {
-        TF(kTMulv)[c] = mu;
-        TF(kTMulv)[32 + c] = lv;
-        TF(kTEps)[c] = ep;
-        TB(kTZ16)[c] = (__bf16)zz;
+        float* const mulvp = F28_KP(float, fa.mulv, 64 * 4);
+        mulvp[c] = mu;
+        mulvp[32 + c] = lv;
+        F28_KP(float, fa.eps, 32 * 4)[c] = ep;
+        F28_KP(__bf16, fa.z16, 32 * 2)[c] = (__bf16)zz;
       }
     }
     if (tid == 32) {
@@ -497,14 +477,14 @@ __device__ __forceinline__ void pair_rest(uint8_t* lds, int n, int r) {
   lds_barrier();
   const bool near = __builtin_amdgcn_readfirstlane(reinterpret_cast<const int*>(Scr)[30]) != 0;
   if (tid == 0) {  // slot 15: mode | near << 4
-    unsigned long long* st = tab<L, unsigned long long>(lds, kTStamp);
+    unsigned long long* st = stamps();
     if (st) st[15] |= (unsigned long long)near << 4;
   }
 
   pstamp(5);
   // ---- P5: dec_fc on own pixels (n-tiles [t0, t1)), ReLU; X2 publishes them
   {
-    __bf16* const d0p = TB(kTD0);
+    __bf16* const d0p = F28_KP(__bf16, fa.d0, kFlat * 2);
     const bf16x8 av = (lane & 15) == 0 ? *reinterpret_cast<const bf16x8*>(Zs + 8 * (lane >> 4)) : zero8();
     stream2_pre<13, 1>(wd5, wd5_ld, [&](int i, const bf16x8& bw) {
       const int t = t0 + w + 8 * i;
@@ -539,7 +519,7 @@ __device__ __forceinline__ void pair_rest(uint8_t* lds, int n, int r) {
 
   pstamp(6);
   // ---- P6: dec1 (convT 64 -> 32) on own channels [16 r, 16 r + 16), ReLU
-  __bf16* const d1p = TB(kTD1);
+  __bf16* const d1p = F28_KP(__bf16, fa.d1, 6272 * 2);
   tconv7to14_half(D0u, Zero, IMG, r, [&](int, int co) { return Bias[kB3 + co]; }, [&](int pix, int co, float v, float bias) {
     const __bf16 o = (__bf16)fmaxf(v + bias, 0.f);
     D1s[pix * 32 + co] = o;
@@ -552,8 +532,8 @@ __device__ __forceinline__ void pair_rest(uint8_t* lds, int n, int r) {
   // ---- P7: dec2 partial logits over own channels, X3, then BCE + dlogits (both)
   float loss = 0.f, gsum = 0.f;
   {
-    float* const dlp = TF(kTDlog);
-    float* const rcp = TF(kTRecon);
+    float* const dlp = F28_KP(float, fa.dlog, 784 * 4);
+    float* const rcp = F28_KP(float, fa.recon, 784 * 4);
     float tp[2] = {0.f, 0.f};
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
@@ -621,9 +601,9 @@ __device__ __forceinline__ void pair_rest(uint8_t* lds, int n, int r) {
       sl += Scr[8 + i];
       sg += Scr[16 + i];
     }
-    TF(kTBce)[0] = sl;
-    TF(kTKld)[0] = Scr[0];
-    if (float* d4 = TF(kTDb4)) d4[0] = sg;
+    F28_KP(float, fa.bce_part, 4)[0] = sl;
+    F28_KP(float, fa.kld_part, 4)[0] = Scr[0];
+    if (float* d4 = F28_KP(float, fa.db4_part, 4)) d4[0] = sg;
   }
   // eval (forward only): both halves end here; X1-X3 are consumed (cleared),
   // X4-X6 never written, so the granules are zero for the next launch
@@ -635,7 +615,7 @@ __device__ __forceinline__ void pair_rest(uint8_t* lds, int n, int r) {
   // [pixel] = W4[channel][tap] x im2col(dlogits)[tap][pixel], 13 pixel tiles x
   // 4 tap steps, wave w takes pixel tiles w and w + 8; a lane ends with four
   // consecutive own channels of one pixel.
-  __bf16* const gd1p = TB(kTGd1);
+  __bf16* const gd1p = F28_KP(__bf16, ba.gd1, 6272 * 2);
   {
     const int col = lane & 15, kq = lane >> 4;
     float wa[4];
@@ -685,9 +665,10 @@ __device__ __forceinline__ void pair_rest(uint8_t* lds, int n, int r) {
   }
   // Q3's first dec_fc weight loads (own rows), in flight during X4 and Q2
   const int jr = lane >> 2;
+  const __bf16* const wdq = F28_KP(const __bf16, fa.w.Wd, 0);
   auto wd_ld = [&](int it) {
     const int jj = k0 + it * 128 + w * 16 + jr;
-    return *reinterpret_cast<const bf16x8*>(TB(kTWd) + (size_t)(jj < k0 + klen ? jj : k0) * 32 + 8 * (lane & 3));
+    return *reinterpret_cast<const bf16x8*>(wdq + (size_t)(jj < k0 + klen ? jj : k0) * 32 + 8 * (lane & 3));
   };
   bf16x8 wd0[13];
 #pragma unroll
@@ -700,7 +681,7 @@ __device__ __forceinline__ void pair_rest(uint8_t* lds, int n, int r) {
     s += __shfl_xor(s, 1, 64);
     s += __shfl_xor(s, 2, 64);
     s += __shfl_xor(s, 4, 64);
-    if (part == 0) TF(kTDb3)[16 * r + c] = s;
+    if (part == 0) F28_KP(float, ba.db3_part, 32 * 4)[16 * r + c] = s;
   }
   {  // X4: the partner's gd1 channels into the img14 image
     int gi[4];
@@ -721,8 +702,8 @@ __device__ __forceinline__ void pair_rest(uint8_t* lds, int n, int r) {
 
   pstamp(9);
   // ---- Q2: dec1 backward-data (conv 32 -> 64, B from dec1's tap images) on own pixels x dec_fc mask
-  __bf16* const gd0p = TB(kTGd0);
-  float* const dbdp = TF(kTDbd);
+  __bf16* const gd0p = F28_KP(__bf16, ba.gd0, kFlat * 2);
+  float* const dbdp = F28_KP(float, ba.dbd_part, kFlat * 4);
   conv14to7_rows(GD1s, Zero, p0, p1,
                  [&](int j, int t) {
                    return *reinterpret_cast<const bf16x8*>(IMG + t * 4096 + timg<32>(16 * j + (lane & 15), lane >> 4));
@@ -770,10 +751,15 @@ __device__ __forceinline__ void pair_rest(uint8_t* lds, int n, int r) {
   // Q5's first 16 head-weight loads: row group grp = tid >> 8 (rows 32 grp ..), own 8-chunk ck
   const int nck = klen >> 3, grp = tid >> 8, ck = tid & 255;
   const int kk = k0 + 8 * (ck < nck ? ck : 0);
-  auto wh_ld = [&](int i) { return *reinterpret_cast<const bf16x8*>(TB(kTWh) + (size_t)(32 * grp + i) * kFlat + kk); };
+  auto wh_ld = [&](const __bf16* wh, int i) {
+    return *reinterpret_cast<const bf16x8*>(wh + (size_t)(32 * grp + i) * kFlat + kk);
+  };
   bf16x8 wh5[16];
+  {
+    const __bf16* const wh = F28_KP(const __bf16, fa.w.Wh, 0);
 #pragma unroll
-  for (int i = 0; i < 16; ++i) wh5[i] = wh_ld(i);
+    for (int i = 0; i < 16; ++i) wh5[i] = wh_ld(wh, i);
+  }
   lds_barrier();
 
   pstamp(11);
@@ -789,7 +775,8 @@ __device__ __forceinline__ void pair_rest(uint8_t* lds, int n, int r) {
     xget<1>(xi, gi, tg + 5, pv, err, near);
     const float dz = r ? bitsf(pv[0]) + mine : mine + bitsf(pv[0]);
     // the KL weight of the step being computed (t = step + 1: the step is advanced by a later launch)
-    const float beta = tab<L, const TrainState>(lds, kTSt)->kl_next, fb = tab<L, const TrainState>(lds, kTSt)->fb_t;
+    const TrainState* const stt = state();
+    const float beta = stt->kl_next, fb = stt->fb_t;
     const float mu = Hs[c], lv = Hs[32 + c], ep = Eps[c];
     const float sd = expf(0.5f * lv);
     const float ks = kl_sum_fma(mu, lv, sd);  // as X1 + P4 formed it
@@ -799,10 +786,12 @@ __device__ __forceinline__ void pair_rest(uint8_t* lds, int n, int r) {
     DMs[c] = dm;
     DMs[32 + c] = dl;
     if (r == 0) {
-      TF(kTDmulv)[c] = dm;
-      TF(kTDmulv)[32 + c] = dl;
-      TB(kTDmulv16)[c] = (__bf16)dm;
-      TB(kTDmulv16)[32 + c] = (__bf16)dl;
+      float* const dmp = F28_KP(float, ba.dmulv, 64 * 4);
+      __bf16* const dm16p = F28_KP(__bf16, ba.dmulv16, 64 * 2);
+      dmp[c] = dm;
+      dmp[32 + c] = dl;
+      dm16p[c] = (__bf16)dm;
+      dm16p[32 + c] = (__bf16)dl;
     }
   }
   lds_barrier();
@@ -814,9 +803,10 @@ __device__ __forceinline__ void pair_rest(uint8_t* lds, int n, int r) {
 #pragma unroll
     for (int e = 0; e < 8; ++e) acc[e] = 0.f;
     bf16x8 wh6[16];  // rows 16..31 of the group: with wh5, all 32 in flight at once
+    const __bf16* const wh = F28_KP(const __bf16, fa.w.Wh, 0);
 #pragma unroll
-    for (int i = 0; i < 16; ++i) wh6[i] = wh_ld(16 + i);
-    w2r.load(TB(kTW2));  // enc2 tap images: in flight during Q5
+    for (int i = 0; i < 16; ++i) wh6[i] = wh_ld(wh, 16 + i);
+    w2r.load(F28_KP(const __bf16, fa.w.W2, 0));  // enc2 tap images: in flight during Q5
 #pragma unroll
     for (int i = 0; i < 32; ++i) {
       const bf16x8& wv = i < 16 ? wh5[i] : wh6[i - 16];
@@ -829,7 +819,7 @@ __device__ __forceinline__ void pair_rest(uint8_t* lds, int n, int r) {
       for (int e = 0; e < 8; ++e) CSB[ck * 8 + e] = acc[e];
     }
     lds_barrier();
-    __bf16* const ga2p = TB(kTGa2);
+    __bf16* const ga2p = F28_KP(__bf16, ba.ga2, kFlat * 2);
     if (grp == 0 && ck < nck) {
       const bf16x8 mk = *reinterpret_cast<const bf16x8*>(A2s + kk);
       bf16x8 o;
@@ -871,13 +861,14 @@ __device__ __forceinline__ void pair_rest(uint8_t* lds, int n, int r) {
   if (tid < 64) {  // enc2 bias partials over own pixels, in order: row r of [2][M][64]
     float s = 0.f;
     for (int p = p0; p < p1; ++p) s += GA2F[p * 64 + tid];
-    TF(kTDb2)[(size_t)r * M * 64 + tid] = s;
+    const int M = kval<int>(offsetof(StepKargs, pc.M));
+    F28_KP(float, ba.db2_part, 64 * 4)[(size_t)r * M * 64 + tid] = s;
   }
 
   pstamp(13);
   // ---- Q6: enc2 backward-data (convT 64 -> 32 with the conv weights) on own channels x enc1 mask
   {
-    __bf16* const ga1p = TB(kTGa1);
+    __bf16* const ga1p = F28_KP(__bf16, ba.ga1, 6272 * 2);
     const float cs = tconv7to14_half(GA2u, Zero, IMG, r,
                                      [&](int pix, int co) {
                                        return (float)*reinterpret_cast<const __bf16*>(A1s + img14(pix, co >> 3) +
@@ -895,10 +886,12 @@ __device__ __forceinline__ void pair_rest(uint8_t* lds, int n, int r) {
     float s = 0.f;
 #pragma unroll
     for (int i = 0; i < 8; ++i) s += CS[i * 16 + tid];
-    TF(kTDb1)[16 * r + tid] = s;
+    F28_KP(float, ba.db1_part, 32 * 4)[16 * r + tid] = s;
   }
   pstamp(14);
 }
+
+#undef F28_KP
 
 }  // namespace f28
 }  // namespace mdt

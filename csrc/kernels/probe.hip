@@ -33,6 +33,27 @@ __global__ void probe_latency(const int* idx, int hops, unsigned long long* out)
 
 __global__ void probe_empty() {}
 
+// probe_empty with the fused 28x28 step's launch shape (256 workgroups of 512
+// threads, its static LDS bytes): each workgroup stores its entry time
+// (s_memrealtime, 100 MHz) and where it ran ((XCC id << 16) | HW_ID bits, as
+// probe_cu_ids). It does no work, so it only tells which resource -- LDS
+// bytes or threads per workgroup -- sets the ramp of the dispatch.
+// out: [blocks][2].
+template <int LDS>
+__global__ void __launch_bounds__(512) probe_ramp(unsigned long long* out) {
+  const unsigned long long t = __builtin_amdgcn_s_memrealtime();
+  if constexpr (LDS > 0) {
+    __shared__ unsigned char lds[LDS];
+    reinterpret_cast<volatile unsigned char*>(lds)[threadIdx.x] = 0;  // keeps the allocation
+  }
+  if (threadIdx.x != 0) return;
+  unsigned hw, xcc;
+  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
+  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID, 0, 4)" : "=s"(xcc));
+  out[2 * blockIdx.x] = t;
+  out[2 * blockIdx.x + 1] = (xcc << 16) | (hw & 0xff00u);
+}
+
 // Fill every CU's LDS (the whole 160 KB, one 1024-thread workgroup per CU at
 // a time) with a pattern: an uninitialised-LDS read in a later kernel then
 // shows up as a changed result (tests: the fused step under a poisoned LDS).
@@ -75,6 +96,21 @@ extern "C" int mdt_probe_latency(const int* idx, int hops, unsigned long long* o
 
 extern "C" int mdt_probe_empty(int blocks, int threads, hipStream_t s) {
   hipLaunchKernelGGL(mdt::probe_empty, dim3(blocks), dim3(threads), 0, s);
+  return (int)hipGetLastError();
+}
+
+// lds: 0, 65536 or the step kernel's bytes (any other value: error 1)
+extern "C" int mdt_probe_ramp(unsigned long long* out, int blocks, int threads, int lds, hipStream_t s) {
+  constexpr int kStepLds = 161216;  // f28::StepLayout::LDS
+  if (threads <= 0 || threads > 512 || blocks <= 0) return 1;
+  if (lds == 0)
+    hipLaunchKernelGGL(mdt::probe_ramp<0>, dim3(blocks), dim3(threads), 0, s, out);
+  else if (lds == 65536)
+    hipLaunchKernelGGL(mdt::probe_ramp<65536>, dim3(blocks), dim3(threads), 0, s, out);
+  else if (lds == kStepLds)
+    hipLaunchKernelGGL(mdt::probe_ramp<kStepLds>, dim3(blocks), dim3(threads), 0, s, out);
+  else
+    return 1;
   return (int)hipGetLastError();
 }
 

@@ -5,6 +5,7 @@
 extern "C" int mdt_probe_clock(unsigned long long* out, int iters, hipStream_t s);
 extern "C" int mdt_probe_latency(const int* idx, int hops, unsigned long long* out, hipStream_t s);
 extern "C" int mdt_probe_empty(int blocks, int threads, hipStream_t s);
+extern "C" int mdt_probe_ramp(unsigned long long* out, int blocks, int threads, int lds, hipStream_t s);
 extern "C" int mdt_probe_lds_poison(unsigned pattern, int blocks, hipStream_t s);
 extern "C" int mdt_probe_cu_ids(unsigned* out, int blocks, hipStream_t s);
 
@@ -27,6 +28,18 @@ void probe_latency(at::Tensor idx, int64_t hops, at::Tensor out) {
 void probe_empty(int64_t blocks, int64_t threads) {
   TORCH_CHECK(mdt_probe_empty((int)blocks, (int)threads, c10::hip::getCurrentHIPStream().stream()) == 0,
               "probe_empty");
+}
+
+// out: int64 [blocks][2] (entry tick, XCC / HW_ID bits) of an empty launch of `threads` threads and `lds` static
+// LDS bytes per workgroup (0, 65536 or the fused 28x28 step's)
+void probe_ramp(at::Tensor out, int64_t threads, int64_t lds) {
+  TORCH_CHECK(out.is_cuda() && out.scalar_type() == torch::kInt64 && out.is_contiguous() && out.dim() == 2 &&
+                  out.size(1) == 2 && out.size(0) >= 1 && out.size(0) <= 65536,
+              "out: contiguous cuda int64[blocks][2]");
+  TORCH_CHECK(threads >= 1 && threads <= 512, "probe_ramp: threads");
+  TORCH_CHECK(mdt_probe_ramp(reinterpret_cast<unsigned long long*>(out.data_ptr<int64_t>()), (int)out.size(0),
+                             (int)threads, (int)lds, c10::hip::getCurrentHIPStream().stream()) == 0,
+              "probe_ramp: lds must be 0, 65536 or the step kernel's bytes");
 }
 
 void probe_lds_poison(int64_t pattern, int64_t blocks) {
