@@ -346,10 +346,16 @@ std::vector<double> MlpVaeEngine::iw_read() { return iw_state_read(iw_state); }
 
 at::Tensor MlpVaeEngine::iw_act(const std::string& name, int64_t S, int64_t M) {
   TORCH_CHECK(iw_ws_.defined() && S >= 1 && M >= 1 && S * M <= iw_cap_, "iw_act: no pass has run at this size");
-  int64_t off = align64(iw_cap_ * H_);
-  if (name == "z") off += align64(iw_cap_ * Z_);
-  else TORCH_CHECK(name == "eps", "iw_act: unknown buffer ", name);
-  return iw_ws_.narrow(0, off, S * M * Z_).view({S, M, Z_});
+  if (name == "h3") return iw_ws_.narrow(0, 0, S * M * H_).view({S * M, H_});
+  int64_t off = align64(iw_cap_ * H_);  // the workspace layout of iw_batch: h3 | eps | z | prior | bce
+  if (name == "eps" || name == "z") {
+    if (name == "z") off += align64(iw_cap_ * Z_);
+    return iw_ws_.narrow(0, off, S * M * Z_).view({S, M, Z_});
+  }
+  off += 2 * align64(iw_cap_ * Z_);
+  if (name == "bce") off += align64(iw_cap_);
+  else TORCH_CHECK(name == "prior", "iw_act: unknown buffer ", name);
+  return iw_ws_.narrow(0, off, S * M).view({S, M});
 }
 
 // ------------------------------------------------------ latent report pass ----

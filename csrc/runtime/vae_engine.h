@@ -74,7 +74,7 @@ class MlpVaeEngine {
   void iw_batch(const at::Tensor& X, const at::Tensor& idx, int64_t M, int64_t K, int64_t chunk,
                 at::Tensor row_nll, at::Tensor row_neg_elbo);
   std::vector<double> iw_read();    // nll, neg_elbo, step (batches begun), cursor
-  at::Tensor iw_act(const std::string& name, int64_t S, int64_t M);  // "eps" | "z" of the last chunk: [S, M, Z]
+  at::Tensor iw_act(const std::string& name, int64_t S, int64_t M);  // of the last chunk: "eps" | "z" [S, M, Z], "prior" | "bce" [S, M], "h3" [S*M, H]
   // virtual rows the chunk workspace holds; it grows (reallocates) when a pass
   // asks for more, which invalidates graphs captured over the old one
   int64_t iw_capacity() const { return iw_cap_; }

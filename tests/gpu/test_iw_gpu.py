@@ -9,7 +9,9 @@ Bounds, none of them taken from the code under test:
     test_philox_host_matches_device;
   * conv rows against a float64 recomputation that shares the pass's bf16
     rounding points (same decoder kernels on the same latents): rel 1e-4
-    (test_conv28_fused.py);
+    (test_conv28_fused.py), and per row the derived reduce bound of
+    tests/iw_checker.py on the recomputed log-weights, with the BCE and prior
+    bounds carried (about 1e-4 nat absolute at |logw| ~ 540);
   * conv degenerate identity against ``evaluate()``: rel 1e-3, the layer
     path's loss bound (test_conv_vae_kernels.py).
 The log-weights sit near -540 (MLP, fresh weights) with a spread of several
@@ -172,46 +174,49 @@ def test_mlp_graphs_survive_a_larger_chunk(native_ext):
 
 
 def _conv_recompute(tr, X, idx, K, chunk):
-    """float64 row_nll / row_neg_elbo of the LAST batch of the pass over
-    X[idx], from what the pass exposes: mulv, and eps / z of the last chunk.
-    The noise of sample k does not depend on K, so passes with K' = the chunk
-    ends expose every sample in turn. Each z goes through ``tr.decode()`` (the
-    same decoder kernels on the same bf16 latents); BCE, prior term and
-    logsumexp are redone in float64."""
-    from multidisttorch_amd.models.iw import iw_prior_term, iw_reduce
-    from multidisttorch_amd.models.mlp_vae import _bce_terms
+    """float64 log-weights ``lw[K, M]`` of the LAST batch of the pass over
+    X[idx] and their bound, from what the pass exposes: mulv, and eps / z of
+    the last chunk. The noise of sample k does not depend on K, so passes with
+    K' = the chunk ends expose every chunk in turn. Each chunk's z goes through
+    ``tr.decode()`` packed as the pass packs it (the same decoder kernels on the
+    same bf16 latents in the same launch shapes: the same logits); BCE and prior
+    term are redone in float64 with the bounds of tests/iw_checker.py. Also
+    ``rolled``: lw with the image rows rolled by one (None when M = 1)."""
+    from multidisttorch_amd.models.iw import default_chunk
+    from tests import iw_checker as ck
 
     B, n = tr.B, idx.numel()
     nb = -(-n // B)
     M = n - (nb - 1) * B
-    Sc = max(1, min(chunk, B // M))
-    x = X[idx[(nb - 1) * B:].long()].cpu().double()
+    Sc = max(1, min(default_chunk(K, B, chunk), B // M))
+    x = X[idx[(nb - 1) * B:].long()].cpu()
     host = _host_eps(K, B, tr.Z, nb - 1)
-    logw = []
+    lw, b_lw, rolled = [], [], []
     for k0 in range(0, K, Sc):
         k1 = min(k0 + Sc, K)
+        s = k1 - k0
         tr.evaluate_iw(X, idx, k1, chunk_samples=chunk)
         torch.cuda.synchronize()
-        buf = tr.iw_buffers(k1 - k0, M)
+        buf = tr.iw_buffers(s, M)
         np.testing.assert_allclose(buf["eps"].cpu().numpy(), host[k0:k1, :M], rtol=1e-5, atol=1e-5)
-        mu, lv = buf["mulv"][:, : tr.Z].cpu().double(), buf["mulv"][:, tr.Z:].cpu().double()
-        for s in range(k1 - k0):
-            z, eps = buf["z"][s], buf["eps"][s].cpu().double()
-            np.testing.assert_allclose(z.cpu().double().numpy(), (mu + eps * torch.exp(0.5 * lv)).numpy(), rtol=1e-5,
-                                       atol=1e-5)
-            tr.decode(z)
-            t = tr.logits[: M * tr.D].view(M, tr.D).cpu().double()
-            logw.append(-_bce_terms(t, x).sum(-1) + iw_prior_term(z.cpu().double(), eps, lv))
-    return iw_reduce(torch.stack(logw))
+        z, bz, prior, bp = ck.reparam_ref(buf["mulv"].cpu(), buf["eps"].cpu())
+        assert ck.ratio(buf["z"].cpu(), z, bz) <= 1
+        tr.decode(buf["z"].reshape(s * M, tr.Z))
+        t = tr.logits[: s * M * tr.D].view(s * M, tr.D).cpu()
+        bce, bb = ck.row_bce_ref(t, x, ck.conv_depth(tr.D))
+        a, b = ck.lw_ref(prior, bce.view(s, M), bp, bb.view(s, M))
+        lw.append(a)
+        b_lw.append(b)
+        if M > 1:
+            rolled.append(prior - ck.row_bce_ref(t, x.roll(1, 0), ck.conv_depth(tr.D))[0].view(s, M))
+    return torch.cat(lw), torch.cat(b_lw), torch.cat(rolled) if rolled else None
 
 
-@pytest.mark.parametrize("n,K,chunk", [(53, 3, 2), (37, 4, 2)])  # tail 21: chunks of 1; tail 5: chunks of 2
-def test_conv28_composition(n, K, chunk, native_ext):
-    B = 32
-    X = _images(256)
-    tr = _conv(B, 28)
-    assert tr.f28, "MDT_CONV_F28 default: training runs the fused step, the pass the layer path"
-    _train(tr, X, 40)
+def _check_composition(tr, X, n, K, chunk, five_percent):
+    from multidisttorch_amd.models.iw import iw_reduce
+    from tests import iw_checker as ck
+
+    B = tr.B
     idx = _arange(n)
     r = tr.evaluate_iw(X, idx, K, chunk_samples=chunk, return_rows=True)
     torch.cuda.synchronize()
@@ -220,14 +225,46 @@ def test_conv28_composition(n, K, chunk, native_ext):
     r0 = tr.evaluate_iw(X, idx[:B], K, chunk_samples=chunk, return_rows=True)
     assert torch.equal(r0["row_nll"].cpu(), r["row_nll"][:B].cpu())
     for lo, sub in ((0, idx[:B]), (n - n % B, idx)):
-        rn, re_ = _conv_recompute(tr, X, sub, K, chunk)
+        lw, b_lw, rolled = _conv_recompute(tr, X, sub, K, chunk)
+        rn, re_ = iw_reduce(lw)
         m = rn.numel()
         print("rows", lo, "max rel err", float(((rows[0][lo:lo + m] - rn).abs() / rn).max()),
               float(((rows[1][lo:lo + m] - re_).abs() / re_).max()), "row spread", float(rn.max() - rn.min()))
         np.testing.assert_allclose(rows[0][lo:lo + m].numpy(), rn.numpy(), rtol=1e-4, atol=0)
         np.testing.assert_allclose(rows[1][lo:lo + m].numpy(), re_.numpy(), rtol=1e-4, atol=0)
-        assert float(rn.max() - rn.min()) > 0.05 * float(rn.mean()), "rows too alike to tell a mispaired sample"
+        # the reduce bound of tests/iw_checker.py on the recomputed log-weights, b_lw from the BCE and prior bounds
+        nll, ne, bn, be = ck.reduce_ref(lw, b_lw)
+        ra, rb = ck.ratio(rows[0][lo:lo + m], nll, bn), ck.ratio(rows[1][lo:lo + m], ne, be)
+        print(f"RATIO conv_pass.row_nll {ra:.4g} conv_pass.row_neg_elbo {rb:.4g} (n={n} K={K} rows {lo}..)")
+        assert ra <= 1 and rb <= 1, (ra, rb)
+        # a mispaired image row would show at every row: the oracle with the rows rolled by one leaves the bound
+        n2, e2, _, _ = ck.reduce_ref(rolled)   # (every batch here has more than one row)
+        assert bool((((n2 - nll).abs() > bn) | ((e2 - ne).abs() > be)).all()), "rows too alike to tell a mispaired sample"
+        if five_percent:
+            assert float(rn.max() - rn.min()) > 0.05 * float(rn.mean()), "rows too alike to tell a mispaired sample"
+    for name, tot in (("nll", rows[0]), ("neg_elbo", rows[1])):
+        rt = ck.totals_ratio(r[name], tot.float())
+        print(f"RATIO conv_pass.total_{name} {rt:.4g}")
+        assert rt <= 1
     assert bool((r["row_nll"] <= r["row_neg_elbo"] + 1e-3).all())
+
+
+# tail 21: chunks of 1; tail 5: chunks of 2; tail 5 with the default chunk: 6 samples per chunk, the last chunk holds 2
+@pytest.mark.parametrize("n,K,chunk", [(53, 3, 2), (37, 4, 2), (37, 50, None)])
+def test_conv28_composition(n, K, chunk, native_ext):
+    X = _images(256)
+    tr = _conv(32, 28)
+    assert tr.f28, "MDT_CONV_F28 default: training runs the fused step, the pass the layer path"
+    _train(tr, X, 40)
+    _check_composition(tr, X, n, K, chunk, five_percent=True)
+
+
+def test_conv128_composition(native_ext):
+    """The same at 128 x 128, B = 16, Z = 64: a tail of 5 in chunks of 2 (n = 21, K = 3, chunk = 2)."""
+    X = _images(64, 128)
+    tr = _conv(16, 128)
+    _train(tr, X, 10)
+    _check_composition(tr, X, 21, 3, 2, five_percent=False)
 
 
 @pytest.mark.parametrize("image,B,n", [(28, 32, 53), (128, 16, 21)])
