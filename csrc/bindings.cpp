@@ -22,6 +22,7 @@ void bind_latent(pybind11::module& m);
 void bind_data(pybind11::module& m);
 void bind_tc(pybind11::module& m);
 void bind_ema(pybind11::module& m);
+void bind_two_sample(pybind11::module& m);
 }  // namespace mdt
 
 PYBIND11_MODULE(_C, m) {
@@ -42,6 +43,7 @@ PYBIND11_MODULE(_C, m) {
   mdt::bind_data(m);
   mdt::bind_tc(m);
   mdt::bind_ema(m);
+  mdt::bind_two_sample(m);
 
   // the trial-state owner of both trainers (runtime/trial_state.h); kLossHist: the length of its loss rings
   m.attr("kLossHist") = (int64_t)mdt::kLossHist;

@@ -12,18 +12,22 @@ __all__ = ["trial_record", "summarize"]
 LATENT_KEYS = ("kl", "active_units", "mi", "tc", "dwkl")
 # per-trial scores of the after-trial passes (``TrialResult.extra``); None where the pass did not run
 SCORES = ("iw_nll", "latent", "test_loss_raw")
+SAMPLE_KEYS = ("mmd2", "nn_acc", "nn_acc_real", "nn_acc_fake")
 
 
 def trial_record(result, opts) -> dict:
     """One rank's record of one trial it took part in."""
-    return dict(group_id=result.group_id, samples=result.samples, wall_s=result.wall_s, failed=result.failed,
-                **{k: result.extra.get(k) for k in SCORES})
+    rec = dict(group_id=result.group_id, samples=result.samples, wall_s=result.wall_s, failed=result.failed,
+               **{k: result.extra.get(k) for k in SCORES})
+    if opts.sample_report > 0:  # only then: the default record stays what it was
+        rec["sample_report"] = result.extra.get("sample_report")
+    return rec
 
 
 def summarize(gathered, specs, opts) -> dict:
     """``gathered``: per rank, the list of its ``trial_record``s (None or empty: an idle rank)."""
     per_trial, wall, failed = {}, 0.0, set()
-    scores = {k: {} for k in SCORES}
+    scores = {k: {} for k in SCORES + ("sample_report",)}
     for lst in gathered:
         for r in lst or []:
             gid = r["group_id"]
@@ -31,7 +35,7 @@ def summarize(gathered, specs, opts) -> dict:
             wall = max(wall, r["wall_s"])
             if r["failed"]:
                 failed.add(gid)
-            for k in SCORES:
+            for k in scores:
                 if r.get(k) is not None:
                     scores[k][gid] = r[k]
     iw_nll, latent = scores["iw_nll"], scores["latent"]
@@ -62,4 +66,10 @@ def summarize(gathered, specs, opts) -> dict:
         for g, v in latent.items():  # trials with a KL floor: the dimensions it holds up
             if "below_floor" in v:
                 summary["latent"][str(g)]["below_floor"] = v["below_floor"]
+    if opts.sample_report > 0:
+        # prior samples against test rows: the lowest kernel MMD is the best trial; 1-NN accuracy 0.5 is ideal
+        samples = scores["sample_report"]
+        summary["sample_rows"] = opts.sample_report
+        summary["sample_report"] = {str(g): {k: round(v[k], 6) for k in SAMPLE_KEYS} for g, v in sorted(samples.items())}
+        summary["best_trial_by_mmd2"] = (min(samples, key=lambda g: (samples[g]["mmd2"], g)) if samples else None)
     return summary

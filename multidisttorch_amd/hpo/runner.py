@@ -80,6 +80,7 @@ class RunOptions:
     au_threshold: float = 0.01             # a dimension is active when Var_x(mu_d) exceeds this
     binarize: str = "none"                 # none | threshold | static | dynamic (data/binarize.py); one value per run
     report_objective: tuple = ()           # objective.reported(specs): knobs whose values the metrics carry
+    sample_report: int = 0                 # N > 0: kernel MMD + 1-NN test of N prior samples against N test rows
 
 
 @dataclass
@@ -467,11 +468,39 @@ def _latent_eval(trainer, test, opts: RunOptions, group, metrics, device, tag: s
     return dict(latent=r)
 
 
+def _check_sample_rows(opts: RunOptions, test):
+    """At run start: ``--sample-report N`` needs N test rows."""
+    if opts.sample_report > len(test):
+        raise ValueError(f"--sample-report {opts.sample_report} exceeds the test set's {len(test)} rows")
+
+
+def _sample_eval(trainer, test, opts: RunOptions, group, metrics, device, tag: str = "") -> dict:
+    """One sample report pass after a trial's last epoch (``--sample-report N``,
+    models/sample_report.py): the kernel MMD and the 1-NN two-sample test between
+    N decoded prior samples and the first N test rows -- what the decoder makes of
+    the prior, which neither the test loss nor the IW bound looks at. Like its
+    siblings it runs after the trial's wall time was taken."""
+    n = int(opts.sample_report)
+    _check_sample_rows(opts, test)
+    t = time.perf_counter()
+    idx = torch.arange(n, dtype=torch.int32, device=test.data.device)
+    with trace.range("sample_eval"), trainer.averaged_weights():
+        r = trainer.evaluate_samples(test.data, idx, n)
+        if device.type == "cuda":
+            torch.cuda.synchronize(device)
+    r["sample_s"] = round(time.perf_counter() - t, 6)
+    print0(tag + "====> Test set samples: MMD2 {:.6f} 1-NN acc {:.4f} (real {:.4f} gen {:.4f})".format(
+        r["mmd2"], r["nn_acc"], r["nn_acc_real"], r["nn_acc_fake"]), process_group=group)
+    metrics.log(event="sample_eval", **r)
+    return dict(sample_report=r)
+
+
 # after a trial's last epoch and its wall time, in this order: (label, enabled(spec, opts), pass -> part of extra)
 _AFTER_TRIAL = (
     ("IW pass", lambda spec, opts: opts.iw_samples > 0, _iw_eval),
     ("latent pass", lambda spec, opts: opts.latent_report, _latent_eval),
     ("raw-weight test pass", lambda spec, opts: spec.ema_decay > 0, _raw_test_eval),
+    ("sample pass", lambda spec, opts: opts.sample_report > 0, _sample_eval),
 )
 
 
@@ -500,6 +529,7 @@ def run_trial(spec: TrialSpec, group, opts: RunOptions, data=None, num_trials: O
     device = bound_device()
 
     train, test = data if data is not None else _load_data(opts, device)
+    _check_sample_rows(opts, test)
     if grank == 0:  # stderr: stdout stays byte-compatible with the reference
         print(f"[mdt] trial {spec.group_id}: train data {train.name} ({'synthetic' if train.synthetic else 'IDX'}, "
               f"{len(train)} x {tuple(train.shape)})", file=sys.stderr, flush=True)
@@ -682,6 +712,7 @@ def run_packed_trials(specs, group, opts: RunOptions, data=None, num_trials: Opt
     total = num_trials if num_trials is not None else world_size * len(specs)
     device = bound_device()
     train, test = data if data is not None else _load_data(opts, device)
+    _check_sample_rows(opts, test)
     D = int(train.data.shape[1])
     shape = (1, opts.image_size, opts.image_size)
     tr = []

@@ -29,8 +29,10 @@ import torch
 from ..ops import native
 from .iw import check_iw_args, default_chunk, iw_eps, iw_reduce
 from .latent import check_latent_args, latent_eps, latent_report
+from .sample_report import (COLS, bandwidths_of, check_sample_args, mean_pair_d2, sample_rows, sample_stats,
+                            sample_z)
 
-__all__ = ["GraphedEval", "GraphedIwEval", "GraphedLatentEval", "capture_replayable"]
+__all__ = ["GraphedEval", "GraphedIwEval", "GraphedLatentEval", "SampleEval", "capture_replayable"]
 
 
 def capture_replayable(snapshot_tensors, launch, repeats: int):
@@ -341,3 +343,50 @@ class GraphedLatentEval:
         ws = self._lat_ws[1]
         return dict(mulv=self._lat_rows[:n].clone(), eps=C.latent_ws_view(ws[0], n, self.Z, None, "eps").clone(),
                     z=C.latent_ws_view(ws[0], n, self.Z, None, "z").clone())
+
+
+class SampleEval:
+    """Mixin: ``evaluate_samples``, the sample report (models/sample_report.py):
+    kernel MMD and the 1-NN two-sample test between decoded prior samples and
+    rows ``X[idx]``. The decoder runs through the trainer's ``decode`` (the
+    Bernoulli mean the sample images show); the per-row table comes from the
+    HIP kernels (csrc/kernels/two_sample.hip) on the hip backend and from the
+    oracle's torch ops otherwise. Eager: three launches per pass.
+
+    Requires ``self.Z``, ``self.seed``, ``self.device``, ``self.backend`` and
+    ``self.decode(z) -> [n, D]``."""
+
+    # elements per torch-backend block: [chunk, na + nb, D] float32 stays within 64 MiB
+    SAMPLE_CHUNK_ELEMS = 1 << 24
+
+    @torch.no_grad()
+    def evaluate_samples(self, X: torch.Tensor, idx: torch.Tensor, n_samples=None, return_rows: bool = False) -> dict:
+        """The sample report of ``n_samples`` decoded prior draws (default: as
+        many as rows) against rows ``X[idx]``: ``dict(rows_real, rows_fake,
+        mean_pair_d2, bandwidths, mmd2, mmd2_per_bandwidth, nn_acc, nn_acc_real,
+        nn_acc_fake, nn_dist_real_to_fake, nn_dist_fake_to_real, rf_asym)``;
+        with ``return_rows`` also ``table`` (float32 ``[rows_real + rows_fake,
+        8]``), ``real`` and ``fake``. Training, eval, iw and latent state are not
+        touched; the result depends on (weights, data, seed, n) only."""
+        idx = idx.to(device=self.device, dtype=torch.int64).contiguous()
+        na = idx.numel()
+        nb = na if n_samples is None else int(n_samples)
+        real = X[idx].to(self.device, torch.float32).reshape(na, -1).contiguous()
+        D = real.shape[1]
+        check_sample_args(na, nb, D)
+        m = mean_pair_d2(real)
+        h = bandwidths_of(m)
+        z = torch.from_numpy(sample_z(nb, self.Z, self.seed)).to(self.device)
+        fake = self.decode(z).to(torch.float32).reshape(nb, -1).contiguous()
+        if self.backend != "hip":
+            table = sample_rows(real, fake, h, chunk=max(1, self.SAMPLE_CHUNK_ELEMS // ((na + nb) * D)))
+        else:
+            C = native.require()
+            # the workspace grows with (na + nb)^2 / 32 (58 MB at 20000 rows): it lives for this pass only
+            ws = torch.empty(C.two_sample_ws_numel(na, nb, D), dtype=torch.float32, device=self.device)
+            table = torch.empty(na + nb, COLS, dtype=torch.float32, device=self.device)
+            C.two_sample_rows(real, fake, list(h), ws, table)
+        out = dict(rows_real=na, rows_fake=nb, mean_pair_d2=m, bandwidths=list(h), **sample_stats(table, na, nb))
+        if return_rows:
+            out.update(table=table, real=real, fake=fake)
+        return out

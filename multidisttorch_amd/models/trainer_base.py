@@ -29,7 +29,7 @@ from ..hpo import objective
 from ..hpo.schedule import Schedule
 from ..ops import native
 from ..ops.philox import reparam_eps
-from .eval_graphs import GraphedEval, GraphedIwEval, GraphedLatentEval, capture_replayable
+from .eval_graphs import GraphedEval, GraphedIwEval, GraphedLatentEval, SampleEval, capture_replayable
 from .mlp_vae import views
 
 __all__ = ["VaeTrainerBase", "LOSS_HIST", "EVAL_STREAM", "check_free_bits", "check_ema_decay", "ema_omd"]
@@ -49,7 +49,7 @@ def ema_omd(decay: float, t: int) -> float:
     return float(np.float32(1.0 - min(float(decay), (1.0 + t) / (10.0 + t))))
 
 
-class VaeTrainerBase(GraphedEval, GraphedIwEval, GraphedLatentEval):
+class VaeTrainerBase(GraphedEval, GraphedIwEval, GraphedLatentEval, SampleEval):
     def __init__(self, batch_size: int, device, backend: Optional[str], seed: int, rng_stream: int, lr: float,
                  kl_beta: float, betas, eps: float, weight_decay: float, decoupled_wd: bool, use_graphs: bool,
                  graph_steps: int, schedule: Optional[Schedule], knobs: Optional[dict] = None):

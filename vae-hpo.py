@@ -23,7 +23,9 @@ does not depend on the trial's beta), ``--latent-report`` (+ ``--au-threshold``;
 after each trial's last epoch: active units and the MI / TC / dimension-wise-KL
 split of the KL term over the test set), ``--binarize {none,threshold,static,dynamic}``
 (train and test on {0, 1} pixels, redrawn on the device: the test loss and the
-IW bound are then negative log-likelihoods of binarized data; one value per run).
+IW bound are then negative log-likelihoods of binarized data; one value per run),
+``--sample-report N`` (after each trial's last epoch: the kernel MMD and the 1-NN
+two-sample test between N decoded prior samples and N test rows).
 """
 
 import argparse
@@ -109,7 +111,17 @@ def parse_args(argv=None):
                         help="binarize the data on the device: threshold = x >= 0.5; static = one Bernoulli(x) draw "
                              "per trial; dynamic = a fresh draw of the training rows every epoch. The test set is "
                              "drawn once. One value for the whole run: trials of a sweep share a likelihood")
-    return parser.parse_args(argv)
+    parser.add_argument("--sample-report", type=int, default=0, metavar="N",
+                        help="after each trial's last epoch: kernel MMD and 1-NN two-sample test between N decoded "
+                             "prior samples and the first N test rows (a score of the samples themselves; 0 = off)")
+    args = parser.parse_args(argv)
+    if args.sample_report != 0:
+        from multidisttorch_amd.models.sample_report import check_sample_args
+
+        check_sample_args(args.sample_report, args.sample_report, 1)
+        if args.test_samples is not None and args.sample_report > args.test_samples:
+            raise ValueError(f"--sample-report {args.sample_report} exceeds --test-samples {args.test_samples}")
+    return args
 
 
 def main(argv=None):
@@ -152,7 +164,7 @@ def main(argv=None):
                       model=args.model, image_size=args.image_size, bucket_mb=parse_bucket_mb(args.bucket_mb),
                       profile=args.profile, iw_samples=max(0, args.iw_samples), latent_report=args.latent_report,
                       au_threshold=args.au_threshold, binarize=args.binarize,
-                      report_objective=objective.reported(specs))
+                      report_objective=objective.reported(specs), sample_report=args.sample_report)
     results = []
     member = False
     for group_id, group in enumerate(processes_groups):
