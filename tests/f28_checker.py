@@ -457,9 +457,12 @@ def stage_of(key: str) -> str:
 STAGES = ("P0", "P1", "P2", "P3", "P4", "P5", "P6", "P7", "Q1", "Q2", "Q4", "Q5", "Q6", "WG")
 
 
+KNOB_STAGES = ("AD", "EM")   # after a shipped step: Adam and the weight average (tests/knob_cases.py)
+
+
 def first_failure(ratios: dict):
     """The first stage (in step order) with a ratio > 1, or None."""
-    for st in STAGES:
+    for st in STAGES + KNOB_STAGES:
         if any(not r <= 1 for k, r in ratios.items() if stage_of(k) == st):
             return st
     return None

@@ -53,6 +53,8 @@ most n (EPS | U) mag (Higham, Accuracy and Stability, section 4.2).
   reparameterisation backward ``reparam_bwd_ref`` from the STORED dz, with the
                               KL weight the state held and weight 0 on the
                               floored set; dmulv16 is the bitwise twin of dmulv.
+                              With the total-correlation penalty (``tc``) the
+                              reference gains tc_t g64 (``knob_cases.tc_rule``).
 
 A bf16 output is checked as the bf16 rounding of an f32 value within the stage
 bound of the oracle (``direct_checker.y16_ratio``) plus HALF_SUB = 2^-134, half
@@ -551,9 +553,23 @@ def check_reparam(b, q, seed, stream, step, fb=0.0):
 
 
 # ------------------------------------------------------------------ backward ----
-def check_backward(spec, b, W, pl, klw, fb=0.0, only=None):
+def dmulv_ref(b, klw, fb=0.0, tc=None):
+    """(ref, bound) of d[mu|lv] from the STORED dz, mulv and eps: ``reparam_bwd_ref`` with the KL weight the
+    state held and weight 0 on the floored set, then the penalty's share by ``knob_cases.tc_rule``."""
+    from tests.knob_cases import tc_rule
+
+    fl = floored_set(b["mulv"], fb)
+    beta = torch.where(fl, torch.zeros_like(fl, dtype=F64), torch.full(fl.shape, klw, dtype=F64, device=fl.device))
+    return tc_rule(*reparam_bwd_ref(b["dz"], b["mulv"], b["eps"], beta), tc)
+
+
+def check_backward(spec, b, W, pl, klw, fb=0.0, only=None, tc=None):
     """Ratios of the backward stages B.<layer>: layer's backward-data (the gradient of the previous layer's
-    output) and the bias partial rows it emits. ``only``: layer names to check (None: all)."""
+    output) and the bias partial rows it emits. ``only``: layer names to check (None: all). ``tc``: (tc_t, g64,
+    bg) of ``knob_cases.tc_of`` when the step folds the total-correlation penalty into d[mu|lv] (``tc_fold_k``
+    adds in place and rewrites dmulv16): the reference gains ``tc_t g64`` within ``tc_t bg + 2 U max(|before|,
+    |after|)``; dmulv16 stays the bitwise twin, and the stages fed from the stored dmulv16 (the head's bias
+    partial rows, B.enc_head, WG.enc_head) then show that their kernels consumed the folded value."""
     M, Z = b["z16"].shape
     dev = b["z16"].device
     out = {}
@@ -578,9 +594,7 @@ def check_backward(spec, b, W, pl, klw, fb=0.0, only=None):
                 out[tag + "dz"] = ratio(b["dz"], *slab_sum_ref(got))
             else:
                 out[tag + "dz"] = ratio(b["dz"], gm @ wm, ck.fwd_bound(gm.abs() @ wm.abs(), q.k))
-            fl = floored_set(b["mulv"], fb)
-            beta = torch.where(fl, torch.zeros_like(fl, dtype=F64), torch.full(fl.shape, klw, dtype=F64, device=dev))
-            out[tag + "dmulv"] = ratio(b["dmulv"], *reparam_bwd_ref(b["dz"], b["mulv"], b["eps"], beta))
+            out[tag + "dmulv"] = ratio(b["dmulv"], *dmulv_ref(b, klw, fb, tc))
             out[tag + "dmulv16"] = _bits_ratio(twin_ok(b["dmulv16"].reshape(-1), b["dmulv"].reshape(-1)))
             # the head's bias partials: the colsum kernel over the bf16 gradient
             out[tag + "colsum"] = _colsum16(b["dmulv16"], b["colsum"]["enc_head"])
@@ -699,12 +713,12 @@ def stages(spec):
 
 def stage_of(key: str) -> str:
     p = key.split(".")
-    return p[0] if p[0] in ("WG", "AD") else p[0] + "." + p[1]
+    return p[0] if p[0] in ("WG", "AD", "EM") else p[0] + "." + p[1]
 
 
 def first_failure(spec, ratios: dict):
     """The first stage (in step order) with a ratio > 1, or None."""
-    for st in stages(spec):
+    for st in stages(spec) + ["EM"]:   # EM: the weight average after the step (knob_cases.check_ema)
         if any(not r <= 1 for k, r in ratios.items() if stage_of(k) == st):
             return st
     return None

@@ -16,6 +16,15 @@ Let u = 2^-24 (f32 unit roundoff).
   GEMM's bound through the formula's partial derivatives (sigmoid: |dp| <= |dt|/4)
   plus ``8 u sum|terms|`` for the formula's own roundings.
 * Philox noise: ``ops.philox.reparam_eps`` at rtol = atol = 1e-5.
+* Free bits (``fb`` > 0): the floored set is the float64 one, kl_d < fb, from the
+  stored mulv (the tests keep every element away from the floor:
+  ``free_bits_cases.check_floor``); a floored element adds exactly fb to the KLD
+  sum and its KL gradient is exactly zero (weight 0 in the dmu / dlv formulas).
+* Total-correlation penalty (``tc`` = (tc_t, g64, bg) of ``knob_cases.tc_of``):
+  d[mu|lv] is the value and bound above plus ``tc_t g64`` within
+  ``tc_t bg + 2 u max(|before|, |after|)`` (``knob_cases.tc_rule``); the later
+  stages (dh1, the fc21 / fc22 gradients) read the stored dmulv and so show that
+  their kernels consumed the folded value.
 * Loss: relative 1e-4. The BCE terms are non-negative and no value passes
   through more than a few hundred additions (F3's tile and wave sums, then at
   most 256 partials per thread in the loss reduction at the last BCE slot), so
@@ -138,8 +147,16 @@ def bce_terms(t, x):
     return x * torch.clamp(sp_pos - t, max=100.0) + (1 - x) * torch.clamp(sp_pos, max=100.0)
 
 
+def floored_set(mulv, Z: int, fb: float):
+    """The float64 floored set kl_d < fb ([M, Z] bool; empty for fb = 0)."""
+    m = mulv.double()
+    mu, lv = m[:, :Z], m[:, Z:]
+    kl = 0.5 * (mu * mu + torch.exp(lv) - 1 - lv)
+    return kl < fb if fb > 0 else torch.zeros_like(kl, dtype=torch.bool)
+
+
 def check_forward(dev: Dict[str, torch.Tensor], v, x, beta: float, eps_host: Optional[np.ndarray],
-                  loss: Optional[float]) -> Dict[str, float]:
+                  loss: Optional[float], fb: float = 0.0) -> Dict[str, float]:
     """Ratios of the stored forward stages. ``dev``: CPU copies of the device's
     h1, mulv, eps, z, h3 and (when stored) recon, dlog; ``v``: parameter views;
     ``x``: the batch rows; ``loss``: the device's loss (None: not checked)."""
@@ -164,18 +181,39 @@ def check_forward(dev: Dict[str, torch.Tensor], v, x, beta: float, eps_host: Opt
     if "dlog" in d:
         out["dlog"] = ratio(d["dlog"], p - x, bt / 4 + 8 * U * (p + x.abs()))
     if loss is not None:
-        kld = -0.5 * (1 + lv - mu * mu - sd * sd).sum()
+        kl = -0.5 * (1 + lv - mu * mu - sd * sd)
+        kld = torch.where(floored_set(d["mulv"], Z, fb), torch.full_like(kl, fb), kl).sum()
         ref = float(bce_terms(t, x).sum() + beta * kld)
         out["loss"] = abs(loss - ref) / (LOSS_REL * abs(ref))
     return out
 
 
-def check_backward(dev: Dict[str, torch.Tensor], grads, v, x, beta: float) -> Dict[str, float]:
+def dmulv_ref(d, W3, beta: float, fb: float = 0.0, tc=None):
+    """(ref, bound) of d[mu|lv] from the stored dh3, mulv and eps (float64 dict ``d``)."""
+    from tests.knob_cases import tc_rule
+
+    Z = W3.shape[1]
+    dz, bz = gemm_ref(d["dh3"], W3)
+    mu, lv = d["mulv"][:, :Z], d["mulv"][:, Z:]
+    sd = torch.exp(0.5 * lv)
+    es = d["eps"] * sd
+    # beta: the KL weight, or an [M, Z] tensor of per-element weights (tests/gpu/test_free_bits_gpu.py)
+    bt = beta.double() if torch.is_tensor(beta) else torch.full_like(mu, beta)
+    be = torch.where(floored_set(d["mulv"], Z, fb), torch.zeros_like(mu), bt)
+    dmu = dz + be * mu
+    bmu = bz + 8 * U * (dz.abs() + (be * mu).abs())
+    dlv = 0.5 * dz * es + 0.5 * be * (sd * sd - 1)
+    blv = bz * 0.5 * es.abs() + 8 * U * ((0.5 * dz * es).abs() + 0.5 * be.abs() * (sd * sd + 1))
+    return tc_rule(torch.cat([dmu, dlv], 1), torch.cat([bmu, blv], 1), tc)
+
+
+def check_backward(dev: Dict[str, torch.Tensor], grads, v, x, beta: float, fb: float = 0.0,
+                   tc=None) -> Dict[str, float]:
     """Ratios of the stored backward stages and the ten gradient tensors, each
-    against float64 from the device's own inputs of that stage."""
+    against float64 from the device's own inputs of that stage. ``fb``: the
+    floor the kernels read; ``tc``: (tc_t, g64, bg) or None (module docstring)."""
     W1, b1, W2, b2, W3, b3, W4, b4 = _w(v)
     x = x.double()
-    Z = W3.shape[1]
     d = {k: t.double() for k, t in dev.items()}
     g = {k: t.double() for k, t in grads.items()}
     M = x.shape[0]
@@ -183,15 +221,7 @@ def check_backward(dev: Dict[str, torch.Tensor], grads, v, x, beta: float) -> Di
     out = {}
     m3, m1 = d["h3"] > 0, d["h1"] > 0
     out["dh3"] = check_gemm(d["dh3"], d["dlog"], W4, mask=m3)
-    dz, bz = gemm_ref(d["dh3"], W3)
-    mu, lv = d["mulv"][:, :Z], d["mulv"][:, Z:]
-    sd = torch.exp(0.5 * lv)
-    es = d["eps"] * sd
-    dmu = dz + beta * mu
-    bmu = bz + 8 * U * (dz.abs() + (beta * mu).abs())
-    dlv = 0.5 * dz * es + 0.5 * beta * (sd * sd - 1)
-    blv = bz * 0.5 * es.abs() + 8 * U * ((0.5 * dz * es).abs() + 0.5 * abs(beta) * (sd * sd + 1))
-    out["dmulv"] = ratio(d["dmulv"], torch.cat([dmu, dlv], 1), torch.cat([bmu, blv], 1))
+    out["dmulv"] = ratio(d["dmulv"], *dmulv_ref(d, W3, beta, fb, tc))
     out["dh1"] = check_gemm(d["dh1"], d["dmulv"], W2, mask=m1)
 
     def wg(name_w, name_b, dy, a):  # dW = dy^T a, db = dy^T 1 (K = M)
@@ -221,3 +251,16 @@ def exact_ok(A, B, bias=None, lsb: float = 1.0) -> bool:
 def randint(g, shape, lo, hi):
     """Integers in [lo, hi] as float32."""
     return torch.randint(lo, hi + 1, shape, generator=g).float()
+
+
+# stage names in step order (the keys of check_forward + check_backward; AD and EM: tests/knob_cases.py)
+STAGES = ("h1", "mulv", "eps", "z", "h3", "recon", "dlog", "loss", "dh3", "dmulv", "dh1", "gfc4", "gfc3", "gfc21",
+          "gfc1", "AD", "EM")
+
+
+def first_failure(ratios: dict):
+    """The first stage (in step order) with a ratio > 1, or None."""
+    for st in STAGES:
+        if any(not r <= 1 for k, r in ratios.items() if k.split(".")[0] == st):
+            return st
+    return None

@@ -41,20 +41,32 @@ def _block_sums(v, owners):
     return torch.stack([v[o].sum() for o in owners])
 
 
-def _adam(p, g, m, v, c):
+def _adam(p, g, m, v, c, mut=None):
     f = lambda x: torch.tensor(x, dtype=torch.float32)
-    gr = g * f(c["gs"])
-    m2 = m + f(c["omb1"]) * (gr - m)
-    v2 = f(c["b2"]) * v + f(c["omb2"]) * gr * gr
+    gr = g * f(1.0 if mut == "no_grad_scale" else c["gs"])
+    if c["wd"] != 0:
+        if c["decoupled"]:   # the decay uses the step's lr_t (mutation: the unscheduled lr)
+            p = p * (1 - f(c["lr0"] if mut == "decay_lr" else c["lr"]) * f(c["wd"]))
+        else:
+            gr = gr + f(c["wd"]) * p
+    # adam_update's two fmaf: the product of two f32 numbers is exact in float64, so one rounding each
+    m2 = (m.double() + f(c["omb1"]).double() * (gr - m).double()).float()
+    v2 = ((f(c["b2"]) * v).double() + f(c["omb2"]).double() * (gr * gr).double()).float()
     den = v2.sqrt() / f(c["bc2s"]) + f(c["eps"])
     return p - f(c["step_size"]) * m2 / den, m2, v2
 
 
-def emulate(spec, P, X, idx, B, M, cursor, step, klw=1.0, fb=0.0, mut=None, opt=None, stale=None):
-    """One step in f32 -> (buffers, grads, slabs, loss, after). ``mut`` names one mutation (MUTATIONS);
-    ``opt``: named exp_avg / exp_avg_sq (zeros when None); ``stale``: weights of an earlier step that the
-    ``stale_dec`` mutation lets dec1 read."""
+def emulate(spec, P, X, idx, B, M, cursor, step, klw=1.0, fb=0.0, mut=None, opt=None, stale=None, kn=None):
+    """One step in f32 -> (buffers, grads, slabs, loss, after). ``mut`` names one mutation (MUTATIONS, or
+    those of tests/unit/test_knob_cases.py); ``opt``: named exp_avg / exp_avg_sq (zeros when None); ``stale``:
+    weights of an earlier step that the ``stale_dec`` mutation lets dec1 read. ``kn``: the other knobs of
+    tests/knob_cases.py -- tc_t and tc_weight (the penalty's share, folded into d[mu|lv] after the
+    reparameterisation backward, dmulv16 rewritten), c (Adam's constants, with lr0 the unscheduled lr), e0,
+    decay and t (the weight average, after Adam)."""
     from multidisttorch_amd.ops.philox import reparam_eps
+    from tests import tc_cases as tcc
+
+    kn = kn or {}
 
     pl = lk.plans(spec, M)
     W = lk.weights_of(P, spec)
@@ -90,7 +102,8 @@ def emulate(spec, P, X, idx, B, M, cursor, step, klw=1.0, fb=0.0, mut=None, opt=
             sd = torch.exp(0.5 * lv)
             b["z16"] = _bf(mu + b["eps"] * sd)
             ksum = 1 + lv - mu * mu - sd * sd
-            fl = (-0.5 * ksum < fb) if fb > 0 else torch.zeros_like(ksum, dtype=torch.bool)
+            kl_f = np.float32(klw) * (-0.5 * ksum) if mut == "floor_with_klt" else -0.5 * ksum
+            fl = (kl_f < fb) if fb > 0 else torch.zeros_like(ksum, dtype=torch.bool)
             term = -0.5 * torch.where(fl, torch.full_like(ksum, -2 * fb), ksum)
             b["kld_part"] = _block_sums(term, sk.block_owners(M, Z, q.ksplit if q.ksplit > 1 else None))
             h = b["z16"]
@@ -134,10 +147,17 @@ def emulate(spec, P, X, idx, B, M, cursor, step, klw=1.0, fb=0.0, mut=None, opt=
             dz = b["dz"]
             be = torch.where(fl, torch.zeros_like(dz), torch.full_like(dz, 1.0 if mut == "kl_weight" else klw))
             b["dmulv"] = torch.cat([dz + be * mu, 0.5 * dz * b["eps"] * sd + 0.5 * be * (sd * sd - 1)], 1)
-            b["dmulv16"] = _bf(b["dmulv"])
+            pre16 = _bf(b["dmulv"])
+            if kn.get("tc_t"):
+                tct = kn["tc_weight"] if mut == "tc_no_ramp" else kn["tc_t"]
+                add = np.float32(tct) * tcc.oracle(b["mulv"], b["eps"], torch.float32)[1].float()
+                if mut == "fold_skips_floored":
+                    add = add * (~torch.cat([fl, fl], 1))
+                b["dmulv"] = b["dmulv"] + add
+            b["dmulv16"] = pre16 if mut == "dmulv16_prefold" else _bf(b["dmulv"])
             src = b["dmulv"] if mut == "lin_bias_f32" else b["dmulv16"].float()
             b["colsum"]["enc_head"] = _rows8(src)
-            g = b["dmulv16"]
+            g = pre16 if mut == "consumer_prefold" else b["dmulv16"]
             continue
         if q == "thin":
             v = ck.im2col(g.float().reshape(M, H, H, 1), 4, 2, 1) @ w.reshape(CO, 16).T
@@ -172,6 +192,8 @@ def emulate(spec, P, X, idx, B, M, cursor, step, klw=1.0, fb=0.0, mut=None, opt=
         if mut == "wg_pair" and l.name == "dec1":   # the mirror encoder layer's pair: same conv-view geometry
             src = [j for j, m in enumerate(spec) if m.name == "enc2"][0]
         G, Xw = lk.wg_pair(spec, src, b)
+        if mut == "wg_prefold" and l.name == "enc_head":
+            G = pre16.reshape(G.shape)
         xf = Xw.float() if wp.cfg == 110 else Xw.to(BF).float()
         cols = ck.im2col(xf, k, s, p)
         Gm = G.float().reshape(-1, CO)
@@ -188,14 +210,20 @@ def emulate(spec, P, X, idx, B, M, cursor, step, klw=1.0, fb=0.0, mut=None, opt=
         grads[l.name + ".bias"] = part.reshape(brows[l.name], l.cout).sum(0)
     total = float(b["bce_part"].sum() + np.float32(klw) * b["kld_part"].sum())
     # ---- Adam
-    c = sk.adam_consts(HP, step + (2 if mut == "adam_step" else 1))
-    after = dict(params={}, exp_avg={}, exp_avg_sq={}, w16={})
+    c = kn["c"] if "c" in kn else sk.adam_consts(HP, step + (2 if mut == "adam_step" else 1))
+    after = dict(params={}, exp_avg={}, exp_avg_sq={}, w16={}, ema={})
     for name, gr in grads.items():
         m0 = opt["exp_avg"][name] if opt else torch.zeros_like(gr)
         v0 = opt["exp_avg_sq"][name] if opt else torch.zeros_like(gr)
-        p2, m2, v2 = _adam(P[name].float().reshape(-1), gr, m0.reshape(-1), v0.reshape(-1), c)
+        p2, m2, v2 = _adam(P[name].float().reshape(-1), gr, m0.reshape(-1), v0.reshape(-1), c, mut)
         after["params"][name], after["exp_avg"][name], after["exp_avg_sq"][name] = p2, m2, v2
         after["w16"][name] = p2.to(BF)
+        if "e0" in kn:   # e + (1 - d_t) (p - e) from the parameters Adam just wrote, at the step it advanced to
+            from multidisttorch_amd.models.trainer_base import ema_omd
+
+            e0 = kn["e0"][name].float().reshape(-1)
+            omd = np.float32(ema_omd(kn["decay"], kn["t"] - (1 if mut == "ema_prev_d" else 0)))
+            after["ema"][name] = e0 + omd * ((P[name].float().reshape(-1) if mut == "ema_pre_adam" else p2) - e0)
     return b, grads, slabs, total, after
 
 

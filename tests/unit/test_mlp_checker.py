@@ -96,3 +96,53 @@ def test_checker_rejects_what_it_should():
     # representable, but a partial sum may not be: 2^24 + 1 - 1
     assert not ck.exact_ok(torch.tensor([[4096.0, 1.0, -1.0]]), torch.tensor([[4096.0], [1.0], [1.0]]))
     assert ck.exact_ok(torch.ones(1, 1024), torch.ones(1024, 1))
+
+
+# ------------------------------------------------- f32 emulation of one step ----
+def emulate(v, x, eps, klw, fb=0.0, mut=None, kn=None):
+    """One MLP-VAE step in plain f32 torch -> (stored activations, named gradients, loss), with the knobs of
+    tests/knob_cases.py: the free-bits floor (decided on kl_d itself), and with ``kn`` = dict(tc_t, tc_weight)
+    the total-correlation share added to d[mu|lv] after the floor decision, before dh1 and the fc21 / fc22
+    gradients read it. ``mut`` names one mutation of tests/unit/test_knob_cases.py."""
+    import numpy as np
+
+    from tests import tc_cases as tcc
+
+    kn = kn or {}
+    Z = v["fc3.weight"].shape[1]
+    W2 = torch.cat([v["fc21.weight"], v["fc22.weight"]], 0)
+    b2 = torch.cat([v["fc21.bias"], v["fc22.bias"]], 0)
+    d = {}
+    d["h1"] = torch.relu(x @ v["fc1.weight"].t() + v["fc1.bias"])
+    d["mulv"] = d["h1"] @ W2.t() + b2
+    mu, lv = d["mulv"][:, :Z], d["mulv"][:, Z:]
+    d["eps"] = eps.float()
+    sd = torch.exp(0.5 * lv)
+    d["z"] = mu + d["eps"] * sd
+    d["h3"] = torch.relu(d["z"] @ v["fc3.weight"].t() + v["fc3.bias"])
+    t = d["h3"] @ v["fc4.weight"].t() + v["fc4.bias"]
+    d["recon"] = torch.sigmoid(t)
+    d["dlog"] = d["recon"] - x
+    kl = -0.5 * (1 + lv - mu * mu - sd * sd)
+    kl_f = np.float32(klw) * kl if mut == "floor_with_klt" else kl
+    fl = (kl_f < fb) if fb > 0 else torch.zeros_like(kl, dtype=torch.bool)
+    loss = float(ck.bce_terms(t, x).sum() + np.float32(klw) * torch.where(fl, torch.full_like(kl, fb), kl).sum())
+    d["dh3"] = (d["dlog"] @ v["fc4.weight"]) * (d["h3"] > 0)
+    dz = d["dh3"] @ v["fc3.weight"]
+    be = torch.where(fl, torch.zeros_like(dz), torch.full_like(dz, klw))
+    pre = torch.cat([dz + be * mu, 0.5 * dz * d["eps"] * sd + 0.5 * be * (sd * sd - 1)], 1)
+    d["dmulv"] = pre
+    if kn.get("tc_t"):
+        tct = kn["tc_weight"] if mut == "tc_no_ramp" else kn["tc_t"]
+        add = np.float32(tct) * tcc.oracle(d["mulv"], d["eps"], torch.float32)[1].float()
+        if mut == "fold_skips_floored":
+            add = add * (~torch.cat([fl, fl], 1))
+        d["dmulv"] = pre + add
+    d["dh1"] = ((pre if mut == "consumer_prefold" else d["dmulv"]) @ W2) * (d["h1"] > 0)
+    gml = pre if mut == "wg_prefold" else d["dmulv"]
+    g = {"fc4.weight": d["dlog"].t() @ d["h3"], "fc4.bias": d["dlog"].sum(0),
+         "fc3.weight": d["dh3"].t() @ d["z"], "fc3.bias": d["dh3"].sum(0),
+         "fc21.weight": gml[:, :Z].t() @ d["h1"], "fc21.bias": gml[:, :Z].sum(0),
+         "fc22.weight": gml[:, Z:].t() @ d["h1"], "fc22.bias": gml[:, Z:].sum(0),
+         "fc1.weight": d["dh1"].t() @ x, "fc1.bias": d["dh1"].sum(0)}
+    return d, g, loss
