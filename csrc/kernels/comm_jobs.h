@@ -25,7 +25,7 @@
 //                replica), scale (1/s), then Adam + the bf16 weight copy in
 //                the same thread;
 //   push+reduce  both in one workgroup, the own contribution kept in registers.
-// The 28x28 DDP step (models/conv_vae.py::_step28) puts the decoder units'
+// The 28x28 DDP step (models/conv28.py::_step28) puts the decoder units'
 // push into the launch that computes the encoder weight gradients -- the
 // decoder bucket's transfer runs on the xGMI links while those workgroups
 // compute -- and ends with ONE launch of push+reduce (encoder) || reduce

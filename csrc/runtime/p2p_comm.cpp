@@ -127,6 +127,11 @@ class XgmiP2PReducer : public StreamBuckets {
     TORCH_CHECK(s_ >= 1 && s_ <= kP2PMaxRanks, "XgmiP2PReducer: group size must be 1..", kP2PMaxRanks);
     TORCH_CHECK(me_ >= 0 && me_ < s_, "XgmiP2PReducer: rank out of range");
     TORCH_CHECK(flat_.scalar_type() == torch::kFloat32, "XgmiP2PReducer: f32 gradient arena required");
+    // comm_jobs.h: a vec4 thread stores 16 B at [parity][src][numel] + arena offset in a peer's region, so
+    // the slot pitch (numel) must keep those stores aligned (both trainers' arenas are 64-aligned)
+    TORCH_CHECK(!fused || s_ == 1 || flat_.numel() % 4 == 0,
+                "XgmiP2PReducer: a fused reducer of a group > 1 needs an arena whose numel is a multiple of 4, got ",
+                flat_.numel());
     scale_ = (float)(scale > 0 ? scale : (average ? 1.0 / s_ : 1.0));
     timeout_ticks_ = (long long)(timeout_s * 1e8);  // s_memrealtime: 100 MHz
     const int64_t nb = num_buckets();

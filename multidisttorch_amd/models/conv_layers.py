@@ -365,7 +365,7 @@ class LayerPathStep:
         has no instantiation."""
         p = self._plan(M)
         lu = p["layer_units"]
-        push = lambda job: self._comm_job(p["segs"], p["units"], lu[lo], lu[hi], 1, True, job=job)
+        push = lambda job: self._comm_job(p["segs"], p["units"], lu[lo], lu[hi], 1, not self.comm_skip_adam, job=job)
         return self._launch_fused([self._job(f) for f in fns + [push]], "no comm fusion")
 
     def _comm_tail(self, M, lo, hi):
@@ -373,15 +373,15 @@ class LayerPathStep:
         layers not pushed yet ([lo, hi), the first layer included) || reduce+Adam
         of the ones pushed by the backward launches ([hi, L)), one launch."""
         p, L = self._plan(M), len(self.spec)
-        lu = p["layer_units"]
-        jobs = [self._comm_job(p["segs"], p["units"], lu[lo], lu[hi], 3, True)]
+        lu, adam = p["layer_units"], not self.comm_skip_adam
+        jobs = [self._comm_job(p["segs"], p["units"], lu[lo], lu[hi], 3, adam)]
         if hi < L:
-            jobs.append(self._comm_job(p["segs"], p["units"], lu[hi], lu[L], 2, True))
+            jobs.append(self._comm_job(p["segs"], p["units"], lu[hi], lu[L], 2, adam))
         if len(jobs) == 2:
             ok = self._launch_fused(jobs, "no comm tail")
             assert ok, "jobs_k<JComm, JComm> missing from conv_jobs.hip"
         else:
-            pack, grid = self._comm_single_pack(("tail", M, lo, hi), jobs[0])
+            pack, grid = self._comm_single_pack(("tail", M, lo, hi, adam), jobs[0])
             self.C.launch_jobs_multi(pack, grid)
 
     def _comm_single_pack(self, key, job):

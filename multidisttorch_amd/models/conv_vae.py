@@ -110,6 +110,9 @@ class ConvVaeTrainer(Fused28Step, LayerPathStep, VaeTrainerBase):
         # the GPU (tests/gpu/conv_ddp_worker.py)
         self.comm_split_tail = False
         self.comm_phase_hook = None
+        # tests: the layer path's comm jobs leave the reduced gradients in `grads`, no update
+        # (what f28_skip_adam is to the fused 28x28 step)
+        self.comm_skip_adam = False
         torch.manual_seed(self.seed if init_seed is None else init_seed)
         ref = TorchConvVAE(self.spec, image, channels, z)
         f32 = dict(dtype=torch.float32, device=self.device)

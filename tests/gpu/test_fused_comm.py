@@ -3,7 +3,8 @@
 The reference's intra-group DDP (/root/reference/vae-hpo.py:72, :130) launches
 bucket all-reduces from autograd hooks on NCCL's stream and runs foreach-Adam
 after the wait. Here, with a fused XgmiP2PReducer ("xgmi"), the all-reduce is
-a set of JOBS inside the step's own launches: the decoder units' push runs in
+a set of JOBS inside the step's own launches (models/conv28.py::_step28; the
+layer path: models/conv_layers.py::_comm_tail): the decoder units' push runs in
 the launch that computes the encoder weight gradients, and one tail launch
 does push+reduce (encoder) || reduce (decoder) with Adam fused in.
 
@@ -16,6 +17,9 @@ DDP step structure is exercised and timed on a one-GPU box:
     which proves the scaled reduce actually ran on every unit;
   * the DDP step costs at most ~1.15x the reducer-free step (the verdict's
     structure-cost bar; measured numbers in profiles/r4_ddp_fused).
+
+The values with MORE than one rank (different gradients per rank) are checked
+in tests/gpu/test_comm_jobs_values.py.
 """
 import time
 

@@ -4,6 +4,8 @@ torch fp32 reference of the slab sum."""
 import pytest
 import torch
 
+from tests.comm_checker import _emulated_sum
+
 pytestmark = pytest.mark.gpu
 
 
@@ -41,27 +43,6 @@ def test_grad_finalize_vec4_units_match_scalar_units(ns, native_ext):
     for a, b in zip(by[(256, True)][1:], by[(1024, True)][1:]):
         assert torch.equal(a, b)
     assert not torch.equal(by[(1024, True)][1], P0)  # Adam actually updated the parameters
-
-
-def _emulated_sum(slab, rp):
-    """The finalize kernel's summation order in float32 (conv_small.h): thread
-    row rl sums slabs rl, rl + rp, ... into 4 interleaved accumulators (full
-    quads, the remainder into the first), then row 0 adds the rp row sums in
-    order starting from 0."""
-    ns = slab.shape[0]
-    z = torch.zeros(slab.shape[1], dtype=torch.float32)
-    g = z.clone()
-    for rl in range(rp):
-        ks = list(range(rl, ns, rp))
-        a = [z.clone() for _ in range(4)]
-        q = len(ks) // 4
-        for i in range(q):
-            for j in range(4):
-                a[j] = a[j] + slab[ks[4 * i + j]]
-        for k in range(4 * q, len(ks)):
-            a[0] = a[0] + slab[ks[k]]
-        g = g + ((a[0] + a[1]) + (a[2] + a[3]))
-    return g
 
 
 @pytest.mark.parametrize("ns,cnt", [(5, 16), (20, 128), (131, 16), (131, 256), (300, 64), (3, 1024), (16, 1024),
