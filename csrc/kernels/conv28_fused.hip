@@ -10,7 +10,11 @@
 #include <stddef.h>
 #include <stdlib.h>
 
+#include <type_traits>
+
 #include "conv28_pair.h"
+#include "conv28_slots.h"
+#include "conv_launch.h"
 
 namespace mdt {
 namespace f28 {
@@ -119,94 +123,66 @@ using namespace mdt;
 
 namespace {
 
-template <class T>
-T* P(const long long* p, int i) {
-  return reinterpret_cast<T*>((intptr_t)p[i]);
+// One slot of a table (conv28_slots.h) into the argument member of its name.
+// The slot's dtype tag, which the bindings check the tensor against, must be
+// the member's element type.
+template <char Tag, class T>
+void put(T*& member, const long long* p, int slot) {
+  using E = std::remove_const_t<T>;
+  static_assert(Tag == 'f'   ? std::is_same_v<E, float>
+                : Tag == 'b' ? std::is_same_v<E, __bf16>
+                : Tag == 'i' ? std::is_same_v<E, int> || std::is_same_v<E, unsigned>
+                : Tag == 'l' ? std::is_same_v<E, unsigned long long>
+                : Tag == 'u' ? std::is_same_v<E, TrainState> || std::is_same_v<E, HParams>
+                             : false,
+                "conv28_slots.h: the slot's dtype tag is not the argument member's element type");
+  member = reinterpret_cast<T*>((intptr_t)p[slot]);
 }
 
 void fill_weights(f28::Weights& w, const long long* p) {
-  w.W1f = P<const float>(p, 0);
-  w.b1 = P<const float>(p, 1);
-  w.W2 = P<const __bf16>(p, 2);
-  w.b2 = P<const float>(p, 3);
-  w.Wh = P<const __bf16>(p, 4);
-  w.bh = P<const float>(p, 5);
-  w.Wd = P<const __bf16>(p, 6);
-  w.bd = P<const float>(p, 7);
-  w.W3 = P<const __bf16>(p, 8);
-  w.b3 = P<const float>(p, 9);
-  w.W4f = P<const float>(p, 10);
-  w.b4 = P<const float>(p, 11);
+#define MDT_PUT(name, tag, ...) put<tag>(w.name, p, f28::kW_##name);
+  MDT_F28_WEIGHT_SLOTS(MDT_PUT)
+#undef MDT_PUT
 }
 
 void fill_fwd(f28::FwdArgs& a, const long long* p, int B, unsigned stream, int train) {
   fill_weights(a.w, p);
-  a.X = P<const float>(p, 12);
-  a.idx = P<const int>(p, 13);
-  a.st = P<const TrainState>(p, 14);
-  a.hp = P<const HParams>(p, 15);
+  put<f28::kFwdSlots[f28::kFwd_state].dtype>(a.st, p, f28::kFwd_state);
+  put<f28::kFwdSlots[f28::kFwd_hparams].dtype>(a.hp, p, f28::kFwd_hparams);
+#define MDT_PUT(name, tag, ...) put<tag>(a.name, p, f28::kFwd_##name);
+  MDT_F28_FWD_BUFFER_SLOTS(MDT_PUT)
+#undef MDT_PUT
   a.B = B;
   a.stream = stream;
   a.train = train;
-  a.xb = P<float>(p, 16);
-  a.a1 = P<__bf16>(p, 17);
-  a.a2 = P<__bf16>(p, 18);
-  a.mulv = P<float>(p, 19);
-  a.eps = P<float>(p, 20);
-  a.z16 = P<__bf16>(p, 21);
-  a.d0 = P<__bf16>(p, 22);
-  a.d1 = P<__bf16>(p, 23);
-  a.dlog = P<float>(p, 24);
-  a.recon = P<float>(p, 25);
-  a.bce_part = P<float>(p, 26);
-  a.kld_part = P<float>(p, 27);
-  a.db4_part = P<float>(p, 28);
-  a.stamps = P<unsigned long long>(p, 29);
   a.pf_slices = 16;
-  a.xn = P<const float>(p, 30);
-  a.xtag = P<const unsigned>(p, 31);
 }
 
 void fill_bwd(f28::BwdArgs& a, const long long* p, int M, const TrainState* st) {
   fill_weights(a.w, p);
-  a.klw = st ? &st->kl_next : &P<const HParams>(p, 12)->kl_beta;  // device addresses, not dereferenced here
-  a.fbw = st ? &st->fb_t : &P<const HParams>(p, 12)->free_bits;
-  a.mulv = P<const float>(p, 13);
-  a.eps = P<const float>(p, 14);
-  a.a1 = P<const __bf16>(p, 15);
-  a.a2 = P<const __bf16>(p, 16);
-  a.d0 = P<const __bf16>(p, 17);
-  a.d1 = P<const __bf16>(p, 18);
-  a.dlog = P<const float>(p, 19);
-  a.gd1 = P<__bf16>(p, 20);
-  a.gd0 = P<__bf16>(p, 21);
-  a.dbd_part = P<float>(p, 22);
-  a.dmulv = P<float>(p, 23);
-  a.dmulv16 = P<__bf16>(p, 24);
-  a.ga2 = P<__bf16>(p, 25);
-  a.ga1 = P<__bf16>(p, 26);
-  a.db3_part = P<float>(p, 27);
-  a.db2_part = P<float>(p, 28);
-  a.db1_part = P<float>(p, 29);
-  a.stamps = P<unsigned long long>(p, 30);
+  const HParams* hp;
+  put<f28::kBwdSlots[f28::kBwd_hparams].dtype>(hp, p, f28::kBwd_hparams);
+  a.klw = st ? &st->kl_next : &hp->kl_beta;  // device addresses, not dereferenced here
+  a.fbw = st ? &st->fb_t : &hp->free_bits;
+#define MDT_PUT(name, tag, ...) put<tag>(a.name, p, f28::kBwd_##name);
+  MDT_F28_BWD_BUFFER_SLOTS(MDT_PUT)
+#undef MDT_PUT
   a.db2_m2 = M;  // db2_part is always [2][M][64] (second row: the paired step's role-1 half)
+}
+
+// false: no pair table, or one with a null slot
+bool fill_pair(f28::PairCtl& pc, const long long* pp) {
+  if (!pp) return false;
+#define MDT_PUT(name, tag, ...) put<tag>(pc.name, pp, f28::kPair_##name);
+  MDT_F28_PAIR_SLOTS(MDT_PUT)
+#undef MDT_PUT
+  return pc.xg && pc.pairw && pc.err;
 }
 
 }  // namespace
 
 extern "C" {
 
-// Pointer tables (validated by the caller, csrc/runtime/conv_ops.cpp):
-// forward  [0..11] weights (W1f b1 W2 b2 Wh bh Wd bd W3 b3 W4f b4), 12 X, 13 idx,
-//          14 state, 15 hparams, 16 xb, 17 a1, 18 a2, 19 mulv, 20 eps, 21 z16,
-//          22 d0, 23 d1, 24 dlog, 25 recon, 26 bce_part, 27 kld_part, 28 db4_part,
-//          29 stamps (optional)
-// backward [0..11] weights, 12 hparams, 13 mulv, 14 eps, 15 a1, 16 a2, 17 d0,
-//          18 d1, 19 dlog, 20 gd1, 21 gd0, 22 dbd_part, 23 dmulv, 24 dmulv16,
-//          25 ga2, 26 ga1, 27 db3_part, 28 db2_part ([2][M][64]), 29 db1_part,
-//          30 stamps (optional)
-// pair     0 exchange granules [M][2][f28_pair_words], 1 pairing words [M] int32,
-//          2 error word (uint32); all zero before the first launch
 int mdt_f28_forward(const long long* p, int B, int M, unsigned stream, int train, hipStream_t s) {
   if (M <= 0 || M > B) return 1;
   f28::FwdArgs a{};
@@ -223,17 +199,14 @@ int mdt_f28_pair_words() { return f28::kXW; }
 // solo forms are bitwise equal); the backward half of the kernel is skipped.
 int mdt_f28_forward_pair(const long long* p, const long long* pp, int B, int M, unsigned stream, hipStream_t s) {
   if (M <= 0 || M > B) return 1;
-  if (!pp || !pp[0] || !pp[1] || !pp[2]) return 2;
   f28::FwdArgs fa{};
   fill_fwd(fa, p, B, stream, 0);
   fa.pf_slices = 0;
   f28::BwdArgs ba{};
   f28::PairCtl pc{};
+  if (!fill_pair(pc, pp)) return 2;
   pc.M = M;
   pc.pair = 1;
-  pc.xg = P<unsigned long long>(pp, 0);
-  pc.pairw = P<int>(pp, 1);
-  pc.err = P<unsigned>(pp, 2);
   hipLaunchKernelGGL(f28::f28_step_k, dim3(2 * M), dim3(f28::kThreads), 0, s, fa, ba, pc);
   return (int)hipGetLastError();
 }
@@ -258,10 +231,7 @@ int mdt_f28_step(const long long* pf, const long long* pb, const long long* pp, 
   }();
   pc.acquire = acq;
   if (pair) {
-    if (!pp || !pp[0] || !pp[1] || !pp[2]) return 2;
-    pc.xg = P<unsigned long long>(pp, 0);
-    pc.pairw = P<int>(pp, 1);
-    pc.err = P<unsigned>(pp, 2);
+    if (!fill_pair(pc, pp)) return 2;
     // no P0 L2 prefetch in the paired form: measured 0.0636-0.0639 vs
     // 0.0638-0.0644 ms/step on the driver command with 32 slices, 200/20
     // 0.0608-0.0613 vs 0.0616-0.0622 (profiles/r4_end, gpurun_out r4af/r4ag)

@@ -9,6 +9,7 @@
 #include "adam_common.h"
 #include "conv_igemm.h"
 #include "conv_small.h"
+#include "conv_launch.h"
 
 namespace mdt {
 

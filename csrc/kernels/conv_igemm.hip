@@ -27,6 +27,7 @@
 #include "conv_direct.h"
 #include "conv_dwgrad.h"
 #include "conv_thin_wg.h"
+#include "conv_launch.h"
 
 namespace mdt {
 

@@ -28,6 +28,7 @@
 #include "conv_small.h"
 #include "conv_thin.h"
 #include "conv_thin_wg.h"
+#include "conv_launch.h"
 
 namespace mdt {
 using namespace tiles;

@@ -17,6 +17,7 @@
 #include <stdlib.h>
 
 #include "conv_thin.h"
+#include "conv_launch.h"
 
 namespace mdt {
 

@@ -1,6 +1,7 @@
 // Hardware probes used by the profiling tools (multidisttorch_amd/obs/probe.py):
 // shader clock under load, dependent-load latency, empty-kernel cost.
 #include "common.h"
+#include "probe.h"
 
 namespace mdt {
 

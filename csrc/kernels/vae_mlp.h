@@ -166,4 +166,9 @@ int mdt_vae_forward(const mdt::VaeArgs* a, hipStream_t s);
 int mdt_vae_encode(const mdt::VaeArgs* a, hipStream_t s);  // F1 only
 int mdt_vae_backward(const mdt::VaeArgs* a, hipStream_t s, int part);
 int mdt_vae_decode(const mdt::VaeArgs* a, const float* zin, hipStream_t s);
+// adam.hip: one fused Adam pass over a flat arena of n (a multiple of 4) elements; the eval-path loss reduction
+int mdt_adam_step(float* p, const float* g, float* m, float* v, long long n, const mdt::HParams* hp,
+                  mdt::TrainState* st, hipStream_t s);
+int mdt_loss_finalize(const mdt::HParams* hp, mdt::TrainState* st, const float* partials, int nkld, int nbce,
+                      hipStream_t s);
 }

@@ -5,82 +5,19 @@
 #include <c10/hip/HIPStream.h>
 #include <ATen/hip/impl/HIPGuardImplMasqueradingAsCUDA.h>
 
+#include <array>
 #include <cmath>
 #include <cstring>
+#include <map>
+#include <memory>
+#include <string>
 #include <tuple>
+#include <unordered_map>
+#include <variant>
 #include <vector>
 
-#include "../kernels/vae_mlp.h"
-
-#include "../kernels/conv_igemm.h"
-
-extern "C" {
-int mdt_igemm_plan(int mode, mdt::ConvDesc d, int allow_split, int* info, int fwd);
-void mdt_dconv_stamps(unsigned long long* p);
-int mdt_wgrad_plan(mdt::ConvDesc d, int* info);
-int mdt_igemm(int mode, const void* A, int a_is_f32, const void* B16, mdt::ConvDesc d, const float* bias, int relu,
-              void* y16, float* y32, const void* omask, float* colsum, float* ws, int skip_combine, hipStream_t s,
-              const mdt::APro* pro, int fwd);
-int mdt_wgrad(const void* G16, const void* X, int x_is_f32, mdt::ConvDesc d, float* out, hipStream_t s);
-int mdt_colsum(const void* G16, int M, int N, int rows_per, float* slab, hipStream_t s);
-int mdt_gather_rows(const float* X, const int* idx, const void* st, int B, int M, int P, float* xb, hipStream_t s);
-int mdt_reparam(const float* mulv, float* eps, void* z16, float* z32, int B, int Z, const void* st, const void* hp,
-                unsigned stream, float* kld_part, hipStream_t s);
-int mdt_reparam_bwd(const float* dz, const float* mulv, const float* eps, float* dmulv, void* dmulv16, int B, int Z,
-                    const float* klw, const float* fbw, hipStream_t s);
-int mdt_bce_logits(const float* logits, const float* X, const int* rows, int B, int P, void* dlog16, float* recon,
-                   float* part, float* gpart, hipStream_t s);
-int mdt_conv_loss_finalize(const float* bce_part, int nb, const float* kld_part, int nk, void* st, const void* hp,
-                           int advance_cursor, hipStream_t s);
-int mdt_step_begin(void* st, const void* hp, hipStream_t s);
-int mdt_adam_cast(float* P, const float* G, float* Mo, float* Vo, void* w16, const void* segs, int nseg,
-                  long long total, const void* st, const void* hp, int do_adam, hipStream_t s);
-int mdt_grad_finalize(float* P, float* G, float* Mo, float* Vo, void* w16, const void* segs, const void* units,
-                      int nunits, const void* st, const void* hp, int do_adam, const float* gX, const int* gidx,
-                      float* xn, unsigned* xtag, int gB, hipStream_t s);
-int mdt_wtrans(const void* w16, void* w16t, const void* segs, const void* units, int nunits, hipStream_t s);
-int mdt_thin_conv(const void* X, int x_is_f32, const float* Wf, mdt::ConvDesc d, const float* bias, int relu, void* y16,
-                  const void* omask, float* colsum, const int* idx, void* st, const void* hp, int B, float* xb,
-                  hipStream_t s);
-int mdt_thin_blocks(int tconv, mdt::ConvDesc d);
-int mdt_thin_tconv(const void* G16, const float* Wf, mdt::ConvDesc d, const float* bias, float* y32, const float* X,
-                   void* dlog16, float* recon, float* part, float* gpart, hipStream_t s);
-int mdt_job_igemm(mdt::JobBlob* g, mdt::JobBlob* c, int mode, const void* A, int a_is_f32, const void* B16,
-                  mdt::ConvDesc d, const float* bias, int relu, void* y16, float* y32, const void* omask,
-                  float* colsum, float* ws, int skip_combine);
-int mdt_job_finalize(mdt::JobBlob* j, float* P, float* G, float* Mo, float* Vo, void* w16, const void* segs,
-                     const void* units, int nunits, const void* st, const void* hp, int do_adam);
-int mdt_job_wtrans(mdt::JobBlob* j, const void* w16, void* w16t, const void* segs, const void* units, int nunits);
-int mdt_job_comm(mdt::JobBlob* j, float* P, float* G, float* Mo, float* Vo, void* w16, const void* segs,
-                 const void* units, int nunits, const void* st, const void* hp, int do_adam, const void* ctx, int mode);
-int mdt_combine_reparam(const float* slab, int ks, const float* bias, float* mulv, float* eps, void* z16, float* z32,
-                        int B, int Z, const void* st, const void* hp, unsigned stream, float* kld_part, hipStream_t s);
-int mdt_combine_reparam_blocks(int ks, int B, int Z);
-int mdt_combine_reparam_bwd(const float* slab, int ks, const float* mulv, const float* eps, float* dmulv,
-                            void* dmulv16, float* dz, int B, int Z, const float* klw, const float* fbw,
-                            hipStream_t s);
-int mdt_job_wgrad(mdt::JobBlob* j, const void* G16, const void* X, int x_is_f32, mdt::ConvDesc d, float* out);
-int mdt_job_wgrad_adam(mdt::JobBlob* j, const void* G16, const void* X, int x_is_f32, mdt::ConvDesc d, float* P,
-                       float* Mo, float* Vo, void* w16, const float* adamc);
-int mdt_job_thin_conv(mdt::JobBlob* j, const void* X, int x_is_f32, const float* Wf, mdt::ConvDesc d,
-                      const float* bias, int relu, void* y16, const void* omask, float* colsum, const int* idx,
-                      void* st, const void* hp, int B, float* xb);
-int mdt_job_colsum(mdt::JobBlob* j, const void* G16, int M, int N, int rows_per, float* slab);
-int mdt_job_loss(mdt::JobBlob* j, const float* bce_part, int nb, const float* kld_part, int nk, void* st,
-                 const void* hp, int advance_cursor);
-int mdt_launch_jobs(const mdt::JobBlob* jobs, int n, hipStream_t s);
-int mdt_jobs_multi_bytes();
-int mdt_pack_jobs_multi(const mdt::JobBlob* jobs, int n, void* dst);
-int mdt_pack_jobs_multi_stamps(void* img, void* stamps);
-int mdt_launch_jobs_multi(const void* dev_pack, int grid, hipStream_t s);
-int mdt_f28_forward(const long long* p, int B, int M, unsigned stream, int train, hipStream_t s);
-int mdt_f28_forward_pair(const long long* p, const long long* pp, int B, int M, unsigned stream, hipStream_t s);
-int mdt_f28_backward(const long long* p, int M, const void* st, hipStream_t s);
-int mdt_f28_step(const long long* pf, const long long* pb, const long long* pp, int B, int M, unsigned stream,
-                 int pair, int delay_us, float* adamc, hipStream_t s);
-int mdt_f28_pair_words();
-int mdt_launch_job1(const mdt::JobBlob* j, hipStream_t s);
-}
+#include "../kernels/conv28_slots.h"
+#include "../kernels/conv_launch.h"
 
 namespace mdt {
 
@@ -520,157 +457,174 @@ void launch_jobs_multi(const at::Tensor& dev_pack, int64_t grid) {
   TORCH_CHECK(r == 0, "mdt: launch_jobs_multi failed (", r, ")");
 }
 
-// Fused 28x28 step launches (conv28_fused.hip). `t` lists the tensors in the
-// kernel's pointer-table order (None -> nullptr where optional); every tensor is
-// checked for device, contiguity, dtype and minimum size BEFORE the launch, so
-// a wrong buffer is a Python error rather than an out-of-bounds access. Not
-// checkable here: the gathered rows X[idx[cursor * B + n]] depend on device
-// state (the cursor) and on the index VALUES; the trainer guarantees them
-// (bind_train_data pads idx to whole batches of in-range rows, set_cursor
-// keeps cursor < nbatches), and the checks below pin the shapes they assume.
-namespace {
-struct Slot {
-  const char* name;
-  char dtype;        // 'f' f32, 'b' bf16, 'i' int32, 'u' uint8 (state blobs)
-  int64_t per_m;     // elements per sample (or fixed count when fixed)
-  bool fixed;        // per_m is a fixed element count
-  bool optional;
-};
+// Fused 28x28 step launches (conv28_fused.hip). A launch takes its tensors by
+// slot name (csrc/kernels/conv28_slots.h; None or absent -> nullptr where
+// optional); every tensor is checked for device, contiguity, dtype and minimum
+// size BEFORE the launch, so a wrong buffer is a Python error rather than an
+// out-of-bounds access. Not checkable here: the gathered rows
+// X[idx[cursor * B + n]] depend on device state (the cursor) and on the index
+// VALUES; the trainer guarantees them (bind_train_data pads idx to whole
+// batches of in-range rows, set_cursor keeps cursor < nbatches), and the
+// checks below pin the shapes they assume.
+//
+// f28_table resolves the names once: a trainer makes its tables when it plans a
+// batch size and launches with them; a launch given a dict makes its table on
+// the spot (as the eval pass does, whose data tensors change with the set).
+using F28Tensors = std::unordered_map<std::string, c10::optional<at::Tensor>>;
 
-std::vector<long long> f28_ptrs(const std::vector<c10::optional<at::Tensor>>& t, const std::vector<Slot>& slots,
-                                int64_t M, int dev) {
-  TORCH_CHECK(t.size() <= slots.size(), "f28: expected ", slots.size(), " tensors, got ", t.size());
-  for (size_t i = t.size(); i < slots.size(); ++i)  // trailing slots left out: must be optional (null)
-    TORCH_CHECK(slots[i].optional, "f28: expected ", slots.size(), " tensors, got ", t.size());
-  std::vector<long long> p(slots.size(), 0);
-  for (size_t i = 0; i < t.size(); ++i) {
-    const Slot& s = slots[i];
-    if (!t[i].has_value() || !t[i]->defined()) {
-      TORCH_CHECK(s.optional, "f28: tensor ", s.name, " is required");
+// One validated table of a launch over M samples of batches of B: the device
+// addresses in slot order, and the tensors they point into, kept alive.
+struct F28Table {
+  std::string kind;  // "forward", "backward" or "pair"
+  int64_t B, M;      // B: the forward's (idx holds whole batches of B); M elsewhere
+  bool train;        // forward: validated for a launch that stores the activations
+  int dev;
+  std::array<long long, f28::kNumFwdSlots> p;
+  F28Tensors keep;
+};
+static_assert(f28::kNumFwdSlots >= f28::kNumBwdSlots && f28::kNumFwdSlots >= f28::kNumPairSlots, "F28Table::p");
+using F28Arg = std::variant<std::shared_ptr<F28Table>, F28Tensors>;
+
+namespace {
+const at::Tensor* f28_find(const F28Tensors& t, const char* name) {
+  const auto it = t.find(name);
+  return it != t.end() && it->second.has_value() && it->second->defined() ? &*it->second : nullptr;
+}
+
+// r.p of `slots` from the tensors r.keep holds under their names, on the device of the first slot's.
+template <size_t N>
+void f28_resolve(F28Table& r, const f28::Slot (&slots)[N]) {
+  const F28Tensors& t = r.keep;
+  const at::Tensor* first = f28_find(t, slots[0].name);
+  TORCH_CHECK(first, "f28: tensor ", slots[0].name, " is required");
+  r.dev = (int)first->device().index();
+  size_t known = 0;
+  for (size_t i = 0; i < N; ++i) {
+    const f28::Slot& s = slots[i];
+    known += t.count(s.name);
+    const at::Tensor* x = f28_find(t, s.name);
+    if (!x) {
+      TORCH_CHECK(s.need == f28::kOptional || (s.need == f28::kTrainOnly && !r.train), "f28: tensor ", s.name,
+                  " is required");
       continue;
     }
-    const at::Tensor& x = *t[i];
-    TORCH_CHECK(x.is_cuda() && x.device().index() == dev && x.is_contiguous(), "f28: ", s.name,
-                " must be a contiguous tensor on cuda:", dev);
-    const auto st = x.scalar_type();
+    TORCH_CHECK(x->is_cuda() && x->device().index() == r.dev && x->is_contiguous(), "f28: ", s.name,
+                " must be a contiguous tensor on cuda:", r.dev);
+    const auto st = x->scalar_type();
     const bool ok = (s.dtype == 'f' && st == torch::kFloat32) || (s.dtype == 'b' && st == torch::kBFloat16) ||
                     (s.dtype == 'i' && st == torch::kInt32) || (s.dtype == 'u' && st == torch::kUInt8) ||
                     (s.dtype == 'l' && st == torch::kInt64);
     TORCH_CHECK(ok, "f28: ", s.name, " has dtype ", st);
-    const int64_t need = s.fixed ? s.per_m : s.per_m * M;
-    TORCH_CHECK(x.numel() >= need, "f28: ", s.name, " has ", x.numel(), " elements, needs ", need);
-    p[i] = (long long)(intptr_t)x.data_ptr();
+    int64_t unit = 1;
+    switch (s.unit) {
+      case f28::kFixed: break;
+      case f28::kPerSample: unit = r.M; break;
+      case f28::kPerBatchRow: unit = r.B; break;
+      case f28::kTrainState: unit = (int64_t)sizeof(TrainState); break;
+      case f28::kHParams: unit = (int64_t)sizeof(HParams); break;
+      case f28::kPairGranules: unit = r.M * mdt_f28_pair_words(); break;
+    }
+    TORCH_CHECK(x->numel() >= s.count * unit, "f28: ", s.name, " has ", x->numel(), " elements, needs ",
+                s.count * unit);
+    r.p[i] = (long long)(intptr_t)x->data_ptr();
   }
-  return p;
-}
-
-const std::vector<Slot>& f28_weight_slots() {
-  static const std::vector<Slot> w = {
-      {"W1f", 'f', 512, true, false},    {"b1", 'f', 32, true, false},    {"W2", 'b', 32768, true, false},
-      {"b2", 'f', 64, true, false},      {"Wh", 'b', 200704, true, false}, {"bh", 'f', 64, true, false},
-      {"Wd", 'b', 100352, true, false},  {"bd", 'f', 3136, true, false},  {"W3", 'b', 32768, true, false},
-      {"b3", 'f', 32, true, false},      {"W4f", 'f', 512, true, false},  {"b4", 'f', 1, true, false}};
-  return w;
+  if (known != t.size())  // a key that is no slot of this table
+    for (const auto& kv : t) {
+      bool is_slot = false;
+      for (const f28::Slot& s : slots) is_slot |= kv.first == s.name;
+      TORCH_CHECK(is_slot, "f28: unknown tensor name ", kv.first);
+    }
 }
 }  // namespace
 
-std::vector<Slot> f28_fwd_slots(int64_t B, bool train) {
-  std::vector<Slot> slots = f28_weight_slots();
-  const std::vector<Slot> rest = {
-      {"X", 'f', 784, true, false},        {"idx", 'i', B, true, false},
-      {"state", 'u', (int64_t)sizeof(TrainState), true, false}, {"hparams", 'u', (int64_t)sizeof(HParams), true, false},
-      {"xb", 'f', 784, false, !train},     {"a1", 'b', 6272, false, !train},  {"a2", 'b', 3136, false, !train},
-      {"mulv", 'f', 64, false, !train},    {"eps", 'f', 32, false, !train},   {"z16", 'b', 32, false, !train},
-      {"d0", 'b', 3136, false, !train},    {"d1", 'b', 6272, false, !train},  {"dlog", 'f', 784, false, !train},
-      {"recon", 'f', 784, false, true},    {"bce_part", 'f', 1, false, false}, {"kld_part", 'f', 1, false, false},
-      {"db4_part", 'f', 1, false, true},   {"stamps", 'l', 32, false, true},
-      {"xn", 'f', 784, false, true},       {"xtag", 'i', 1, false, true}};
-  slots.insert(slots.end(), rest.begin(), rest.end());
-  return slots;
+std::shared_ptr<F28Table> f28_table(const std::string& kind, const F28Tensors& t, int64_t B, int64_t M, bool train) {
+  TORCH_CHECK(M > 0 && M <= B, "f28: bad M ", M, " for B ", B);
+  const bool fwd = kind == "forward";
+  auto r = std::make_shared<F28Table>(F28Table{kind, fwd ? B : M, M, train || !fwd, 0, {}, t});
+  if (fwd) {
+    f28_resolve(*r, f28::kFwdSlots);
+    // X is [rows][784] and idx whole batches of B (cursor * B + n indexes it)
+    const int64_t nx = f28_find(t, "X")->numel(), ni = f28_find(t, "idx")->numel();
+    TORCH_CHECK(nx % 784 == 0, "f28: X must be [rows][784], has ", nx, " elements");
+    TORCH_CHECK(ni % B == 0, "f28: idx must hold whole batches of ", B, ", has ", ni);
+  } else if (kind == "backward") {
+    f28_resolve(*r, f28::kBwdSlots);
+  } else {
+    TORCH_CHECK(kind == "pair", "f28_table: kind is forward, backward or pair, got ", kind);
+    f28_resolve(*r, f28::kPairSlots);
+  }
+  return r;
 }
 
-std::vector<Slot> f28_bwd_slots() {
-  std::vector<Slot> slots = f28_weight_slots();
-  const std::vector<Slot> rest = {
-      {"hparams", 'u', (int64_t)sizeof(HParams), true, false},
-      {"mulv", 'f', 64, false, false},     {"eps", 'f', 32, false, false},     {"a1", 'b', 6272, false, false},
-      {"a2", 'b', 3136, false, false},     {"d0", 'b', 3136, false, false},    {"d1", 'b', 6272, false, false},
-      {"dlog", 'f', 784, false, false},    {"gd1", 'b', 6272, false, false},   {"gd0", 'b', 3136, false, false},
-      {"dbd_part", 'f', 3136, false, false}, {"dmulv", 'f', 64, false, false}, {"dmulv16", 'b', 64, false, false},
-      {"ga2", 'b', 3136, false, false},    {"ga1", 'b', 6272, false, false},   {"db3_part", 'f', 32, false, false},
-      {"db2_part", 'f', 128, false, false}, {"db1_part", 'f', 32, false, false},
-      {"stamps", 'l', 32, false, true}};
-  slots.insert(slots.end(), rest.begin(), rest.end());
-  return slots;
+namespace {
+// The launch's table of `kind`: the one given, if it was made for this launch, or one made from the dict given.
+std::shared_ptr<F28Table> f28_get(const F28Arg& a, const char* kind, int64_t B, int64_t M, bool train, int dev = -1) {
+  auto r = a.index() == 0 ? std::get<0>(a) : f28_table(kind, std::get<1>(a), B, M, train);
+  const int64_t b = std::strcmp(kind, "forward") == 0 ? B : M;
+  TORCH_CHECK(r && r->kind == kind && r->B == b && r->M == M && r->train == train, "f28: not a ", kind,
+              " table made for this launch's B, M and train");
+  TORCH_CHECK(dev < 0 || r->dev == dev, "f28: the ", kind, " table's tensors are on another device than the forward's");
+  return r;
 }
+bool f28_empty(const F28Arg& a) { return a.index() == 1 && std::get<1>(a).empty(); }
+}  // namespace
 
-// X is [rows][784] and idx whole batches of B (cursor * B + n indexes it).
-void f28_check_data(const std::vector<c10::optional<at::Tensor>>& t, int64_t B) {
-  TORCH_CHECK(t.size() > 13 && t[12].has_value() && t[13].has_value(), "f28: X and idx are required");
-  TORCH_CHECK(t[12]->numel() % 784 == 0, "f28: X must be [rows][784], has ", t[12]->numel(), " elements");
-  TORCH_CHECK(t[13]->numel() % B == 0, "f28: idx must hold whole batches of ", B, ", has ", t[13]->numel());
-}
-
-std::vector<long long> f28_pair_ptrs(const std::vector<c10::optional<at::Tensor>>& pair, int64_t M, int dev) {
-  const std::vector<Slot> ps = {{"xchg", 'l', 2 * (int64_t)mdt_f28_pair_words(), false, false},
-                                {"pairw", 'i', 1, false, false},
-                                {"err", 'i', 1, true, false}};
-  return f28_ptrs(pair, ps, M, dev);
+// The names of the four tables, in table order (the launch tables begin with the weights).
+std::map<std::string, std::vector<std::string>> f28_slot_names() {
+  const auto names = [](const auto& slots) {
+    std::vector<std::string> v;
+    for (const f28::Slot& s : slots) v.push_back(s.name);
+    return v;
+  };
+  return {{"weights", names(f28::kWeightSlots)}, {"forward", names(f28::kFwdSlots)},
+          {"backward", names(f28::kBwdSlots)}, {"pair", names(f28::kPairSlots)}};
 }
 
 // `pair` (eval only, train = false): the same three tensors as f28_step's;
 // the forward then runs two workgroups per sample (mdt_f28_forward_pair).
-void f28_forward(const std::vector<c10::optional<at::Tensor>>& t, int64_t B, int64_t M, int64_t stream, bool train,
-                 const std::vector<c10::optional<at::Tensor>>& pair) {
+void f28_forward(const F28Arg& t, int64_t B, int64_t M, int64_t stream, bool train, const F28Arg& pair) {
   TORCH_CHECK(M > 0 && M <= B, "f28_forward: bad M ", M, " for B ", B);
-  TORCH_CHECK(pair.empty() || !train, "f28_forward: the paired forward is eval-only");
-  f28_check_data(t, B);
-  const int dev = t[0].has_value() ? (int)t[0]->device().index() : 0;
-  const auto p = f28_ptrs(t, f28_fwd_slots(B, train), M, dev);
-  if (!pair.empty()) {
-    const auto pp = f28_pair_ptrs(pair, M, dev);
-    rc(mdt_f28_forward_pair(p.data(), pp.data(), (int)B, (int)M, (unsigned)stream, cur()), "f28_forward(pair)");
+  TORCH_CHECK(f28_empty(pair) || !train, "f28_forward: the paired forward is eval-only");
+  const auto f = f28_get(t, "forward", B, M, train);
+  if (!f28_empty(pair)) {
+    const auto pp = f28_get(pair, "pair", B, M, true, f->dev);
+    rc(mdt_f28_forward_pair(f->p.data(), pp->p.data(), (int)B, (int)M, (unsigned)stream, cur()), "f28_forward(pair)");
     return;
   }
-  rc(mdt_f28_forward(p.data(), (int)B, (int)M, (unsigned)stream, train ? 1 : 0, cur()), "f28_forward");
+  rc(mdt_f28_forward(f->p.data(), (int)B, (int)M, (unsigned)stream, train ? 1 : 0, cur()), "f28_forward");
 }
 
 // `state` (optional): the training state whose step is advanced AFTER this
 // launch (the fused step's loss job): the backward then uses the KL weight of
 // step + 1 recorded there; without it, HParams.kl_beta.
-void f28_backward(const std::vector<c10::optional<at::Tensor>>& t, int64_t M, const c10::optional<at::Tensor>& state) {
+void f28_backward(const F28Arg& t, int64_t M, const c10::optional<at::Tensor>& state) {
   TORCH_CHECK(M > 0, "f28_backward: bad M");
-  const int dev = t[0].has_value() ? (int)t[0]->device().index() : 0;
-  const auto p = f28_ptrs(t, f28_bwd_slots(), M, dev);
+  const auto b = f28_get(t, "backward", M, M, true);
   const void* st = nullptr;
   if (state.has_value() && state->defined()) {
     TORCH_CHECK(state->is_cuda() && state->numel() * state->element_size() >= (int64_t)sizeof(TrainState),
                 "f28_backward: state must be a TrialState device buffer");
     st = state->data_ptr();
   }
-  rc(mdt_f28_backward(p.data(), (int)M, st, cur()), "f28_backward");
+  rc(mdt_f28_backward(b->p.data(), (int)M, st, cur()), "f28_backward");
 }
 
 // Forward + backward of one training step in ONE launch (f28_step_k). With
-// `pair` (three tensors: exchange granules int64 [B][2][f28_pair_words()],
-// pairing words int32 [B], error word int32 [1], all zero-initialised) the
+// `pair` (exchange granules `xg` int64 [B][2][f28_pair_words()], pairing words
+// `pairw` int32 [B], error word `err` int32 [1], all zero-initialised) the
 // launch runs two workgroups per sample. `adamc` (optional, f32 [16]): receives
 // the Adam constants of the step that the following launch advances to, for
 // weight-gradient jobs that apply Adam in it (wgrad's `adam`).
-void f28_step(const std::vector<c10::optional<at::Tensor>>& tf, const std::vector<c10::optional<at::Tensor>>& tb,
-              int64_t B, int64_t M, int64_t stream, const std::vector<c10::optional<at::Tensor>>& pair,
+void f28_step(const F28Arg& tf, const F28Arg& tb, int64_t B, int64_t M, int64_t stream, const F28Arg& pair,
               int64_t pair_delay_us, const c10::optional<at::Tensor>& adamc) {
   TORCH_CHECK(M > 0 && M <= B, "f28_step: bad M ", M, " for B ", B);
-  f28_check_data(tf, B);
-  const int dev = tf[0].has_value() ? (int)tf[0]->device().index() : 0;
-  const auto pf = f28_ptrs(tf, f28_fwd_slots(B, true), M, dev);
-  const auto pb = f28_ptrs(tb, f28_bwd_slots(), M, dev);
-  std::vector<long long> pp;
-  if (!pair.empty()) pp = f28_pair_ptrs(pair, M, dev);
+  const auto f = f28_get(tf, "forward", B, M, true);
+  const auto b = f28_get(tb, "backward", B, M, true, f->dev);
+  const auto pp = f28_empty(pair) ? nullptr : f28_get(pair, "pair", B, M, true, f->dev);
   float* ac = nullptr;
-  if (adamc.has_value() && adamc->defined()) ac = adamc_ptr(*adamc, dev, "f28_step");
-  rc(mdt_f28_step(pf.data(), pb.data(), pp.empty() ? nullptr : pp.data(), (int)B, (int)M, (unsigned)stream,
-                  pp.empty() ? 0 : 1, (int)pair_delay_us, ac, cur()),
+  if (adamc.has_value() && adamc->defined()) ac = adamc_ptr(*adamc, f->dev, "f28_step");
+  rc(mdt_f28_step(f->p.data(), b->p.data(), pp ? pp->p.data() : nullptr, (int)B, (int)M, (unsigned)stream,
+                  pp ? 1 : 0, (int)pair_delay_us, ac, cur()),
      "f28_step");
 }
 
@@ -879,11 +833,15 @@ void bind_conv(pybind11::module& m) {
   m.def("pack_jobs_multi", &pack_jobs_multi, py::arg("jobs"), py::arg("stamps") = py::none());
   m.def("launch_jobs_multi", &launch_jobs_multi, py::arg("dev_pack"), py::arg("grid"));
   m.def("f28_forward", &f28_forward, py::arg("tensors"), py::arg("B"), py::arg("M"), py::arg("stream"),
-        py::arg("train"), py::arg("pair") = std::vector<c10::optional<at::Tensor>>{});
+        py::arg("train"), py::arg("pair") = F28Arg{F28Tensors{}});
   m.def("f28_backward", &f28_backward, py::arg("tensors"), py::arg("M"), py::arg("state") = py::none());
   m.def("f28_pair_words", &mdt_f28_pair_words);
+  m.def("f28_slot_names", &f28_slot_names);
+  py::class_<F28Table, std::shared_ptr<F28Table>>(m, "F28Table");
+  m.def("f28_table", &f28_table, py::arg("kind"), py::arg("tensors"), py::arg("B"), py::arg("M"),
+        py::arg("train") = true);
   m.def("f28_step", &f28_step, py::arg("fwd_tensors"), py::arg("bwd_tensors"), py::arg("B"), py::arg("M"),
-        py::arg("stream"), py::arg("pair") = std::vector<c10::optional<at::Tensor>>{},
+        py::arg("stream"), py::arg("pair") = F28Arg{F28Tensors{}},
         py::arg("pair_delay_us") = 0, py::arg("adamc") = py::none());
   m.def("igemm", &igemm, py::arg("mode"), py::arg("A"), py::arg("B16"), py::arg("desc"), py::arg("bias"),
         py::arg("relu"), py::arg("y16"), py::arg("y32"), py::arg("omask") = py::none(),

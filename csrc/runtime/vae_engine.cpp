@@ -11,11 +11,6 @@
 #include "../kernels/vae_latent.h"
 #include "../kernels/vae_mlp.h"
 
-extern "C" int mdt_adam_step(float* p, const float* g, float* m, float* v, long long n,
-                             const mdt::HParams* hp, mdt::TrainState* st, hipStream_t s);
-extern "C" int mdt_loss_finalize(const mdt::HParams* hp, mdt::TrainState* st,
-                                 const float* partials, int nkld, int nbce, hipStream_t s);
-
 namespace mdt {
 
 static inline int64_t align64(int64_t v) { return (v + 63) / 64 * 64; }

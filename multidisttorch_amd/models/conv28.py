@@ -85,7 +85,7 @@ class Fused28Step:
         return msgs
 
     def _plan28(self, M):
-        """Pointer tables, weight-gradient jobs and finalize units of the fused
+        """Tensor tables, weight-gradient jobs and finalize units of the fused
         28x28 step for a batch of M (built once per M and data binding; the
         tensors never move, so captured graphs stay valid)."""
         p = self._plans28.get(M)
@@ -95,7 +95,6 @@ class Fused28Step:
         f32 = dict(dtype=torch.float32, device=dev)
         X, idx = self._data[0], self._data[1]
         st = self.state
-        w = self._f28_weights()
         bce, kld, db4 = self._parts28()
         bias = self.f28_bias
         dbd = bias.narrow(0, 0, B * 3136)
@@ -104,10 +103,13 @@ class Fused28Step:
         db1 = bias.narrow(0, B * 3296, B * 32)
         a1, a2, d0, d1 = self.acts["enc1"], self.acts["enc2"], self.acts["dec_fc"], self.acts["dec1"]
         gd1, gd0, ga2, ga1 = self.gacts["dec1"], self.gacts["dec_fc"], self.gacts["enc2"], self.gacts["enc1"]
-        fwd = w + [X, idx, st.train_state, st.hparams, self.xb, a1, a2, self.mulv, self.eps, self.z16, d0, d1,
-                   self.dlog32, None, bce, kld, db4, self.f28_stamps[0], self.f28_xn, self.f28_xtag]
-        bwd = w + [st.hparams, self.mulv, self.eps, a1, a2, d0, d1, self.dlog32, gd1, gd0, dbd, self.dmulv,
-                   self.dmulv16, ga2, ga1, db3, db2, db1, self.f28_stamps[1]]
+        fwd = self._fwd_table28(X, idx, st.train_state, True, stamps=self.f28_stamps[0], prefetch=True)
+        bwd = dict(self._f28_weight_table(), hparams=st.hparams, mulv=self.mulv, eps=self.eps, a1=a1, a2=a2, d0=d0,
+                   d1=d1, dlog=self.dlog32, gd1=gd1, gd0=gd0, dbd_part=dbd, dmulv=self.dmulv, dmulv16=self.dmulv16,
+                   ga2=ga2, ga1=ga1, db3_part=db3, db2_part=db2, db1_part=db1, stamps=self.f28_stamps[1])
+        # the names are resolved and every tensor checked here, once: the step launches with these
+        launch = dict(fwd=C.f28_table("forward", fwd, B, M), bwd=C.f28_table("backward", bwd, B, M),
+                      pair=C.f28_table("pair", self._pair_table28(), B, M))
         # weight gradients: (G, X) per layer in the conv view (see _backward_hip)
         srcs = {"enc1": (ga1, self.xb), "enc2": (ga2, a1), "enc_head": (self.dmulv16, a2),
                 "dec_fc": (gd0, self.z16), "dec1": (d0, gd1), "dec2": (d1, self.dlog32)}
@@ -137,7 +139,7 @@ class Fused28Step:
         dec_pack, dec_grid = C.pack_jobs_multi(dec_jobs)
         enc_pack, enc_grid = C.pack_jobs_multi(enc_jobs)
         first_dec = self.spec.index(self.dec[0])
-        p = dict(fwd=fwd, bwd=bwd, jobs=jobs, jobs_pack=pack.to(dev), jobs_grid=grid, slabs=slabs,
+        p = dict(fwd=fwd, bwd=bwd, launch=launch, jobs=jobs, jobs_pack=pack.to(dev), jobs_grid=grid, slabs=slabs,
                  segs=C.make_grad_segs(segs, dev.index or 0), units=C.make_grad_units(units, dev.index or 0),
                  nunits=len(units), layer_units=layer_units, first_dec=first_dec,
                  dec_pack=dec_pack.to(dev), dec_grid=dec_grid, enc_pack=enc_pack.to(dev), enc_grid=enc_grid,
@@ -192,13 +194,13 @@ class Fused28Step:
         # step kernel get the buffer to hand the step's Adam constants over in
         epi = (self._epi_plan28(p) if self.f28_epi_adam and red is None and self.f28_merge
                and not self.f28_skip_adam else None)
+        t = p["launch"]
         if self.f28_merge:
-            C.f28_step(p["fwd"], p["bwd"], self.B, M, self.rng_stream,
-                       pair=[self.f28_xg, self.f28_pairw, self.f28_err] if self.f28_pair else [],
+            C.f28_step(t["fwd"], t["bwd"], self.B, M, self.rng_stream, pair=t["pair"] if self.f28_pair else {},
                        pair_delay_us=self.f28_pair_delay_us, **({"adamc": self.f28_adamc} if epi else {}))
         else:
-            C.f28_forward(p["fwd"], self.B, M, self.rng_stream, True)
-            C.f28_backward(p["bwd"], M, state=st.train_state)
+            C.f28_forward(t["fwd"], self.B, M, self.rng_stream, True)
+            C.f28_backward(t["bwd"], M, state=st.train_state)
         if red is None:
             q = epi or p
             C.launch_jobs_multi(q["jobs_pack"], q["jobs_grid"])
@@ -310,14 +312,31 @@ class Fused28Step:
         """f28_part as (bce, kld, dec2-bias partials)."""
         return [self.f28_part.narrow(0, i * self.B, self.B) for i in range(3)]
 
-    def _eval_fwd28(self, X, idx, want_recon):
-        """Pointer table of the fused forward over an eval set: the eval state,
-        no activation outputs (train = 0), the reconstruction when wanted."""
-        st = self.state
+    def _f28_weight_table(self):
+        """``_f28_weights`` under their slot names (``C.f28_slot_names()``)."""
+        return dict(zip(self.C.f28_slot_names()["weights"], self._f28_weights()))
+
+    def _fwd_table28(self, X, idx, state, acts, recon=None, stamps=None, prefetch=False):
+        """The fused forward's tensors by slot name, every slot of the table a
+        key (None = a null argument). ``state``: the train or the eval state;
+        ``acts``: the activation outputs a backward reads (a launch with
+        train = True needs them); ``recon``, ``stamps``: optional outputs;
+        ``prefetch``: the rows the previous step's finalize gathered."""
         bce, kld, db4 = self._parts28()
-        return self._f28_weights() + [X, idx, st.eval_state, st.hparams, self.xb, None, None, self.mulv, self.eps,
-                                      self.z16, None, None, None, self.recon if want_recon else None, bce, kld, db4,
-                                      None]
+        a1, a2, d0, d1 = ((self.acts[k] for k in ("enc1", "enc2", "dec_fc", "dec1")) if acts else (None,) * 4)
+        return dict(self._f28_weight_table(), X=X, idx=idx, state=state, hparams=self.state.hparams, xb=self.xb,
+                    a1=a1, a2=a2, mulv=self.mulv, eps=self.eps, z16=self.z16, d0=d0, d1=d1,
+                    dlog=self.dlog32 if acts else None, recon=recon, bce_part=bce, kld_part=kld, db4_part=db4,
+                    stamps=stamps, xn=self.f28_xn if prefetch else None, xtag=self.f28_xtag if prefetch else None)
+
+    def _pair_table28(self):
+        """The paired launches' exchange state by slot name."""
+        return dict(xg=self.f28_xg, pairw=self.f28_pairw, err=self.f28_err)
+
+    def _eval_fwd28(self, X, idx, want_recon):
+        """Tensor table of the fused forward over an eval set: the eval state,
+        no activation outputs (train = 0), the reconstruction when wanted."""
+        return self._fwd_table28(X, idx, self.state.eval_state, False, recon=self.recon if want_recon else None)
 
     def _eval_batch28(self, M, X, idx, want_recon):
         # the fused 28x28 forward in eval mode (f28_fwd_k, one workgroup
@@ -327,7 +346,7 @@ class Fused28Step:
         st = self.state
         bce, kld, _ = self._parts28()
         # paired (two workgroups per sample, 2M CUs) unless MDT_F28_EVAL_PAIR=0
-        pair = [self.f28_xg, self.f28_pairw, self.f28_err] if self.f28_pair and self._eval_pair else []
+        pair = self._pair_table28() if self.f28_pair and self._eval_pair else {}
         self.C.f28_forward(self._eval_fwd28(X, idx, want_recon), self.B, M, EVAL_STREAM + self.rng_stream,
                            False, pair=pair)
         self.C.loss_finalize2(bce, M, kld, M, st.eval_state, st.hparams, True, advance_step=True)

@@ -235,10 +235,7 @@ def test_eval_forward_recon_and_eval_pass_bitwise(M, native_ext):
     bufs["recon"] = tr.recon
     for t in bufs.values():
         _poison(t)
-    bce, kld, db4 = tr._parts28()
-    a1, a2, d0, d1 = tr.acts["enc1"], tr.acts["enc2"], tr.acts["dec_fc"], tr.acts["dec1"]
-    table = tr._f28_weights() + [X, idx, st.eval_state, st.hparams, tr.xb, a1, a2, tr.mulv, tr.eps, tr.z16, d0, d1,
-                                 tr.dlog32, tr.recon, bce, kld, db4]
+    table = tr._fwd_table28(X, idx, st.eval_state, True, recon=tr.recon)
     stream = EVAL_STREAM + tr.rng_stream
     tr.C.f28_forward(table, B, M, stream, True)
     torch.cuda.synchronize()
