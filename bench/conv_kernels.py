@@ -59,6 +59,7 @@ def main():
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
     from multidisttorch_amd.models.conv_vae import ConvVaeTrainer
+    from multidisttorch_amd.ops import conv_plans as plans
     from multidisttorch_amd.data.datasets import synthetic_images
 
     dev = torch.device("cuda")
@@ -93,9 +94,9 @@ def main():
         row = dict(i=i, op=name, tag=tag, us=round(us, 2), tflops=round(fl / us / 1e6, 1) if fl else None,
                    desc=desc)
         if name == "igemm":
-            row["plan"] = tr.C.igemm_plan(args[0], desc, kw.get("ws") is not None)
+            row["plan"] = plans.igemm_plan(args[0], desc, kw.get("ws") is not None)._asdict()
         if name == "wgrad":
-            row["plan"] = tr.C.wgrad_plan(desc)
+            row["plan"] = plans.wgrad_plan(desc)._asdict()
         out.append(row)
         total += us
         print(f"{i:3d} {name:14s} {tag:6s} {us:8.2f} us  {row['tflops'] or '':>7}  {desc or ''}  {row.get('plan', '')}",

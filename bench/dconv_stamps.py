@@ -27,6 +27,7 @@ def main():
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
+    from multidisttorch_amd.ops import conv_plans as plans
     from multidisttorch_amd.ops import native
 
     C = native.require()
@@ -35,7 +36,7 @@ def main():
     out = {}
     for mode, H, Cc, OH, CO in CASES:
         d = [N, H, H, Cc, OH, OH, CO, 4, 4, 2, 1]
-        info = C.igemm_plan(mode, d, False, fwd=True)
+        info = plans.igemm_plan(mode, d, False, fwd=True)
         if mode == 0:
             A = torch.randn(N * H * H * Cc, device=dev).bfloat16()
             B = torch.randn(CO * 16 * Cc, device=dev).bfloat16()
@@ -59,7 +60,7 @@ def main():
         e.record()
         torch.cuda.synchronize()
         us = s.elapsed_time(e) * 1e3 / a.reps
-        grid = info[7] * info[8]
+        grid = info.mtiles * info.ntiles
         st = torch.zeros(grid * 8, dtype=torch.int64, device=dev)
         C.dconv_stamps(st)
         run()
@@ -67,8 +68,8 @@ def main():
         C.dconv_stamps(None)
         t = st.view(grid, 8)[:, :4].cpu().numpy().astype(np.float64) * 0.01
         ph = {"load": t[:, 1] - t[:, 0], "kloop": t[:, 2] - t[:, 1], "epi": t[:, 3] - t[:, 2]}
-        flops = 2.0 * info[3] * info[4] * info[5] * info[6]
-        r = {"cfg": info[0], "grid": grid, "us": round(us, 2), "TF/s": round(flops / us * 1e-6, 1),
+        flops = 2.0 * info.classes * info.m * info.ncols * info.k
+        r = {"cfg": info.cfg, "grid": grid, "us": round(us, 2), "TF/s": round(flops / us * 1e-6, 1),
              "span_us": round(float(t[:, 3].max() - t[:, 0].min()), 2),
              "start_skew_us": round(float(t[:, 0].max() - t[:, 0].min()), 2)}
         for k, v in ph.items():
@@ -80,8 +81,8 @@ def main():
     for H, Cc, CO in ((64, 32, 64),):
         OH = H // 2
         d = [N, H, H, Cc, OH, OH, CO, 4, 4, 2, 1]
-        info = C.wgrad_plan(d)
-        if info[0] < 100:
+        info = plans.wgrad_plan(d)
+        if info.cfg < plans.WG_DIRECT_BASE:
             continue
         X = torch.randn(N * H * H * Cc, device=dev).bfloat16()
         G = torch.randn(N * OH * OH * CO, device=dev).bfloat16()
@@ -106,7 +107,7 @@ def main():
         t = st.view(grid, 8)[:, :5].cpu().numpy().astype(np.float64) * 0.01
         ph = {"first_stage": t[:, 1] - t[:, 0], "first_half": t[:, 2] - t[:, 1], "second_half": t[:, 3] - t[:, 2],
               "epi": t[:, 4] - t[:, 3]}
-        r = {"cfg": info[0], "grid": grid, "us": round(us, 2), "span_us": round(float(t[:, 4].max() - t[:, 0].min()), 2),
+        r = {"cfg": info.cfg, "grid": grid, "us": round(us, 2), "span_us": round(float(t[:, 4].max() - t[:, 0].min()), 2),
              "start_skew_us": round(float(t[:, 0].max() - t[:, 0].min()), 2)}
         for k, v in ph.items():
             r[k] = (round(float(np.median(v)), 2), round(float(v.max()), 2))

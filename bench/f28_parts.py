@@ -36,6 +36,7 @@ def main():
     a = ap.parse_args()
     from multidisttorch_amd.data.datasets import synthetic_images
     from multidisttorch_amd.models.conv_vae import ConvVaeTrainer
+    from multidisttorch_amd.ops import conv_plans as plans
 
     dev = torch.device("cuda", 0)
     B = 128
@@ -59,9 +60,9 @@ def main():
     for name, (G, Xw) in srcs.items():
         d = tr._desc(L[name], B)
         slab = p["slabs"][name + ".weight"][0]
-        plan = C.wgrad_plan(d)
+        plan = plans.wgrad_plan(d)
         out[f"wgrad_{name}"] = {"us": timeit(lambda G=G, Xw=Xw, d=d, slab=slab: C.wgrad(G, Xw, d, slab), a.reps),
-                                "plan": list(plan)}
+                                "plan": plan._asdict()}
     out["finalize"] = timeit(lambda: C.grad_finalize(tr.params, tr.grads, tr.exp_avg, tr.exp_avg_sq, tr.w16,
                                                      p["segs"], p["units"], p["nunits"], st.train_state,
                                                      st.hparams, False), a.reps)

@@ -31,6 +31,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
     a = ap.parse_args()
+    from multidisttorch_amd.ops import conv_plans as plans
     from multidisttorch_amd.ops import native
 
     C = native.require()
@@ -42,14 +43,14 @@ def main():
         d = [M, 1, 1, K, 1, 1, N, 1, 1, 1, 0]
         us = timeit(lambda: C.igemm(0, A, W.flatten(), d, None, False, y, None), a.reps)
         ref_us = timeit(lambda: torch.mm(A, W.t()), a.reps)
-        plan = C.igemm_plan(0, d, False)
+        plan = plans.igemm_plan(0, d, False)
         fl = 2.0 * M * N * K
         print(f"igemm M={M} N={N} K={K}: {us:8.1f} us {fl / us / 1e6:7.1f} TF/s   torch.mm {ref_us:8.1f} us "
               f"{fl / ref_us / 1e6:7.1f} TF/s  plan={plan}", flush=True)
         # weight gradient: dW[N][K] = G^T X with the reduction over M
         G = torch.randn(M, N, device=dev).to(torch.bfloat16)
-        info = C.wgrad_plan(d)
-        out = torch.empty(info[6] * N * K, device=dev)
+        info = plans.wgrad_plan(d)
+        out = torch.empty(info.nsplit * N * K, device=dev)
         us = timeit(lambda: C.wgrad(G, A, d, out), a.reps)
         ref_us = timeit(lambda: torch.mm(G.t(), A), a.reps)
         print(f"wgrad M={M} N={N} K={K}: {us:8.1f} us {fl / us / 1e6:7.1f} TF/s   torch.mm {ref_us:8.1f} us "

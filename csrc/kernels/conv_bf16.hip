@@ -9,6 +9,8 @@
 #include "adam_common.h"
 #include "conv_igemm.h"
 #include "conv_small.h"
+#include "comm_jobs.h"
+#include "conv_host.h"
 #include "conv_launch.h"
 
 namespace mdt {
@@ -199,13 +201,14 @@ __global__ void __launch_bounds__(256) combine_reparam_bwd_k(CombineReparamBwdAr
 using namespace mdt;
 
 // ------------------------------------------------------------ host API ----
-static inline int cdivh(long long a, long long b) { return (int)((a + b - 1) / b); }
+// An op with a JobBlob* first parameter is launched on `s` when that is null
+// and recorded into it (a job of a fused launch, conv_jobs.hip) when it is not.
 
 extern "C" {
 
 int mdt_reparam(const float* mulv, float* eps, void* z16, float* z32, int B, int Z, const void* st, const void* hp,
                 unsigned stream, float* kld_part, hipStream_t s) {
-  hipLaunchKernelGGL(reparam_k, dim3(cdivh((long long)B * Z, 256)), dim3(256), 0, s, mulv, eps,
+  hipLaunchKernelGGL(reparam_k, dim3(cdiv((long long)B * Z, 256)), dim3(256), 0, s, mulv, eps,
                      reinterpret_cast<__bf16*>(z16), z32, B, Z, reinterpret_cast<const TrainState*>(st),
                      reinterpret_cast<const HParams*>(hp), (uint32_t)stream, kld_part);
   return (int)hipGetLastError();
@@ -213,14 +216,14 @@ int mdt_reparam(const float* mulv, float* eps, void* z16, float* z32, int B, int
 
 int mdt_reparam_bwd(const float* dz, const float* mulv, const float* eps, float* dmulv, void* dmulv16, int B, int Z,
                     const float* klw, const float* fbw, hipStream_t s) {
-  hipLaunchKernelGGL(reparam_bwd_k, dim3(cdivh((long long)B * Z, 256)), dim3(256), 0, s, dz, mulv, eps, dmulv,
+  hipLaunchKernelGGL(reparam_bwd_k, dim3(cdiv((long long)B * Z, 256)), dim3(256), 0, s, dz, mulv, eps, dmulv,
                      reinterpret_cast<__bf16*>(dmulv16), B, Z, klw, fbw);
   return (int)hipGetLastError();
 }
 
 int mdt_gather_rows(const float* X, const int* idx, const void* st, int B, int M, int P, float* xb, hipStream_t s) {
   if (P % 4) return 1;
-  int blocks = cdivh((long long)M * (P / 4), 256);
+  int blocks = cdiv((long long)M * (P / 4), 256);
   if (blocks > 1024) blocks = 1024;
   hipLaunchKernelGGL(gather_rows_k, dim3(blocks), dim3(256), 0, s, X, idx, reinterpret_cast<const TrainState*>(st),
                      B, M, P, xb);
@@ -229,17 +232,19 @@ int mdt_gather_rows(const float* X, const int* idx, const void* st, int B, int M
 
 int mdt_bce_logits(const float* logits, const float* X, const int* rows, int B, int P, void* dlog16, float* recon,
                    float* part, float* gpart, hipStream_t s) {
-  hipLaunchKernelGGL(bce_logits_k, dim3(cdivh((long long)B * P, 256)), dim3(256), 0, s, logits, X, rows, B, P,
+  hipLaunchKernelGGL(bce_logits_k, dim3(cdiv((long long)B * P, 256)), dim3(256), 0, s, logits, X, rows, B, P,
                      reinterpret_cast<__bf16*>(dlog16), recon, part, gpart);
   return (int)hipGetLastError();
 }
 
-int mdt_conv_loss_finalize(const float* bce_part, int nb, const float* kld_part, int nk, void* st, const void* hp,
-                           int advance_cursor, hipStream_t s) {
+int mdt_conv_loss_finalize(JobBlob* j, const float* bce_part, int nb, const float* kld_part, int nk, void* st,
+                           const void* hp, int advance_cursor, hipStream_t s) {
   // advance_cursor: bit 0 = advance the batch cursor, bit 1 = also advance the step (loss_step_body)
+  const int step = (advance_cursor >> 1) & 1;
   const LossArgs la{bce_part, nb, kld_part, nk, reinterpret_cast<TrainState*>(st), reinterpret_cast<const HParams*>(hp),
                     advance_cursor & 1};
-  hipLaunchKernelGGL(conv_loss_finalize_k, dim3(1), dim3(256), 0, s, la, (advance_cursor >> 1) & 1);
+  if (j) return record_job(j, step ? kJobLossStep : kJobLoss, 1, la);
+  hipLaunchKernelGGL(conv_loss_finalize_k, dim3(1), dim3(256), 0, s, la, step);
   return (int)hipGetLastError();
 }
 
@@ -254,7 +259,7 @@ int mdt_adam_cast(float* P, const float* G, float* Mo, float* Vo, void* w16, con
   (void)segs;
   (void)nseg;
   if (total % 4 || ((uintptr_t)P | (uintptr_t)G | (uintptr_t)Mo | (uintptr_t)Vo) % 16 || (uintptr_t)w16 % 8) return 1;
-  int blocks = cdivh(total / 4, 256);
+  int blocks = cdiv(total / 4, 256);
   if (blocks > 1024) blocks = 1024;
   if (blocks < 1) blocks = 1;
   hipLaunchKernelGGL(adam_cast_k, dim3(blocks), dim3(256), 0, s, P, G, Mo, Vo, reinterpret_cast<__bf16*>(w16), total,
@@ -262,13 +267,17 @@ int mdt_adam_cast(float* P, const float* G, float* Mo, float* Vo, void* w16, con
   return (int)hipGetLastError();
 }
 
-int mdt_grad_finalize(float* P, float* G, float* Mo, float* Vo, void* w16, const void* segs, const void* units,
-                      int nunits, const void* st, const void* hp, int do_adam, const float* gX, const int* gidx,
-                      float* xn, unsigned* xtag, int gB, hipStream_t s) {
-  if (nunits <= 0) return 0;
+// nunits <= 0: launched, a no-op (0); recorded, an error (1) with `j` zeroed:
+// a job needs workgroups. The next-batch gather exists for the launch only.
+int mdt_grad_finalize(JobBlob* j, float* P, float* G, float* Mo, float* Vo, void* w16, const void* segs,
+                      const void* units, int nunits, const void* st, const void* hp, int do_adam, const float* gX,
+                      const int* gidx, float* xn, unsigned* xtag, int gB, hipStream_t s) {
+  if (j) memset(j, 0, sizeof(*j));
+  if (nunits <= 0) return j ? 1 : 0;
   const FinalizeArgs fa{P, G, Mo, Vo, reinterpret_cast<__bf16*>(w16), reinterpret_cast<const GradSeg*>(segs),
                         reinterpret_cast<const GradUnit*>(units), reinterpret_cast<const TrainState*>(st),
                         reinterpret_cast<const HParams*>(hp), do_adam};
+  if (j) return record_job(j, kJobFinalize, nunits, fa);
   const bool gather = xn && xtag && gX && gidx && gB > 0;
   const BatchGather bg{gX, gidx, reinterpret_cast<const TrainState*>(st), gather ? xn : nullptr, xtag, gB, nunits};
   const int grid = nunits + (gather ? gather_blocks(gB) : 0);
@@ -283,10 +292,29 @@ int mdt_grad_finalize(float* P, float* G, float* Mo, float* Vo, void* w16, const
   return (int)hipGetLastError();
 }
 
-int mdt_wtrans(const void* w16, void* w16t, const void* segs, const void* units, int nunits, hipStream_t s) {
-  if (nunits <= 0) return 0;
+// The fused xGMI all-reduce over finalize units (comm_jobs.h) runs inside fused
+// launches only: there is no stand-alone kernel, so this records and never launches.
+int mdt_job_comm(JobBlob* j, float* P, float* G, float* Mo, float* Vo, void* w16, const void* segs, const void* units,
+                 int nunits, const void* st, const void* hp, int do_adam, const void* ctx, int mode) {
+  memset(j, 0, sizeof(*j));
+  if (nunits <= 0 || !ctx || mode < kCommPush || mode > kCommPushReduce) return 1;
+  CommJobArgs a{};
+  a.fa = FinalizeArgs{P, G, Mo, Vo, reinterpret_cast<__bf16*>(w16), reinterpret_cast<const GradSeg*>(segs),
+                      reinterpret_cast<const GradUnit*>(units), reinterpret_cast<const TrainState*>(st),
+                      reinterpret_cast<const HParams*>(hp), do_adam};
+  a.ctx = reinterpret_cast<const CommCtx*>(ctx);
+  a.mode = mode;
+  return record_job(j, kJobComm, nunits, a);
+}
+
+// nunits <= 0: as for mdt_grad_finalize.
+int mdt_wtrans(JobBlob* j, const void* w16, void* w16t, const void* segs, const void* units, int nunits,
+               hipStream_t s) {
+  if (j) memset(j, 0, sizeof(*j));
+  if (nunits <= 0) return j ? 1 : 0;
   const WtransArgs wa{reinterpret_cast<const __bf16*>(w16), reinterpret_cast<__bf16*>(w16t),
                       reinterpret_cast<const GradSeg*>(segs), reinterpret_cast<const TrUnit*>(units)};
+  if (j) return record_job(j, kJobWtrans, nunits, wa);
   hipLaunchKernelGGL(wtrans_k, dim3(nunits), dim3(256), 0, s, wa);
   return (int)hipGetLastError();
 }

@@ -42,7 +42,7 @@ enum IgemmMode : int {
 // Launch plan of one forward-type GEMM (computed on the host, deterministic
 // in the geometry so the trainer can size the partial-sum buffers up front).
 struct FwdPlan {
-  int cfg;          // tile configuration index (see conv_igemm.hip)
+  int cfg;          // forward tile index (conv_tiles.h), or kFwdDirectBase + direct configuration
   int BM, BN;
   int classes;      // 1, or S*S parity classes (kModeTconv)
   int M;            // GEMM rows per class
@@ -56,13 +56,18 @@ struct FwdPlan {
 
 // Weight-gradient GEMM plan: dW[CO][KH*KW*C] = sum_m G[m][co] * im2col(X)[m][k'].
 struct WgradPlan {
-  int cfg;
+  int cfg;          // weight-gradient tile index, kWgDirectBase + DwL index, or kWgThinMfma
   int BM, BN;       // co tile x k' tile
   int M, K2;
   int cotiles, ktiles, mtiles;  // m-tiles of 64
   int nsplit, mt_per_split;
   int thin;
 };
+
+// Plan numbers (`cfg`) of the kernels that are no tile of the im2col families.
+constexpr int kFwdDirectBase = 100;  // + direct configuration (conv_direct.h)
+constexpr int kWgDirectBase = 100;   // + direct weight-gradient geometry (conv_dwgrad.h: DwL1, DwL2)
+constexpr int kWgThinMfma = 110;     // MFMA single-channel weight gradient (conv_thin_wg.h)
 
 // Gradient finalisation: per arena segment, g = sum over `nsplit` partial rows
 // of width `numel` (deterministic order), then either stored to the gradient
@@ -109,7 +114,8 @@ struct JobBlob {
   alignas(16) unsigned char args[kJobArgBytes];
 };
 
-// Job kind ids (see conv_jobs.hip for the instantiated combinations).
+// Job kind ids (see conv_jobs.hip for the instantiated combinations); the
+// encoders below the enum spell the "+ ..." of each family.
 enum JobKindBase : int {
   kJobIgemm = 1000,      // + mode*100 + cfg  (bf16, vector gathers)
   kJobWgrad = 2000,      // + cfg              (bf16, vector gathers)
@@ -127,6 +133,16 @@ enum JobKindBase : int {
   kJobComm = 5006,       // fused xGMI all-reduce + Adam over finalize units (comm_jobs.h)
   kJobDconv = 6000,      // + direct cfg       (patch-resident direct conv, conv_direct.h)
 };
+
+// The kinds of each family, encoded in one place: the builders, the J* wrappers
+// of conv_jobs.hip and the multi-job dispatch all go through these.
+constexpr int job_igemm(int mode, int cfg) { return kJobIgemm + mode * 100 + cfg; }
+constexpr int job_wgrad(int cfg) { return kJobWgrad + cfg; }
+constexpr int job_wgrad_thin(bool f32, int cfg) { return kJobWgradThin + (f32 ? 20 : 0) + cfg; }
+constexpr int job_thin_wgm(bool f32) { return kJobThinWgM + (f32 ? 1 : 0); }
+constexpr int job_wgrad_adam(int cfg) { return kJobWgradAdam + cfg; }
+constexpr int job_thin_conv(int co, bool f32) { return kJobThinConv + co + (f32 ? 100 : 0); }
+constexpr int job_dconv(int dc) { return kJobDconv + dc; }
 
 // Up to kMaxMultiJobs jobs of any kind of the multi-job kernel (jobs_multi_k).
 constexpr int kMaxMultiJobs = 8;

@@ -977,8 +977,8 @@ using W5 = TileCfg<32, 16, 2, 1>;
 
 }  // namespace tiles
 
-// Host-side builders shared by the stand-alone entry points (conv_igemm.hip)
-// and the job builders (conv_jobs.hip).
+// Host side: the planners (conv_plan.hip) and what the op builders of
+// conv_igemm.hip share.
 bool plan_fwd(int mode, const ConvDesc& d, bool allow_split, FwdPlan* p, bool allow_direct = true,
               bool fwd = false);
 int direct_cfg(int mode, const ConvDesc& d, bool fwd);

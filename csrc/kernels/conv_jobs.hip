@@ -29,6 +29,7 @@
 #include "conv_thin.h"
 #include "conv_thin_wg.h"
 #include "conv_launch.h"
+#include "conv_tiles.h"
 
 namespace mdt {
 using namespace tiles;
@@ -51,7 +52,7 @@ struct JNone {
 // forward-type GEMM (bf16, vector gathers); aux = {tiles per plane, k-splits}
 template <int MODE, int CFG, class TC>
 struct JIg {
-  static constexpr int ID = kJobIgemm + MODE * 100 + CFG, LDS = igemm_lds_bytes<TC>();
+  static constexpr int ID = job_igemm(MODE, CFG), LDS = igemm_lds_bytes<TC>();
   static __device__ __forceinline__ void run(const JobBlob& j, uint8_t* lds, int b) {
     const int ntb = j.aux[0], ks = j.aux[1];
     const int r = b / ntb, t = b - r * ntb;
@@ -62,7 +63,7 @@ struct JIg {
 
 template <int CFG, class TC>
 struct JWg {
-  static constexpr int ID = kJobWgrad + CFG, LDS = wgrad_lds_bytes<TC>();
+  static constexpr int ID = job_wgrad(CFG), LDS = wgrad_lds_bytes<TC>();
   static __device__ __forceinline__ void run(const JobBlob& j, uint8_t* lds, int b) {
     wgrad_body<__bf16, true, TC>(job_args<WgArgs>(j), lds, b, j.nblk);
   }
@@ -70,7 +71,7 @@ struct JWg {
 
 template <typename XT, int CFG, class TC>
 struct JWgThin {
-  static constexpr int ID = kJobWgradThin + (sizeof(XT) == 4 ? 20 : 0) + CFG, LDS = wgrad_lds_bytes<TC>();
+  static constexpr int ID = job_wgrad_thin(sizeof(XT) == 4, CFG), LDS = wgrad_lds_bytes<TC>();
   static __device__ __forceinline__ void run(const JobBlob& j, uint8_t* lds, int b) {
     wgrad_body<XT, false, TC>(job_args<WgArgs>(j), lds, b, j.nblk);
   }
@@ -78,7 +79,7 @@ struct JWgThin {
 
 template <typename XT>
 struct JThinWg {
-  static constexpr int ID = kJobThinWgM + (sizeof(XT) == 4 ? 1 : 0), LDS = thin_wgrad_mfma_lds_bytes();
+  static constexpr int ID = job_thin_wgm(sizeof(XT) == 4), LDS = thin_wgrad_mfma_lds_bytes();
   static __device__ __forceinline__ void run(const JobBlob& j, uint8_t* lds, int b) {
     thin_wgrad_mfma_body<XT>(job_args<WgArgs>(j), lds, b);
   }
@@ -86,7 +87,7 @@ struct JThinWg {
 
 template <int CO, typename TIN>
 struct JThinConv {
-  static constexpr int ID = kJobThinConv + CO + (sizeof(TIN) == 4 ? 100 : 0), LDS = thin_conv_lds_bytes<CO, 4>();
+  static constexpr int ID = job_thin_conv(CO, sizeof(TIN) == 4), LDS = thin_conv_lds_bytes<CO, 4>();
   static __device__ __forceinline__ void run(const JobBlob& j, uint8_t* lds, int b) {
     thin_conv_body<CO, 4, TIN>(job_args<ThinConvArgs>(j), lds, b);
   }
@@ -96,7 +97,7 @@ struct JThinConv {
 // shares a launch with the layer's weight gradient
 template <int CFG, class CF>
 struct JDc {
-  static constexpr int ID = kJobDconv + CFG, LDS = CF::LDS;
+  static constexpr int ID = job_dconv(CFG), LDS = CF::LDS;
   static __device__ __forceinline__ void run(const JobBlob& j, uint8_t* lds, int b) {
     dconv_body<CF>(job_args<DcArgs>(j), lds, xcd_remap(b, j.nblk));
   }
@@ -159,46 +160,58 @@ struct JobPackN {
   unsigned long long* stamps;  // profiling (null = off): per workgroup {start, end} s_memrealtime
 };
 
-constexpr int kMultiLds = cmax(cmax(cmax(wgrad_lds_bytes<W0>(), wgrad_lds_bytes<W1>()),
-                                    cmax(wgrad_lds_bytes<W3>(), wgrad_lds_bytes<W4>())),
-                               cmax(cmax(wgrad_lds_bytes<W2>(), wgrad_lds_bytes<W5>()),
-                                    cmax(cmax(JFinalize::LDS, JComm::LDS), JColsum::LDS + 64)));
+// the largest weight-gradient tile's LDS (every W tile can run in jobs_multi_k)
+constexpr int wgrad_lds_max() {
+  int m = 0;
+  for (int cfg = 0; cfg < kNumWgTiles; ++cfg)
+    visit_wg_tile(cfg, [&m](auto t) { m = cmax(m, wgrad_lds_bytes<typename decltype(t)::type>()); });
+  return m;
+}
+constexpr int kMultiLds = cmax(wgrad_lds_max(), cmax(cmax(JFinalize::LDS, JComm::LDS), JColsum::LDS + 64));
 
 template <int CFG, class TC>
 __device__ __forceinline__ bool run_wg_cfg(const JobBlob& j, uint8_t* lds, int b) {
-  if (j.kind == kJobWgrad + CFG) {
+  if (j.kind == job_wgrad(CFG)) {
     wgrad_body<__bf16, true, TC>(job_args<WgArgs>(j), lds, b, j.nblk);
     return true;
   }
-  if (j.kind == kJobWgradThin + CFG) {
+  if (j.kind == job_wgrad_thin(false, CFG)) {
     wgrad_body<__bf16, false, TC>(job_args<WgArgs>(j), lds, b, j.nblk);
     return true;
   }
-  if (j.kind == kJobWgradThin + 20 + CFG) {
+  if (j.kind == job_wgrad_thin(true, CFG)) {
     wgrad_body<float, false, TC>(job_args<WgArgs>(j), lds, b, j.nblk);
     return true;
   }
   return false;
 }
 
+// The kinds of jobs_multi_k besides the weight-gradient tiles (run_wg_cfg), as
+// X(kind, statement that runs it): the device switch and the host's
+// multi_kind_ok both expand this list, so neither can name a kind the other
+// lacks. The first two are the single-split Linear weight gradients of the
+// fused 28x28 step with Adam in their epilogue (conv_igemm_dev.h WgAdamArgs),
+// in the two tile shapes they plan to.
+#define MDT_WG_ADAM(TC) \
+  wgrad_body<__bf16, true, TC, true>(job_args<WgAdamArgs>(j).w, lds, lb, j.nblk, &job_args<WgAdamArgs>(j))
+#define MDT_MULTI_JOBS(X)                  \
+  X(job_wgrad_adam(0), MDT_WG_ADAM(W0))    \
+  X(job_wgrad_adam(1), MDT_WG_ADAM(W1))    \
+  X(kJobLossStep, JLossStep::run(j, lds, lb)) \
+  X(kJobLoss, JLoss::run(j, lds, lb))      \
+  X(kJobFinalize, JFinalize::run(j, lds, lb)) \
+  X(kJobComm, JComm::run(j, lds, lb))      \
+  X(kJobColsum, JColsum::run(j, lds, lb))
+
 __device__ __forceinline__ void run_multi_job(const JobBlob& j, uint8_t* lds, int lb) {
+  static_assert(kNumWgTiles == 6, "one run_wg_cfg per weight-gradient tile");
   if (run_wg_cfg<0, W0>(j, lds, lb) || run_wg_cfg<1, W1>(j, lds, lb) || run_wg_cfg<2, W2>(j, lds, lb) ||
       run_wg_cfg<3, W3>(j, lds, lb) || run_wg_cfg<4, W4>(j, lds, lb) || run_wg_cfg<5, W5>(j, lds, lb))
     return;
   switch (j.kind) {
-    // single-split Linear weight gradients of the fused 28x28 step with Adam in
-    // their epilogue (conv_igemm_dev.h WgAdamArgs): the two tile shapes they plan to
-    case kJobWgradAdam:
-      wgrad_body<__bf16, true, W0, true>(job_args<WgAdamArgs>(j).w, lds, lb, j.nblk, &job_args<WgAdamArgs>(j));
-      break;
-    case kJobWgradAdam + 1:
-      wgrad_body<__bf16, true, W1, true>(job_args<WgAdamArgs>(j).w, lds, lb, j.nblk, &job_args<WgAdamArgs>(j));
-      break;
-    case kJobLossStep: JLossStep::run(j, lds, lb); break;
-    case kJobLoss: JLoss::run(j, lds, lb); break;
-    case kJobFinalize: JFinalize::run(j, lds, lb); break;
-    case kJobComm: JComm::run(j, lds, lb); break;
-    case kJobColsum: JColsum::run(j, lds, lb); break;
+#define X(KIND, RUN) case KIND: RUN; break;
+    MDT_MULTI_JOBS(X)
+#undef X
     default: break;
   }
 }
@@ -239,11 +252,12 @@ __global__ void __launch_bounds__(256) jobs_multi_k(const JobPackN* __restrict__
 }
 
 __host__ inline bool multi_kind_ok(int k) {
-  if (k >= kJobWgrad && k <= kJobWgrad + 5) return true;
-  if (k >= kJobWgradThin && k <= kJobWgradThin + 5) return true;
-  if (k >= kJobWgradThin + 20 && k <= kJobWgradThin + 25) return true;
-  if (k == kJobWgradAdam || k == kJobWgradAdam + 1) return true;
-  return k == kJobLossStep || k == kJobLoss || k == kJobFinalize || k == kJobColsum || k == kJobComm;
+  for (int cfg = 0; cfg < kNumWgTiles; ++cfg)
+    if (k == job_wgrad(cfg) || k == job_wgrad_thin(false, cfg) || k == job_wgrad_thin(true, cfg)) return true;
+#define X(KIND, RUN) if (k == KIND) return true;
+  MDT_MULTI_JOBS(X)
+#undef X
+  return false;
 }
 
 template <class A, class B, class C>
@@ -373,194 +387,9 @@ const Combo kCombos[] = {
 #undef COMBO3
 #undef COMBO2
 
-inline int cdivj(long long a, long long b) { return (int)((a + b - 1) / b); }
-
-// workgroups of a direct-conv launch (conv_igemm.hip launch_dc)
-template <class CF>
-constexpr int dc_grid(int n) { return n * CF::RB * CF::NBB; }
-inline int direct_grid(int dc, int n) {
-  switch (dc) {
-    case 0: return dc_grid<DcS1>(n);
-    case 1: return dc_grid<DcS2>(n);
-    case 2: return dc_grid<DcT2>(n);
-    case 3: return dc_grid<DcT3>(n);
-    default: return 0;
-  }
-}
-
-template <class T>
-void put_args(JobBlob* j, const T& a) {
-  static_assert(sizeof(T) <= kJobArgBytes, "job arguments exceed the blob");
-  memset(j->args, 0, sizeof(j->args));
-  memcpy(j->args, &a, sizeof(T));
-}
-
 }  // namespace
 
 extern "C" {
-
-// Forward-type GEMM as a job (`g`); with split-K the combine pass is a second
-// job (`c`, kind kJobCombine, to run after `g`), else c->kind = 0. g->kind = 0
-// when the GEMM has no job form (f32 / per-element gathers, LDS-DMA path).
-int mdt_job_igemm(JobBlob* g, JobBlob* c, int mode, const void* A, int a_is_f32, const void* B16, ConvDesc d,
-                  const float* bias, int relu, void* y16, float* y32, const void* omask, float* colsum, float* ws,
-                  int skip_combine) {
-  IgArgs a;
-  FwdPlan q;
-  CombineArgs cb;
-  int nc = 0;
-  if (build_igemm(mode, A, B16, d, bias, relu, y16, y32, omask, colsum, ws, &a, &q, &cb, &nc)) return 1;
-  memset(g, 0, sizeof(*g));
-  memset(c, 0, sizeof(*c));
-  // direct-kernel geometries: the direct body as a job (backward-data calls;
-  // the 16x16 <-> 8x8 forward-only tiles have no job form)
-  const int dc = direct_cfg(mode, d, false);
-  if (dc >= 0) {
-    if (a_is_f32 || dc > 3) return 0;  // kind 0: the caller launches it alone
-    DcArgs da{};
-    da.A = reinterpret_cast<const __bf16*>(A);
-    da.B = reinterpret_cast<const __bf16*>(B16);
-    da.y16 = reinterpret_cast<__bf16*>(y16);
-    da.y32 = y32;
-    da.bias = bias;
-    da.omask = reinterpret_cast<const __bf16*>(omask);
-    da.colsum = colsum;
-    da.relu = relu;
-    da.nimg = d.N;
-    g->kind = kJobDconv + dc;
-    g->nblk = direct_grid(dc, d.N);
-    put_args(g, da);
-    return 0;
-  }
-  const bool ok = !a_is_f32 && !q.thin;
-  g->kind = ok ? kJobIgemm + mode * 100 + q.cfg : 0;
-  g->nblk = q.mtiles * q.ntiles * q.ksplit * q.classes;
-  g->aux[0] = q.mtiles * q.ntiles;
-  g->aux[1] = q.ksplit;
-  put_args(g, a);
-  if (nc > 0 && !skip_combine) {
-    c->kind = kJobCombine;
-    c->nblk = nc;
-    put_args(c, cb);
-  }
-  return 0;
-}
-
-int mdt_job_wgrad(JobBlob* j, const void* G16, const void* X, int x_is_f32, ConvDesc d, float* out) {
-  WgArgs a;
-  WgradPlan q;
-  if (build_wgrad(G16, X, d, out, &a, &q)) return 1;
-  memset(j, 0, sizeof(*j));
-  if (q.cfg == 110) j->kind = kJobThinWgM + (x_is_f32 ? 1 : 0);  // MFMA thin weight gradient
-  else if (q.cfg >= 100) {  // direct weight gradient (conv_dwgrad.h): 512-thread workgroups, its own launch
-    return 0;
-  }
-  else if (!q.thin) j->kind = x_is_f32 ? 0 : kJobWgrad + q.cfg;
-  else j->kind = kJobWgradThin + (x_is_f32 ? 20 : 0) + q.cfg;
-  j->nblk = q.cotiles * q.ktiles * q.nsplit;
-  put_args(j, a);
-  return 0;
-}
-
-// The weight gradient as a job that applies Adam in its epilogue and writes no
-// slab (jobs_multi_k only). P / Mo / Vo / w16 point at the weight's arena
-// segment; `adamc` at the AdamC an earlier launch stored (adam_consts_next).
-// Returns 1 when the layer has no such form: more than one m-split, a thin or
-// f32 input, a tile shape other than 64x64 / 64x32, rows not 16-B aligned.
-int mdt_job_wgrad_adam(JobBlob* j, const void* G16, const void* X, int x_is_f32, ConvDesc d, float* P, float* Mo,
-                       float* Vo, void* w16, const float* adamc) {
-  WgAdamArgs a{};
-  WgradPlan q;
-  if (!P || !Mo || !Vo || !w16 || !adamc || x_is_f32) return 1;
-  if (build_wgrad(G16, X, d, nullptr, &a.w, &q)) return 1;
-  if (q.thin || q.cfg < 0 || q.cfg > 1 || q.nsplit != 1 || (q.K2 & 3)) return 1;
-  if ((long long)d.CO * q.K2 >= (1ll << 28)) return 1;  // byte offsets in 32 bits
-  if (((uintptr_t)P | (uintptr_t)Mo | (uintptr_t)Vo) & 15 || ((uintptr_t)w16 & 7)) return 1;
-  a.P = P; a.Mo = Mo; a.Vo = Vo;
-  a.w16 = reinterpret_cast<__bf16*>(w16);
-  a.c = reinterpret_cast<const AdamC*>(adamc);
-  memset(j, 0, sizeof(*j));
-  j->kind = kJobWgradAdam + q.cfg;
-  j->nblk = q.cotiles * q.ktiles;
-  put_args(j, a);
-  return 0;
-}
-
-int mdt_job_thin_conv(JobBlob* j, const void* X, int x_is_f32, const float* Wf, ConvDesc d, const float* bias,
-                      int relu, void* y16, const void* omask, float* colsum, const int* idx, void* st,
-                      const void* hp, int B, float* xb) {
-  if (d.C != 1 || d.KH != 4 || d.KW != 4) return 1;
-  if ((idx || xb || hp) && (!st || !x_is_f32 || (d.H * d.W) % 4)) return 1;
-  memset(j, 0, sizeof(*j));
-  const bool ok = d.CO == 16 || d.CO == 32 || d.CO == 64;
-  j->kind = ok ? kJobThinConv + d.CO + (x_is_f32 ? 100 : 0) : 0;
-  j->nblk = cdivj((long long)d.N * d.OH * d.OW, 256);
-  const ThinConvArgs ta{X, Wf, d, bias, relu, reinterpret_cast<__bf16*>(y16), reinterpret_cast<const __bf16*>(omask),
-                        colsum, idx, reinterpret_cast<TrainState*>(st), reinterpret_cast<const HParams*>(hp), B, xb,
-                        j->nblk, thin_conv_mfma_ok(d, x_is_f32)};
-  put_args(j, ta);
-  return 0;
-}
-
-int mdt_job_colsum(JobBlob* j, const void* G16, int M, int N, int rows_per, float* slab) {
-  if (N % 8 || rows_per < 1) return 1;
-  memset(j, 0, sizeof(*j));
-  const int gx = cdivj(N / 8, 256);
-  j->kind = kJobColsum;
-  j->nblk = gx * cdivj(M, rows_per);
-  put_args(j, ColsumArgs{reinterpret_cast<const __bf16*>(G16), M, N, rows_per, gx, slab});
-  return 0;
-}
-
-int mdt_job_loss(JobBlob* j, const float* bce_part, int nb, const float* kld_part, int nk, void* st, const void* hp,
-                 int advance_cursor) {
-  memset(j, 0, sizeof(*j));
-  // bit 0: advance the batch cursor; bit 1: also advance the step (loss_step_body)
-  j->kind = (advance_cursor & 2) ? kJobLossStep : kJobLoss;
-  advance_cursor &= 1;
-  j->nblk = 1;
-  put_args(j, LossArgs{bce_part, nb, kld_part, nk, reinterpret_cast<TrainState*>(st),
-                       reinterpret_cast<const HParams*>(hp), advance_cursor});
-  return 0;
-}
-
-int mdt_job_finalize(JobBlob* j, float* P, float* G, float* Mo, float* Vo, void* w16, const void* segs,
-                     const void* units, int nunits, const void* st, const void* hp, int do_adam) {
-  memset(j, 0, sizeof(*j));
-  if (nunits <= 0) return 1;
-  j->kind = kJobFinalize;
-  j->nblk = nunits;
-  put_args(j, FinalizeArgs{P, G, Mo, Vo, reinterpret_cast<__bf16*>(w16), reinterpret_cast<const GradSeg*>(segs),
-                           reinterpret_cast<const GradUnit*>(units), reinterpret_cast<const TrainState*>(st),
-                           reinterpret_cast<const HParams*>(hp), do_adam});
-  return 0;
-}
-
-int mdt_job_comm(JobBlob* j, float* P, float* G, float* Mo, float* Vo, void* w16, const void* segs, const void* units,
-                 int nunits, const void* st, const void* hp, int do_adam, const void* ctx, int mode) {
-  memset(j, 0, sizeof(*j));
-  if (nunits <= 0 || !ctx || mode < kCommPush || mode > kCommPushReduce) return 1;
-  j->kind = kJobComm;
-  j->nblk = nunits;
-  CommJobArgs a{};
-  a.fa = FinalizeArgs{P, G, Mo, Vo, reinterpret_cast<__bf16*>(w16), reinterpret_cast<const GradSeg*>(segs),
-                      reinterpret_cast<const GradUnit*>(units), reinterpret_cast<const TrainState*>(st),
-                      reinterpret_cast<const HParams*>(hp), do_adam};
-  a.ctx = reinterpret_cast<const CommCtx*>(ctx);
-  a.mode = mode;
-  put_args(j, a);
-  return 0;
-}
-
-int mdt_job_wtrans(JobBlob* j, const void* w16, void* w16t, const void* segs, const void* units, int nunits) {
-  memset(j, 0, sizeof(*j));
-  if (nunits <= 0) return 1;
-  j->kind = kJobWtrans;
-  j->nblk = nunits;
-  put_args(j, WtransArgs{reinterpret_cast<const __bf16*>(w16), reinterpret_cast<__bf16*>(w16t),
-                         reinterpret_cast<const GradSeg*>(segs), reinterpret_cast<const TrUnit*>(units)});
-  return 0;
-}
 
 // Launch 2-3 jobs as ONE kernel. Returns 0 when launched, 1 when no fused
 // kernel exists for this combination of kinds (nothing launched: the caller

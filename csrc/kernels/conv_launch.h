@@ -4,26 +4,33 @@
 // a compile error (the names have C linkage: the linker would not see it).
 // Host-clean: g++ and hipcc include it. Every launcher returns 0 or an error
 // code; `st` / `hp` are a TrainState / HParams device buffer (vae_mlp.h).
+// An op whose first parameter is a JobBlob* has ONE builder for both forms: null launches its
+// stand-alone kernel, non-null records the same arguments as a job of a fused launch (conv_jobs.hip).
 #pragma once
 #include "conv_igemm.h"
 #include "vae_mlp.h"
 
 extern "C" {
 
+// conv_plan.hip: the planners (1: unsupported geometry)
+int mdt_igemm_plan(int mode, mdt::ConvDesc d, int allow_split, int fwd, mdt::FwdPlan* q);
+int mdt_wgrad_plan(mdt::ConvDesc d, mdt::WgradPlan* q);
+
 // conv_igemm.hip: implicit-GEMM convolutions and weight gradients
-int mdt_igemm_plan(int mode, mdt::ConvDesc d, int allow_split, int* info, int fwd);
-int mdt_wgrad_plan(mdt::ConvDesc d, int* info);
-int mdt_igemm(int mode, const void* A, int a_is_f32, const void* B16, mdt::ConvDesc d, const float* bias, int relu,
-              void* y16, float* y32, const void* omask, float* colsum, float* ws, int skip_combine, hipStream_t s,
-              const mdt::APro* pro, int fwd);
-int mdt_wgrad(const void* G16, const void* X, int x_is_f32, mdt::ConvDesc d, float* out, hipStream_t s);
+int mdt_igemm(mdt::JobBlob* g, mdt::JobBlob* c, int mode, const void* A, int a_is_f32, const void* B16,
+              mdt::ConvDesc d, const float* bias, int relu, void* y16, float* y32, const void* omask, float* colsum,
+              float* ws, int skip_combine, hipStream_t s, const mdt::APro* pro, int fwd);
+int mdt_wgrad(mdt::JobBlob* j, const void* G16, const void* X, int x_is_f32, mdt::ConvDesc d, float* out,
+              hipStream_t s);
+int mdt_job_wgrad_adam(mdt::JobBlob* j, const void* G16, const void* X, int x_is_f32, mdt::ConvDesc d, float* P,
+                       float* Mo, float* Vo, void* w16, const float* adamc);
 void mdt_dconv_stamps(unsigned long long* p);
-int mdt_colsum(const void* G16, int M, int N, int rows_per, float* slab, hipStream_t s);
+int mdt_colsum(mdt::JobBlob* j, const void* G16, int M, int N, int rows_per, float* slab, hipStream_t s);
 
 // conv_thin.hip: the single-channel edge layers
-int mdt_thin_conv(const void* X, int x_is_f32, const float* Wf, mdt::ConvDesc d, const float* bias, int relu, void* y16,
-                  const void* omask, float* colsum, const int* idx, void* st, const void* hp, int B, float* xb,
-                  hipStream_t s);
+int mdt_thin_conv(mdt::JobBlob* j, const void* X, int x_is_f32, const float* Wf, mdt::ConvDesc d, const float* bias,
+                  int relu, void* y16, const void* omask, float* colsum, const int* idx, void* st, const void* hp,
+                  int B, float* xb, hipStream_t s);
 int mdt_thin_blocks(int tconv, mdt::ConvDesc d);
 int mdt_thin_tconv(const void* G16, const float* Wf, mdt::ConvDesc d, const float* bias, float* y32, const float* X,
                    void* dlog16, float* recon, float* part, float* gpart, hipStream_t s);
@@ -36,15 +43,18 @@ int mdt_reparam_bwd(const float* dz, const float* mulv, const float* eps, float*
 int mdt_gather_rows(const float* X, const int* idx, const void* st, int B, int M, int P, float* xb, hipStream_t s);
 int mdt_bce_logits(const float* logits, const float* X, const int* rows, int B, int P, void* dlog16, float* recon,
                    float* part, float* gpart, hipStream_t s);
-int mdt_conv_loss_finalize(const float* bce_part, int nb, const float* kld_part, int nk, void* st, const void* hp,
-                           int advance_cursor, hipStream_t s);
+int mdt_conv_loss_finalize(mdt::JobBlob* j, const float* bce_part, int nb, const float* kld_part, int nk, void* st,
+                           const void* hp, int advance_cursor, hipStream_t s);
 int mdt_step_begin(void* st, const void* hp, hipStream_t s);
 int mdt_adam_cast(float* P, const float* G, float* Mo, float* Vo, void* w16, const void* segs, int nseg,
                   long long total, const void* st, const void* hp, int do_adam, hipStream_t s);
-int mdt_grad_finalize(float* P, float* G, float* Mo, float* Vo, void* w16, const void* segs, const void* units,
-                      int nunits, const void* st, const void* hp, int do_adam, const float* gX, const int* gidx,
-                      float* xn, unsigned* xtag, int gB, hipStream_t s);
-int mdt_wtrans(const void* w16, void* w16t, const void* segs, const void* units, int nunits, hipStream_t s);
+int mdt_grad_finalize(mdt::JobBlob* j, float* P, float* G, float* Mo, float* Vo, void* w16, const void* segs,
+                      const void* units, int nunits, const void* st, const void* hp, int do_adam, const float* gX,
+                      const int* gidx, float* xn, unsigned* xtag, int gB, hipStream_t s);
+int mdt_job_comm(mdt::JobBlob* j, float* P, float* G, float* Mo, float* Vo, void* w16, const void* segs,
+                 const void* units, int nunits, const void* st, const void* hp, int do_adam, const void* ctx, int mode);
+int mdt_wtrans(mdt::JobBlob* j, const void* w16, void* w16t, const void* segs, const void* units, int nunits,
+               hipStream_t s);
 int mdt_combine_reparam(const float* slab, int ks, const float* bias, float* mulv, float* eps, void* z16, float* z32,
                         int B, int Z, const void* st, const void* hp, unsigned stream, float* kld_part, hipStream_t s);
 int mdt_combine_reparam_bwd(const float* slab, int ks, const float* mulv, const float* eps, float* dmulv,
@@ -52,24 +62,7 @@ int mdt_combine_reparam_bwd(const float* slab, int ks, const float* mulv, const 
                             hipStream_t s);
 int mdt_combine_reparam_blocks(int ks, int B, int Z);
 
-// conv_jobs.hip: the same work recorded as jobs of a horizontally fused launch
-int mdt_job_igemm(mdt::JobBlob* g, mdt::JobBlob* c, int mode, const void* A, int a_is_f32, const void* B16,
-                  mdt::ConvDesc d, const float* bias, int relu, void* y16, float* y32, const void* omask,
-                  float* colsum, float* ws, int skip_combine);
-int mdt_job_wgrad(mdt::JobBlob* j, const void* G16, const void* X, int x_is_f32, mdt::ConvDesc d, float* out);
-int mdt_job_wgrad_adam(mdt::JobBlob* j, const void* G16, const void* X, int x_is_f32, mdt::ConvDesc d, float* P,
-                       float* Mo, float* Vo, void* w16, const float* adamc);
-int mdt_job_thin_conv(mdt::JobBlob* j, const void* X, int x_is_f32, const float* Wf, mdt::ConvDesc d,
-                      const float* bias, int relu, void* y16, const void* omask, float* colsum, const int* idx,
-                      void* st, const void* hp, int B, float* xb);
-int mdt_job_colsum(mdt::JobBlob* j, const void* G16, int M, int N, int rows_per, float* slab);
-int mdt_job_loss(mdt::JobBlob* j, const float* bce_part, int nb, const float* kld_part, int nk, void* st,
-                 const void* hp, int advance_cursor);
-int mdt_job_finalize(mdt::JobBlob* j, float* P, float* G, float* Mo, float* Vo, void* w16, const void* segs,
-                     const void* units, int nunits, const void* st, const void* hp, int do_adam);
-int mdt_job_comm(mdt::JobBlob* j, float* P, float* G, float* Mo, float* Vo, void* w16, const void* segs,
-                 const void* units, int nunits, const void* st, const void* hp, int do_adam, const void* ctx, int mode);
-int mdt_job_wtrans(mdt::JobBlob* j, const void* w16, void* w16t, const void* segs, const void* units, int nunits);
+// conv_jobs.hip: the horizontally fused launches over recorded jobs
 int mdt_launch_jobs(const mdt::JobBlob* jobs, int n, hipStream_t s);
 int mdt_launch_job1(const mdt::JobBlob* j, hipStream_t s);
 int mdt_jobs_multi_bytes();

@@ -17,6 +17,7 @@
 #include <stdlib.h>
 
 #include "conv_thin.h"
+#include "conv_host.h"
 #include "conv_launch.h"
 
 namespace mdt {
@@ -49,21 +50,26 @@ __global__ void __launch_bounds__(256) thin_tconv_k(ThinTconvArgs ta) {
 
 using namespace mdt;
 
-static inline int cdiv_t(long long a, long long b) { return (int)((a + b - 1) / b); }
-
 extern "C" {
 
-// conv with a single input channel; x_is_f32 selects f32 / bf16 input.
-int mdt_thin_conv(const void* X, int x_is_f32, const float* Wf, ConvDesc d, const float* bias, int relu, void* y16,
-                  const void* omask, float* colsum, const int* idx, void* st, const void* hp, int B, float* xb,
-                  hipStream_t s) {
+// conv with a single input channel (x_is_f32 selects f32 / bf16 input),
+// launched on `s` or, with `j`, recorded. A CO without a kernel (not 16, 32 or
+// 64) is error 2 when launched and a job of kind 0 ("no job form") when
+// recorded, as it always was.
+int mdt_thin_conv(JobBlob* j, const void* X, int x_is_f32, const float* Wf, ConvDesc d, const float* bias, int relu,
+                  void* y16, const void* omask, float* colsum, const int* idx, void* st, const void* hp, int B,
+                  float* xb, hipStream_t s) {
   if (d.C != 1 || d.KH != 4 || d.KW != 4) return 1;
   if ((idx || xb || hp) && (!st || !x_is_f32 || (d.H * d.W) % 4)) return 1;
-  const long long M = (long long)d.N * d.OH * d.OW;
-  dim3 grid(cdiv_t(M, 256)), blk(256);
+  const int nblk = cdiv((long long)d.N * d.OH * d.OW, 256);
+  dim3 grid(nblk), blk(256);
   const ThinConvArgs ta{X, Wf, d, bias, relu, reinterpret_cast<__bf16*>(y16), reinterpret_cast<const __bf16*>(omask),
                         colsum, idx, reinterpret_cast<TrainState*>(st), reinterpret_cast<const HParams*>(hp), B, xb,
-                        (int)grid.x, thin_conv_mfma_ok(d, x_is_f32)};
+                        nblk, thin_conv_mfma_ok(d, x_is_f32)};
+  if (j) {
+    const bool ok = d.CO == 16 || d.CO == 32 || d.CO == 64;
+    return record_job(j, ok ? job_thin_conv(d.CO, x_is_f32 != 0) : 0, nblk, ta);
+  }
 #define THIN(CO_)                                                                     \
   {                                                                                   \
     if (x_is_f32)                                                                     \
@@ -99,9 +105,9 @@ static bool thin_mfma_on() { return (thin_mfma_mask() & 2) != 0; }
 // blocks of the per-block partial outputs (colsum rows for thin_conv,
 // loss partials for thin_tconv)
 int mdt_thin_blocks(int tconv, ConvDesc d) {
-  if (!tconv) return cdiv_t((long long)d.N * d.OH * d.OW, 256);
+  if (!tconv) return cdiv((long long)d.N * d.OH * d.OW, 256);
   if (tconv_patch_ok(d)) return d.N * (d.OH / 4);
-  return cdiv_t((long long)d.N * (d.H / d.S) * (d.W / d.S), 256) * d.S * d.S;
+  return cdiv((long long)d.N * (d.H / d.S) * (d.W / d.S), 256) * d.S * d.S;
 }
 
 int mdt_thin_tconv(const void* G16, const float* Wf, ConvDesc d, const float* bias, float* y32, const float* X,
@@ -109,7 +115,7 @@ int mdt_thin_tconv(const void* G16, const float* Wf, ConvDesc d, const float* bi
   if (d.C != 1 || d.KH != 4 || d.KW != 4 || d.S != 2 || d.H % 2 || d.W % 2) return 1;
   if (X && !part) return 1;
   const long long Mc = (long long)d.N * (d.H / d.S) * (d.W / d.S);
-  const int gx = cdiv_t(Mc, 256);
+  const int gx = cdiv(Mc, 256);
   if (tconv_patch_ok(d)) {
     const ThinTconvArgs tp{reinterpret_cast<const __bf16*>(G16), Wf, d, bias, y32, X,
                            reinterpret_cast<__bf16*>(dlog16), recon, part, gpart, gx};

@@ -86,17 +86,52 @@ static int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 // fwd: the forward-pass call of this geometry (may select the direct kernel
 // where the backward-data call of the same geometry keeps the fusable one)
-std::vector<int64_t> igemm_plan(int64_t mode, const std::vector<int64_t>& dv, bool allow_split, bool fwd) {
-  int info[12];
-  rc(mdt_igemm_plan((int)mode, desc(dv), allow_split ? 1 : 0, info, fwd ? 1 : 0), "igemm_plan (unsupported geometry)");
-  return std::vector<int64_t>(info, info + 12);
+// A plan goes to Python as a struct sequence (a C-level named tuple) made from
+// ONE field list: read by name (ops/conv_plans.py), and still a sequence in the
+// order of the list.
+template <class P>
+struct PlanField {
+  const char* name;
+  int P::*member;
+};
+static const PlanField<FwdPlan> kFwdPlanFields[] = {
+    {"cfg", &FwdPlan::cfg},         {"bm", &FwdPlan::BM},         {"bn", &FwdPlan::BN},
+    {"classes", &FwdPlan::classes}, {"m", &FwdPlan::M},           {"ncols", &FwdPlan::Ncols},
+    {"k", &FwdPlan::K},             {"mtiles", &FwdPlan::mtiles}, {"ntiles", &FwdPlan::ntiles},
+    {"ktiles", &FwdPlan::ktiles},   {"ksplit", &FwdPlan::ksplit}, {"colsum_rows", &FwdPlan::colsum_rows}};
+static const PlanField<WgradPlan> kWgradPlanFields[] = {
+    {"cfg", &WgradPlan::cfg},         {"bm", &WgradPlan::BM},         {"bn", &WgradPlan::BN},
+    {"cotiles", &WgradPlan::cotiles}, {"ktiles", &WgradPlan::ktiles}, {"mtiles", &WgradPlan::mtiles},
+    {"nsplit", &WgradPlan::nsplit},   {"mt_per_split", &WgradPlan::mt_per_split}};
+
+template <class P, size_t N>
+static pybind11::object plan_tuple(const char* type, const PlanField<P> (&fields)[N], const P& q) {
+  static PyTypeObject* cls = [&] {  // made once per plan type, kept for the life of the process
+    static PyStructSequence_Field f[N + 1] = {};
+    for (size_t i = 0; i < N; ++i) f[i] = PyStructSequence_Field{fields[i].name, nullptr};
+    static PyStructSequence_Desc d{type, nullptr, f, (int)N};
+    return PyStructSequence_NewType(&d);
+  }();
+  TORCH_CHECK(cls != nullptr, "mdt: could not create the plan type ", type);
+  PyObject* t = PyStructSequence_New(cls);
+  for (size_t i = 0; i < N; ++i) PyStructSequence_SetItem(t, i, PyLong_FromLong(q.*fields[i].member));
+  return pybind11::reinterpret_steal<pybind11::object>(t);
 }
 
-std::vector<int64_t> wgrad_plan(const std::vector<int64_t>& dv) {
-  int info[8];
-  rc(mdt_wgrad_plan(desc(dv), info), "wgrad_plan (unsupported geometry)");
-  return std::vector<int64_t>(info, info + 8);
+pybind11::object igemm_plan(int64_t mode, const std::vector<int64_t>& dv, bool allow_split, bool fwd) {
+  FwdPlan q;
+  rc(mdt_igemm_plan((int)mode, desc(dv), allow_split ? 1 : 0, fwd ? 1 : 0, &q), "igemm_plan (unsupported geometry)");
+  return plan_tuple("_C.FwdPlan", kFwdPlanFields, q);
 }
+
+pybind11::object wgrad_plan(const std::vector<int64_t>& dv) {
+  WgradPlan q;
+  rc(mdt_wgrad_plan(desc(dv), &q), "wgrad_plan (unsupported geometry)");
+  return plan_tuple("_C.WgradPlan", kWgradPlanFields, q);
+}
+
+// A job's blob, or null for a launch: the first argument of every op builder.
+static JobBlob* blob(Job* job) { return job ? &job->main : nullptr; }
 
 // mode 0: conv (fwd / convT bwd-data), mode 1: parity-class transposed conv
 // (conv bwd-data / convT fwd; B16 = parity-ordered transposed weights).
@@ -111,10 +146,10 @@ void igemm(int64_t mode, const at::Tensor& A, const at::Tensor& B16, const std::
   const bool f32 = A.scalar_type() == torch::kFloat32;
   TORCH_CHECK(f32 || A.scalar_type() == torch::kBFloat16, "A must be f32 or bf16");
   check_bf16(B16, "B16");
-  int info[12];
-  rc(mdt_igemm_plan((int)mode, d, ws.has_value() && ws->defined() ? 1 : 0, info, fwd ? 1 : 0), "igemm_plan");
+  FwdPlan q;
+  rc(mdt_igemm_plan((int)mode, d, ws.has_value() && ws->defined() ? 1 : 0, fwd ? 1 : 0, &q), "igemm_plan");
   TORCH_CHECK(!(fwd && job), "igemm: fwd calls have no job form");
-  const int64_t classes = info[3], M = info[4], Ncols = info[5], K = info[6], ksplit = info[10];
+  const int64_t classes = q.classes, M = q.M, Ncols = q.Ncols, K = q.K, ksplit = q.ksplit;
   const int64_t rows_total = classes * M;
   const int64_t a_need = mode == kModeConv ? (int64_t)d.N * d.H * d.W * d.C : (int64_t)d.N * d.OH * d.OW * d.CO;
   TORCH_CHECK(A.numel() >= a_need, "A too small: ", A.numel(), " < ", a_need);
@@ -123,7 +158,7 @@ void igemm(int64_t mode, const at::Tensor& A, const at::Tensor& B16, const std::
   check_min(y32, rows_total * Ncols, "y32");
   check_min(omask, rows_total * Ncols, "omask");
   check_min(bias, Ncols, "bias");
-  check_min(colsum, (int64_t)info[11] * Ncols, "colsum");
+  check_min(colsum, (int64_t)q.colsum_rows * Ncols, "colsum");
   if (ksplit > 1) check_min(ws, ksplit * M * Ncols, "ws");
   APro pro{};
   if (a_slab.has_value() && a_slab->defined()) {
@@ -140,17 +175,11 @@ void igemm(int64_t mode, const at::Tensor& A, const at::Tensor& B16, const std::
     pro = APro{(const float*)a_slab->data_ptr(), (const float*)a_bias->data_ptr(),
                a_out16->data_ptr(), (int)a_ks, a_relu ? 1 : 0, (int)cin, (long long)a_need};
   }
-  if (job) {
-    rc(mdt_job_igemm(&job->main, &job->post, (int)mode, A.data_ptr(), f32, B16.data_ptr(), d,
-                     (const float*)opt_ptr(bias), relu, const_cast<void*>(opt_ptr(y16)), (float*)opt_ptr(y32),
-                     opt_ptr(omask), (float*)opt_ptr(colsum), (float*)opt_ptr(ws), combine ? 0 : 1),
-       "job_igemm");
-    return;
-  }
-  rc(mdt_igemm((int)mode, A.data_ptr(), f32, B16.data_ptr(), d, (const float*)opt_ptr(bias), relu,
-               const_cast<void*>(opt_ptr(y16)), (float*)opt_ptr(y32), opt_ptr(omask), (float*)opt_ptr(colsum),
-               (float*)opt_ptr(ws), combine ? 0 : 1, cur(), pro.slab ? &pro : nullptr, fwd ? 1 : 0),
-     "igemm");
+  rc(mdt_igemm(blob(job), job ? &job->post : nullptr, (int)mode, A.data_ptr(), f32, B16.data_ptr(), d,
+               (const float*)opt_ptr(bias), relu, const_cast<void*>(opt_ptr(y16)), (float*)opt_ptr(y32),
+               opt_ptr(omask), (float*)opt_ptr(colsum), (float*)opt_ptr(ws), combine ? 0 : 1, cur(),
+               pro.slab ? &pro : nullptr, fwd ? 1 : 0),
+     job ? "job_igemm" : "igemm");
 }
 
 // The 64-byte device buffer that hands one AdamC from the step kernel to the
@@ -172,17 +201,17 @@ void wgrad(const at::Tensor& G16, const at::Tensor& X, const std::vector<int64_t
   check_f32(out, "out");
   const bool f32 = X.scalar_type() == torch::kFloat32;
   TORCH_CHECK(X.is_cuda() && X.is_contiguous() && (f32 || X.scalar_type() == torch::kBFloat16), "X dtype/layout");
-  int info[8];
-  rc(mdt_wgrad_plan(d, info), "wgrad_plan");
+  WgradPlan q;
+  rc(mdt_wgrad_plan(d, &q), "wgrad_plan");
   TORCH_CHECK(G16.numel() >= (int64_t)d.N * d.OH * d.OW * d.CO, "G16 too small");
   TORCH_CHECK(X.numel() >= (int64_t)d.N * d.H * d.W * d.C, "X too small");
-  TORCH_CHECK(out.numel() >= (int64_t)info[6] * d.CO * d.KH * d.KW * d.C, "wgrad out too small for ", info[6],
+  TORCH_CHECK(out.numel() >= (int64_t)q.nsplit * d.CO * d.KH * d.KW * d.C, "wgrad out too small for ", q.nsplit,
               " partial slabs");
   if (!adam.empty()) {
     const int64_t numel = (int64_t)d.CO * d.KH * d.KW * d.C;
     TORCH_CHECK(job != nullptr && !f32, "wgrad: the Adam epilogue exists for bf16 weight-gradient jobs only");
     TORCH_CHECK(adam.size() == 4 && adamc.has_value() && adamc->defined(), "wgrad: adam = [P, m, v, w16] and adamc");
-    TORCH_CHECK(info[6] == 1, "wgrad: the Adam epilogue needs a single m-split plan, got ", info[6]);
+    TORCH_CHECK(q.nsplit == 1, "wgrad: the Adam epilogue needs a single m-split plan, got ", q.nsplit);
     TORCH_CHECK(adam_off >= 0 && adam_off % 4 == 0 && numel % 4 == 0, "wgrad: adam_off and the weight size must be multiples of 4");
     const int dev = G16.get_device();
     for (int i = 0; i < 4; ++i) {
@@ -197,11 +226,8 @@ void wgrad(const at::Tensor& G16, const at::Tensor& X, const std::vector<int64_t
        "job_wgrad_adam");
     return;
   }
-  if (job) {
-    rc(mdt_job_wgrad(&job->main, G16.data_ptr(), X.data_ptr(), f32, d, out.data_ptr<float>()), "job_wgrad");
-    return;
-  }
-  rc(mdt_wgrad(G16.data_ptr(), X.data_ptr(), f32, d, out.data_ptr<float>(), cur()), "wgrad");
+  rc(mdt_wgrad(blob(job), G16.data_ptr(), X.data_ptr(), f32, d, out.data_ptr<float>(), cur()),
+     job ? "job_wgrad" : "wgrad");
 }
 
 // Single-channel edge layers (conv_thin.hip): Wf is the f32 master weight
@@ -229,17 +255,10 @@ void thin_conv(const at::Tensor& X, const at::Tensor& Wf, const std::vector<int6
     TORCH_CHECK(X.dim() == 2 && X.size(1) == (int64_t)d.H * d.W, "thin_conv gather: X must be [rows, H*W]");
   }
   check_min(xb, (int64_t)d.N * d.H * d.W, "xb");
-  if (job) {
-    rc(mdt_job_thin_conv(&job->main, X.data_ptr(), f32, Wf.data_ptr<float>(), d, (const float*)opt_ptr(bias), relu,
-                         y16.data_ptr(), opt_ptr(omask), (float*)opt_ptr(colsum), (const int*)opt_ptr(idx),
-                         const_cast<void*>(opt_ptr(state)), opt_ptr(hparams), (int)B, (float*)opt_ptr(xb)),
-       "job_thin_conv");
-    return;
-  }
-  rc(mdt_thin_conv(X.data_ptr(), f32, Wf.data_ptr<float>(), d, (const float*)opt_ptr(bias), relu, y16.data_ptr(),
-                   opt_ptr(omask), (float*)opt_ptr(colsum), (const int*)opt_ptr(idx), const_cast<void*>(opt_ptr(state)),
-                   opt_ptr(hparams), (int)B, (float*)opt_ptr(xb), cur()),
-     "thin_conv");
+  rc(mdt_thin_conv(blob(job), X.data_ptr(), f32, Wf.data_ptr<float>(), d, (const float*)opt_ptr(bias), relu,
+                   y16.data_ptr(), opt_ptr(omask), (float*)opt_ptr(colsum), (const int*)opt_ptr(idx),
+                   const_cast<void*>(opt_ptr(state)), opt_ptr(hparams), (int)B, (float*)opt_ptr(xb), cur()),
+     job ? "job_thin_conv" : "thin_conv");
 }
 
 int64_t thin_blocks(bool tconv, const std::vector<int64_t>& dv) { return mdt_thin_blocks(tconv ? 1 : 0, desc(dv)); }
@@ -280,11 +299,8 @@ void colsum(const at::Tensor& G16, int64_t M, int64_t N, int64_t rows_per, at::T
   TORCH_CHECK(slab.get_device() == G16.get_device(), "colsum: slab is on another device than G16");
   TORCH_CHECK(G16.numel() >= M * N, "G16 too small");
   TORCH_CHECK(slab.numel() >= ((M + rows_per - 1) / rows_per) * N, "colsum slab too small");
-  if (job) {
-    rc(mdt_job_colsum(&job->main, G16.data_ptr(), (int)M, (int)N, (int)rows_per, slab.data_ptr<float>()), "job_colsum");
-    return;
-  }
-  rc(mdt_colsum(G16.data_ptr(), (int)M, (int)N, (int)rows_per, slab.data_ptr<float>(), cur()), "colsum");
+  rc(mdt_colsum(blob(job), G16.data_ptr(), (int)M, (int)N, (int)rows_per, slab.data_ptr<float>(), cur()),
+     job ? "job_colsum" : "colsum");
 }
 
 void reparam(const at::Tensor& mulv, at::Tensor eps, at::Tensor z16, const c10::optional<at::Tensor>& z32, int64_t B,
@@ -396,16 +412,10 @@ void loss_finalize2(const at::Tensor& bce_part, int64_t nb, const at::Tensor& kl
   check_buf(kld_part, torch::kFloat32, nk, bce_part, "loss_finalize2", "kld_part");
   check_blob(state, sizeof(TrainState), bce_part, "loss_finalize2", "state");
   check_blob(hparams, sizeof(HParams), bce_part, "loss_finalize2", "hparams");
-  if (job) {
-    rc(mdt_job_loss(&job->main, bce_part.data_ptr<float>(), (int)nb, kld_part.data_ptr<float>(), (int)nk,
-                    state.data_ptr(), hparams.data_ptr(), (advance_cursor ? 1 : 0) | (advance_step ? 2 : 0)),
-       "job_loss");
-    return;
-  }
-  rc(mdt_conv_loss_finalize(bce_part.data_ptr<float>(), (int)nb, kld_part.data_ptr<float>(), (int)nk,
+  rc(mdt_conv_loss_finalize(blob(job), bce_part.data_ptr<float>(), (int)nb, kld_part.data_ptr<float>(), (int)nk,
                             state.data_ptr(), hparams.data_ptr(), (advance_cursor ? 1 : 0) | (advance_step ? 2 : 0),
                             cur()),
-     "loss_finalize");
+     job ? "job_loss" : "loss_finalize");
 }
 
 // Launch recorded jobs as ONE fused kernel when an instantiation exists for
@@ -699,14 +709,7 @@ void grad_finalize(at::Tensor P, at::Tensor G, at::Tensor M, at::Tensor V, at::T
                    const at::Tensor& units, int64_t nunits, const at::Tensor& state, const at::Tensor& hparams,
                    bool do_adam, Job* job, const std::vector<at::Tensor>& gather, int64_t gather_B) {
   TORCH_CHECK(units.numel() >= nunits * (int64_t)sizeof(GradUnit), "grad_finalize: unit table too small");
-  if (job) {
-    TORCH_CHECK(gather.empty(), "grad_finalize: a finalize job takes no gather");
-    rc(mdt_job_finalize(&job->main, P.data_ptr<float>(), G.data_ptr<float>(), M.data_ptr<float>(),
-                        V.data_ptr<float>(), w16.data_ptr(), segs.data_ptr(), units.data_ptr(), (int)nunits,
-                        state.data_ptr(), hparams.data_ptr(), do_adam ? 1 : 0),
-       "job_finalize");
-    return;
-  }
+  TORCH_CHECK(!job || gather.empty(), "grad_finalize: a finalize job takes no gather");
   // optional next-batch gather (the fused 28x28 step): [X, idx, xn, xtag] and the batch size
   const float* gX = nullptr;
   const int* gidx = nullptr;
@@ -729,10 +732,10 @@ void grad_finalize(at::Tensor P, at::Tensor G, at::Tensor M, at::Tensor V, at::T
     xn = gather[2].data_ptr<float>();
     xtag = reinterpret_cast<unsigned*>(gather[3].data_ptr<int>());
   }
-  rc(mdt_grad_finalize(P.data_ptr<float>(), G.data_ptr<float>(), M.data_ptr<float>(), V.data_ptr<float>(),
+  rc(mdt_grad_finalize(blob(job), P.data_ptr<float>(), G.data_ptr<float>(), M.data_ptr<float>(), V.data_ptr<float>(),
                        w16.data_ptr(), segs.data_ptr(), units.data_ptr(), (int)nunits, state.data_ptr(),
                        hparams.data_ptr(), do_adam ? 1 : 0, gX, gidx, xn, xtag, (int)gather_B, cur()),
-     "grad_finalize");
+     job ? "job_finalize" : "grad_finalize");
 }
 
 // Record a fused all-reduce job (csrc/kernels/comm_jobs.h) over `nunits`
@@ -757,12 +760,8 @@ void wtrans(const at::Tensor& w16, at::Tensor w16t, const at::Tensor& segs, cons
   check_bf16(w16, "w16");
   check_bf16(w16t, "w16t");
   TORCH_CHECK(units.numel() >= nunits * (int64_t)sizeof(TrUnit), "wtrans: unit table too small");
-  if (job) {
-    rc(mdt_job_wtrans(&job->main, w16.data_ptr(), w16t.data_ptr(), segs.data_ptr(), units.data_ptr(), (int)nunits),
-       "job_wtrans");
-    return;
-  }
-  rc(mdt_wtrans(w16.data_ptr(), w16t.data_ptr(), segs.data_ptr(), units.data_ptr(), (int)nunits, cur()), "wtrans");
+  rc(mdt_wtrans(blob(job), w16.data_ptr(), w16t.data_ptr(), segs.data_ptr(), units.data_ptr(), (int)nunits, cur()),
+     job ? "job_wtrans" : "wtrans");
 }
 
 // Split-K combine of the encoder head fused with the reparameterisation, and
@@ -813,6 +812,10 @@ void combine_reparam_bwd(const at::Tensor& ws, int64_t ks, const at::Tensor& mul
 
 void bind_conv(pybind11::module& m) {
   namespace py = pybind11;
+  // the plan numbers that are no tile index (ops/conv_plans.py)
+  m.attr("FWD_DIRECT_BASE") = kFwdDirectBase;
+  m.attr("WG_DIRECT_BASE") = kWgDirectBase;
+  m.attr("WG_THIN_MFMA") = kWgThinMfma;
   m.def("igemm_plan", &igemm_plan, py::arg("mode"), py::arg("desc"), py::arg("allow_split"), py::arg("fwd") = false);
   m.def("dconv_stamps", [](const c10::optional<at::Tensor>& t) {
     // profiling: per-workgroup s_memrealtime stamps of the direct conv kernels ([grid][8] int64), None = off

@@ -10,6 +10,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from multidisttorch_amd.ops import conv_plans as plans
+
 pytestmark = pytest.mark.gpu
 
 
@@ -49,8 +51,8 @@ def test_direct_conv_matches_torch(case, epi, native_ext):
     g = torch.Generator(device="cpu").manual_seed(11 + mode + H)
     Wc = (torch.randn(CO, C, 4, 4, generator=g) * 0.05).bfloat16().float().to(dev)
     d = [N, H, H, C, OH, OH, CO, 4, 4, 2, 1]
-    info = C_.igemm_plan(mode, d, False, fwd=True)
-    assert info[0] >= 100, f"direct kernel not selected: {info}"
+    info = plans.igemm_plan(mode, d, False, fwd=True)
+    assert info.cfg >= plans.FWD_DIRECT_BASE, f"direct kernel not selected: {info}"
     if mode == 0:
         A = torch.randn(N, C, H, H, generator=g).bfloat16().float().to(dev)
         ref = F.conv2d(A, Wc, stride=2, padding=1)          # [N][CO][OH][OH]
@@ -74,7 +76,7 @@ def test_direct_conv_matches_torch(case, epi, native_ext):
     else:
         mask = (torch.rand(ref.shape, generator=g) > 0.4).bfloat16().to(dev)
         ref = ref * mask.float()
-        cs = torch.full((info[11] * ncols,), float("nan"), device=dev)
+        cs = torch.full((info.colsum_rows * ncols,), float("nan"), device=dev)
     C_.igemm(mode, A16, B16, d, bias, relu, y16, y32, mask, cs, fwd=True)
     torch.cuda.synchronize()
     r = ref.flatten()
@@ -83,7 +85,7 @@ def test_direct_conv_matches_torch(case, epi, native_ext):
     torch.testing.assert_close(y16.float(), r.bfloat16().float(), rtol=1e-2, atol=1e-2 * float(r.abs().max()))
     if cs is not None:
         assert torch.isfinite(cs).all()
-        tot = cs.view(info[11], ncols).double().sum(0)
+        tot = cs.view(info.colsum_rows, ncols).double().sum(0)
         torch.testing.assert_close(tot, ref.reshape(-1, ncols).double().sum(0), rtol=1e-5,
                                    atol=1e-5 * float(ref.abs().sum(0).max()))
 
@@ -134,8 +136,8 @@ def test_direct_wgrad_matches_torch(geom, native_ext, monkeypatch):
     dev = torch.device("cuda")
     for N in (8, 5):  # XCD-grouped and plain workgroup order
         d = [N, H, H, C, OH, OH, CO, 4, 4, 2, 1]
-        info = C_.wgrad_plan(d)
-        assert info[0] >= 100 and info[6] == N, info
+        info = plans.wgrad_plan(d)
+        assert info.cfg >= plans.WG_DIRECT_BASE and info.nsplit == N, info
         g = torch.Generator(device="cpu").manual_seed(3 + N + H)
         X = torch.randn(N, C, H, H, generator=g).bfloat16().float().to(dev)
         G = torch.randn(N, CO, OH, OH, generator=g).bfloat16().float().to(dev)
@@ -164,8 +166,8 @@ def test_thin_wgrad_mfma_matches_torch(f32_x, H, native_ext):
     N, W, CO = 3, 128, 32
     OH, OW = H // 2, W // 2
     d = [N, H, W, 1, OH, OW, CO, 4, 4, 2, 1]
-    info = C_.wgrad_plan(d)
-    assert info[0] == 110 and info[6] == N * OH // 4, info
+    info = plans.wgrad_plan(d)
+    assert info.cfg == plans.WG_THIN_MFMA and info.nsplit == N * OH // 4, info
     g = torch.Generator(device="cpu").manual_seed(11)
     X = torch.rand(N, 1, H, W, generator=g)
     if not f32_x:
@@ -174,7 +176,7 @@ def test_thin_wgrad_mfma_matches_torch(f32_x, H, native_ext):
     G = torch.randn(N, CO, OH, OW, generator=g).bfloat16().float()
     Xd = (X.flatten(1).contiguous() if f32_x else X.flatten(1).bfloat16().contiguous()).to(dev)
     G16 = G.permute(0, 2, 3, 1).contiguous().bfloat16().to(dev)
-    ns = info[6]
+    ns = info.nsplit
     out = torch.full((ns * CO * 16,), float("nan"), device=dev)
     C_.wgrad(G16, Xd, d, out)
     torch.cuda.synchronize()

@@ -16,6 +16,7 @@ import os
 import pytest
 import torch
 
+from multidisttorch_amd.ops import conv_plans as plans
 from tests import direct_cases as dc
 from tests import direct_checker as dk
 from tests import igemm_cases as ics
@@ -41,9 +42,9 @@ def _ok(tag, r):
 # ------------------------------------------------------------- direct conv ----
 def _plan(C, name, N, fwd=True):
     cfg, mode, H, Ci, CO, BM, BN, R, per_img = dc.DIRECT[name]
-    q = C.igemm_plan(mode, dc.desc(N, H, H, Ci, CO), False, fwd=fwd)
-    assert q[0] == cfg and (q[1], q[2]) == (BM, BN) and q[7] * q[8] == per_img * N, q
-    return dict(mode=mode, d=dc.desc(N, H, H, Ci, CO), n=q[3] * q[4] * q[5], ncols=q[5], K=q[6], rows=q[11])
+    q = plans.igemm_plan(mode, dc.desc(N, H, H, Ci, CO), False, fwd=fwd)
+    assert q.cfg == cfg and (q.bm, q.bn) == (BM, BN) and q.mtiles * q.ntiles == per_img * N, q
+    return dict(mode=mode, d=dc.desc(N, H, H, Ci, CO), n=q.classes * q.m * q.ncols, ncols=q.ncols, K=q.k, rows=q.colsum_rows)
 
 
 def _launch_direct(C, q, inp, ep, job=None, fwd=True):
@@ -120,9 +121,9 @@ def test_direct_job_form_is_bitwise(name, native_ext):
     q = _plan(C, name, 3, fwd=False)
     inp = dk.direct_inputs(name, 3, seed=5, device=DEV)
     wd, wsh = ics.desc(dc.JOB_WGRAD), dc.JOB_WGRAD
-    wq = C.wgrad_plan(wd)
-    assert wq[0] == 0
-    wn = wq[6] * wsh[3] * 16 * wsh[2]
+    wq = plans.wgrad_plan(wd)
+    assert wq.cfg == 0
+    wn = wq.nsplit * wsh[3] * 16 * wsh[2]
     wi = ck.wgrad_inputs(wsh, seed=9, device=DEV)
     wg_alone = ck.guarded(wn, device=DEV)
     C.wgrad(wi["G"], wi["X"], wd, wg_alone)
@@ -157,8 +158,8 @@ def test_direct_wgrad(name, native_ext, monkeypatch):
         monkeypatch.delenv("MDT_DWGRAD_L2", raising=False)
     for N, exact in [(n, False) for n in dc.DWGRAD_N] + [(3, True)]:
         d = dc.desc(N, H, H, Ci, CO)
-        q = C.wgrad_plan(d)
-        assert q[0] == cfg and q[6] == N, q
+        q = plans.wgrad_plan(d)
+        assert q.cfg == cfg and q.nsplit == N, q
         numel = CO * 16 * Ci
         inp = dk.dwgrad_inputs(name, N, seed=N, device=DEV, exact=exact)
         out = ck.guarded(N * numel, device=DEV)
@@ -183,9 +184,9 @@ def test_thin_wgrad(g, x_f32, native_ext):
     C = native_ext
     N, H, W = g
     d = dc.desc(N, H, W, 1, 32)
-    q = C.wgrad_plan(d)
-    assert q[0] == 110 and q[6] == N * (H // 2) // 4, q
-    ns = q[6]
+    q = plans.wgrad_plan(d)
+    assert q.cfg == plans.WG_THIN_MFMA and q.nsplit == N * (H // 2) // 4, q
+    ns = q.nsplit
     inp = dk.thin_inputs(32, g, x_f32, seed=3, device=DEV)
     out = ck.guarded(ns * 512, device=DEV)
     C.wgrad(inp["G"], inp["x"], d, out)
@@ -215,7 +216,7 @@ def test_thin_wgrad_job_form_is_bitwise(native_ext):
     g = (3, 16, 128)
     d = dc.desc(*g, 1, 32)
     inp = dk.thin_inputs(32, g, False, seed=6, device=DEV)
-    ns, M, nb = C.wgrad_plan(d)[6], g[0] * 8 * 64, dc.thin_conv_blocks(g)
+    ns, M, nb = plans.wgrad_plan(d).nsplit, g[0] * 8 * 64, dc.thin_conv_blocks(g)
 
     def run(jobs):
         wg, y16, cs = ck.guarded(ns * 512, device=DEV), ck.guarded(M * 32, ck.BF, DEV), ck.guarded(nb * 32, device=DEV)
@@ -271,7 +272,7 @@ THIN_CONV = dc.THIN_CONV_VALU + dc.THIN_CONV_MFMA
 def test_thin_conv(CO, g, x_f32, native_ext):
     C = native_ext
     assert C.thin_blocks(False, dc.desc(*g, 1, CO)) == dc.thin_conv_blocks(g)
-    assert (C.wgrad_plan(dc.desc(*g, 1, CO))[0] == 110) == dc.thin_mfma_geom(CO, g)   # the body the host picks
+    assert (plans.wgrad_plan(dc.desc(*g, 1, CO)).cfg == plans.WG_THIN_MFMA) == dc.thin_mfma_geom(CO, g)   # the body the host picks
     inp = dk.thin_inputs(CO, g, x_f32, seed=CO + g[1], device=DEV)
     for en, ep in dc.THIN_CONV_EPILOGUES.items():
         bias, mask = (inp["bias"] if ep["bias"] else None), (inp["mask"] if ep["mask"] else None)

@@ -10,6 +10,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from multidisttorch_amd.ops import conv_plans as plans
 from multidisttorch_amd.ops.conv_layout import conv_desc, nchw, nhwc, parity_transpose, torch_weight
 
 pytestmark = pytest.mark.gpu
@@ -111,8 +112,8 @@ def test_colsum_epilogue_and_fold(native_ext):
     C = native_ext
     N, H, Ci, CO = 4, 16, 64, 128
     d = conv_desc(N, H, H, Ci, CO, 4, 2, 1)
-    info = C.igemm_plan(1, d, False)
-    rows, ncols = info[11], info[5]
+    info = plans.igemm_plan(1, d, False)
+    rows, ncols = info.colsum_rows, info.ncols
     g = _bf(torch.randn(N, 8, 8, CO, device=DEV))
     w = _bf(torch.randn(CO, 4, 4, Ci, device=DEV) / 16)
     mask = _bf(torch.randn(N, H, H, Ci, device=DEV))
@@ -144,8 +145,8 @@ def test_wgrad_matches_autograd(shape, native_ext):
     OH = d[4]
     x = torch.rand(N, H, H, Ci, device=DEV) if xf32 else _bf(torch.randn(N, H, H, Ci, device=DEV))
     g = _bf(torch.randn(N, OH, OH, CO, device=DEV))
-    info = C.wgrad_plan(d)
-    ns = info[6]
+    info = plans.wgrad_plan(d)
+    ns = info.nsplit
     numel = CO * k * k * Ci
     out = torch.full((ns * numel,), float("nan"), device=DEV)
     C.wgrad(g, x, d, out)

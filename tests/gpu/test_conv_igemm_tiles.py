@@ -14,6 +14,7 @@ References are float64 matmuls on the device. No tolerance here is measured.
 import pytest
 import torch
 
+from multidisttorch_amd.ops import conv_plans as plans
 from tests import igemm_cases as cs
 from tests import igemm_checker as ck
 
@@ -27,14 +28,15 @@ EPILOGUES = {"bias_relu": dict(bias=True, relu=True), "mask_colsum": dict(mask=T
 
 
 def _plan(C, mode, shape, split=False):
-    q = C.igemm_plan(mode, cs.desc(shape), split)
-    return dict(cfg=q[0], BM=q[1], BN=q[2], classes=q[3], M=q[4], Ncols=q[5], K=q[6], mtiles=q[7], ntiles=q[8],
-                ktiles=q[9], ksplit=q[10], colsum_rows=q[11])
+    q = plans.igemm_plan(mode, cs.desc(shape), split)
+    return dict(cfg=q.cfg, BM=q.bm, BN=q.bn, classes=q.classes, M=q.m, Ncols=q.ncols, K=q.k, mtiles=q.mtiles,
+                ntiles=q.ntiles, ktiles=q.ktiles, ksplit=q.ksplit, colsum_rows=q.colsum_rows)
 
 
 def _wplan(C, shape):
-    q = C.wgrad_plan(cs.desc(shape))
-    return dict(cfg=q[0], BM=q[1], BN=q[2], cotiles=q[3], ktiles=q[4], mtiles=q[5], nsplit=q[6], mps=q[7])
+    q = plans.wgrad_plan(cs.desc(shape))
+    return dict(cfg=q.cfg, BM=q.bm, BN=q.bn, cotiles=q.cotiles, ktiles=q.ktiles, mtiles=q.mtiles, nsplit=q.nsplit,
+                mps=q.mt_per_split)
 
 
 def _launch_fwd(C, mode, shape, inp, q, ep, job=None):

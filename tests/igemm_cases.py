@@ -2,7 +2,7 @@
 ``igemm_fwd_k`` (F0..F7, conv and parity mode, vector and thin gathers) and of
 ``wgrad_k`` (W0..W5, vector and thin), each the smallest shape with the stated
 tails that the DEFAULT planner (``plan_fwd`` / ``plan_wgrad`` of
-csrc/kernels/conv_igemm.hip, no MDT_CONV_* knob set) sends to that tile.
+csrc/kernels/conv_plan.hip, no MDT_CONV_* knob set) sends to that tile.
 
 Shared by tests/unit/test_igemm_tile_cases.py (the real planner returns what
 the tables claim), tests/unit/test_igemm_checker.py (the checker at reduced-row

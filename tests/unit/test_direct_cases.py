@@ -9,6 +9,7 @@ import os
 
 import pytest
 
+from multidisttorch_amd.ops import conv_plans as plans
 from multidisttorch_amd.ops import native
 from tests import direct_cases as dc
 
@@ -29,23 +30,23 @@ def _C():
 def _mfma_geom(CO, g):
     """thin_mfma_geom as the host evaluates it (through the weight-gradient planner)."""
     N, H, W = g
-    return _C().wgrad_plan(dc.desc(N, H, W, 1, CO))[0] == 110
+    return plans.wgrad_plan(dc.desc(N, H, W, 1, CO)).cfg == plans.WG_THIN_MFMA
 
 
 @pytest.mark.parametrize("name", list(dc.DIRECT))
 @pytest.mark.parametrize("N", dc.DIRECT_N)
 def test_direct_case_plans_to_its_configuration(name, N):
     cfg, mode, H, C, CO, BM, BN, R, per_img = dc.DIRECT[name]
-    q = _C().igemm_plan(mode, dc.desc(N, H, H, C, CO), False, fwd=True)
-    assert q[0] == cfg >= 100 and (q[1], q[2]) == (BM, BN), q
-    assert q[3] == (1 if mode == dc.CONV else 4)
-    assert q[5] == (CO if mode == dc.CONV else C) and q[6] == (16 * C if mode == dc.CONV else 4 * CO)
-    assert q[7] * q[8] == per_img * N                      # the grid
+    q = plans.igemm_plan(mode, dc.desc(N, H, H, C, CO), False, fwd=True)
+    assert q.cfg == cfg >= plans.FWD_DIRECT_BASE and (q.bm, q.bn) == (BM, BN), q
+    assert q.classes == (1 if mode == dc.CONV else 4)
+    assert q.ncols == (CO if mode == dc.CONV else C) and q.k == (16 * C if mode == dc.CONV else 4 * CO)
+    assert q.mtiles * q.ntiles == per_img * N              # the grid
     out_rows = H // 2 if mode == dc.CONV else H
-    assert q[11] == N * out_rows // (R if mode == dc.CONV else 2 * R)   # column-sum rows
+    assert q.colsum_rows == N * out_rows // (R if mode == dc.CONV else 2 * R)   # column-sum rows
     # the backward-data call of the same geometry: the 16 <-> 8 tiles are forward only
-    back = _C().igemm_plan(mode, dc.desc(N, H, H, C, CO), False)[0]
-    assert back == (cfg if cfg < 104 else back) and (cfg < 104 or back < 100)
+    back = plans.igemm_plan(mode, dc.desc(N, H, H, C, CO), False).cfg
+    assert back == (cfg if cfg < 104 else back) and (cfg < 104 or back < plans.FWD_DIRECT_BASE)
 
 
 def test_direct_tables_cover_all_six_configurations_and_an_uneven_grid():
@@ -63,22 +64,22 @@ def test_direct_wgrad_case_plans_to_its_kernel(name, monkeypatch):
     else:
         monkeypatch.delenv("MDT_DWGRAD_L2", raising=False)
     for N in dc.DWGRAD_N:
-        q = _C().wgrad_plan(dc.desc(N, H, H, C, CO))
-        assert q[0] == cfg and q[6] == N and q[7] == 1, q
+        q = plans.wgrad_plan(dc.desc(N, H, H, C, CO))
+        assert q.cfg == cfg and q.nsplit == N and q.mt_per_split == 1, q
     assert {n % 8 == 0 for n in dc.DWGRAD_N} == {True, False}   # both workgroup orders
 
 
 def test_dwl2_needs_its_switch(monkeypatch):
     monkeypatch.delenv("MDT_DWGRAD_L2", raising=False)
     _, H, C, CO, _ = dc.DWGRAD["DwL2"]
-    assert _C().wgrad_plan(dc.desc(3, H, H, C, CO))[0] < 100
+    assert plans.wgrad_plan(dc.desc(3, H, H, C, CO)).cfg < plans.WG_DIRECT_BASE
 
 
 @pytest.mark.parametrize("g", dc.THIN_WGRAD)
 def test_thin_wgrad_case_plans_to_cfg_110(g):
     N, H, W = g
-    q = _C().wgrad_plan(dc.desc(N, H, W, 1, 32))
-    assert q[0] == 110 and q[6] == N * (H // 2) // 4, q
+    q = plans.wgrad_plan(dc.desc(N, H, W, 1, 32))
+    assert q.cfg == plans.WG_THIN_MFMA and q.nsplit == N * (H // 2) // 4, q
 
 
 def test_thin_conv_tables_reach_both_bodies_and_every_instantiation():
@@ -118,4 +119,4 @@ def test_thin_tconv_tables_reach_both_forms_and_every_instantiation():
 def test_job_weight_gradient_plans_to_w0():
     from tests import igemm_cases as ics
 
-    assert dc.JOB_WGRAD == ics.JOB_WGRAD and _C().wgrad_plan(ics.desc(dc.JOB_WGRAD))[0] == 0
+    assert dc.JOB_WGRAD == ics.JOB_WGRAD and plans.wgrad_plan(ics.desc(dc.JOB_WGRAD)).cfg == 0

@@ -5,6 +5,7 @@ tests/gpu/test_conv_igemm.py's own tables reaches more than F6, F7, W0, W1, W5
 -- the gap tests/gpu/test_conv_igemm_tiles.py closes."""
 import pytest
 
+from multidisttorch_amd.ops import conv_plans as plans
 from multidisttorch_amd.ops import native
 from tests import igemm_cases as cs
 
@@ -12,14 +13,15 @@ pytestmark = pytest.mark.skipif(not native.available(), reason="native extension
 
 
 def _fwd(mode, shape, split=False):
-    q = native.require().igemm_plan(mode, cs.desc(shape), split)
-    return dict(cfg=q[0], BM=q[1], BN=q[2], classes=q[3], M=q[4], Ncols=q[5], K=q[6], mtiles=q[7], ntiles=q[8],
-                ktiles=q[9], ksplit=q[10], colsum_rows=q[11])
+    q = plans.igemm_plan(mode, cs.desc(shape), split)
+    return dict(cfg=q.cfg, BM=q.bm, BN=q.bn, classes=q.classes, M=q.m, Ncols=q.ncols, K=q.k, mtiles=q.mtiles,
+                ntiles=q.ntiles, ktiles=q.ktiles, ksplit=q.ksplit, colsum_rows=q.colsum_rows)
 
 
 def _wg(shape):
-    q = native.require().wgrad_plan(cs.desc(shape))
-    return dict(cfg=q[0], BM=q[1], BN=q[2], cotiles=q[3], ktiles=q[4], mtiles=q[5], nsplit=q[6], mps=q[7])
+    q = plans.wgrad_plan(cs.desc(shape))
+    return dict(cfg=q.cfg, BM=q.bm, BN=q.bn, cotiles=q.cotiles, ktiles=q.ktiles, mtiles=q.mtiles, nsplit=q.nsplit,
+                mps=q.mt_per_split)
 
 
 @pytest.mark.parametrize("name,mode,thin,cfg,shape", cs.fwd_cases(), ids=[c[0] for c in cs.fwd_cases()])
@@ -82,9 +84,27 @@ def test_tables_reach_every_dispatchable_combination():
         got["wgrad_thin" if thin else "wgrad_vec"].add(_wg(sh)["cfg"])
     assert got == cs.DISPATCHABLE
     # no forward case is a direct-kernel geometry (cfg >= 100), forward or backward call
-    C = native.require()
     for _, mode, _, _, sh in cs.fwd_cases():
-        assert all(C.igemm_plan(mode, cs.desc(sh), False, f)[0] < 100 for f in (False, True))
+        assert all(plans.igemm_plan(mode, cs.desc(sh), False, f).cfg < plans.FWD_DIRECT_BASE for f in (False, True))
+
+
+def test_reported_tile_sizes_are_the_tables():
+    """Over all cases: every forward configuration 0..7 and weight-gradient
+    configuration 0..5 is planned, and the tile the extension reports for it is
+    the one FWD_TILES / WG_TILES states."""
+    fwd, wg = {}, {}
+    for _, mode, _, _, sh in cs.fwd_cases():
+        q = _fwd(mode, sh)
+        fwd.setdefault(q["cfg"], set()).add((q["BM"], q["BN"]))
+    for _, _, _, _, sh in cs.wgrad_cases():
+        q = _wg(sh)
+        wg.setdefault(q["cfg"], set()).add((q["BM"], q["BN"]))
+    assert fwd == {cfg: {tile} for cfg, tile in enumerate(cs.FWD_TILES)}
+    assert wg == {cfg: {tile} for cfg, tile in enumerate(cs.WG_TILES)}
+
+
+def test_special_plan_numbers():
+    assert (plans.FWD_DIRECT_BASE, plans.WG_DIRECT_BASE, plans.WG_THIN_MFMA) == (100, 100, 110)
 
 
 def test_job_table_cases_exist():

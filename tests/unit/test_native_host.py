@@ -5,6 +5,7 @@ build (scripts/sanitize_host.sh, MDT_NATIVE_SO=build/san/_C.so), where an
 out-of-bounds table access or signed overflow in a planner aborts the test."""
 import pytest
 
+from multidisttorch_amd.ops import conv_plans as plans
 from multidisttorch_amd.ops import native
 
 pytestmark = pytest.mark.skipif(not native.available(), reason="native extension not built")
@@ -31,16 +32,16 @@ def test_conv_planners_consistent(image, M):
         for mode in modes:
             for split in (False, True):
                 try:
-                    q = C.igemm_plan(mode, d, split)
+                    q = plans.igemm_plan(mode, d, split)
                 except RuntimeError as e:
                     assert "unsupported geometry" in str(e)
                     continue
-                classes, rows, ncols, K, ks, csrows = q[3], q[4], q[5], q[6], q[10], q[11]
+                classes, rows, ncols, K, ks, csrows = q.classes, q.m, q.ncols, q.k, q.ksplit, q.colsum_rows
                 assert classes >= 1 and rows >= 1 and ncols >= 1 and K >= 1
                 assert ks >= 1 and (split or ks == 1)
                 assert csrows >= 1
-        w = C.wgrad_plan(d)
-        assert w[6] >= 1  # m-splits (partial slabs)
+        w = plans.wgrad_plan(d)
+        assert w.nsplit >= 1  # m-splits (partial slabs)
         assert all(v >= 0 for v in w)
     for ks in (1, 2, 8):
         assert C.combine_reparam_blocks(ks, M, 32) >= 1
@@ -61,11 +62,12 @@ def test_thin_mfma_wgrad_plan(M):
         for l, d in _descs(image, M):
             if not (l.cin == 1 or l.cout == 1):
                 continue
-            info = C.wgrad_plan(d)
+            info = plans.wgrad_plan(d)
             if image == 128:
-                assert info[0] == 110 and info[6] == M * 64 // 4 and info[1] == 32 and info[2] == 16, info
+                assert (info.cfg == plans.WG_THIN_MFMA and info.nsplit == M * 64 // 4 and info.bm == 32
+                        and info.bn == 16), info
             else:
-                assert info[0] != 110, info
+                assert info.cfg != plans.WG_THIN_MFMA, info
 
 
 @pytest.mark.parametrize("args,msg", [
