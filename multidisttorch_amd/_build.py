@@ -105,6 +105,8 @@ FILE_FLAGS = {
     "conv_igemm.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
     "conv_jobs.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
     "conv_thin.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
+    # no packed-f32 VALU forms: every d2 and list value is scalar f32, as the exactness argument assumes
+    "prdc.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
 }
 
 

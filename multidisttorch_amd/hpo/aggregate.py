@@ -13,6 +13,7 @@ LATENT_KEYS = ("kl", "active_units", "mi", "tc", "dwkl")
 # per-trial scores of the after-trial passes (``TrialResult.extra``); None where the pass did not run
 SCORES = ("iw_nll", "latent", "test_loss_raw")
 SAMPLE_KEYS = ("mmd2", "nn_acc", "nn_acc_real", "nn_acc_fake")
+PRDC_KEYS = ("k", "precision", "recall", "density", "coverage")
 
 
 def trial_record(result, opts) -> dict:
@@ -21,13 +22,15 @@ def trial_record(result, opts) -> dict:
                **{k: result.extra.get(k) for k in SCORES})
     if opts.sample_report > 0:  # only then: the default record stays what it was
         rec["sample_report"] = result.extra.get("sample_report")
+    if opts.prdc_k > 0:
+        rec["prdc"] = result.extra.get("prdc")
     return rec
 
 
 def summarize(gathered, specs, opts) -> dict:
     """``gathered``: per rank, the list of its ``trial_record``s (None or empty: an idle rank)."""
     per_trial, wall, failed = {}, 0.0, set()
-    scores = {k: {} for k in SCORES + ("sample_report",)}
+    scores = {k: {} for k in SCORES + ("sample_report", "prdc")}
     for lst in gathered:
         for r in lst or []:
             gid = r["group_id"]
@@ -72,4 +75,8 @@ def summarize(gathered, specs, opts) -> dict:
         summary["sample_rows"] = opts.sample_report
         summary["sample_report"] = {str(g): {k: round(v[k], 6) for k in SAMPLE_KEYS} for g, v in sorted(samples.items())}
         summary["best_trial_by_mmd2"] = (min(samples, key=lambda g: (samples[g]["mmd2"], g)) if samples else None)
+    if opts.prdc_k > 0:
+        # fidelity (precision, density) and diversity (recall, coverage) on k-NN radii: four numbers, no single order
+        summary["prdc"] = {str(g): {k: (v[k] if k == "k" else round(v[k], 6)) for k in PRDC_KEYS}
+                           for g, v in sorted(scores["prdc"].items())}
     return summary

@@ -80,6 +80,7 @@ class RunOptions:
     au_threshold: float = 0.01             # a dimension is active when Var_x(mu_d) exceeds this
     binarize: str = "none"                 # none | threshold | static | dynamic (data/binarize.py); one value per run
     report_objective: tuple = ()           # objective.reported(specs): knobs whose values the metrics carry
+    prdc_k: int = 0                        # k > 0: the sample pass adds precision / recall / density / coverage on k-NN radii
     sample_report: int = 0                 # N > 0: kernel MMD + 1-NN test of N prior samples against N test rows
 
 
@@ -485,14 +486,22 @@ def _sample_eval(trainer, test, opts: RunOptions, group, metrics, device, tag: s
     t = time.perf_counter()
     idx = torch.arange(n, dtype=torch.int32, device=test.data.device)
     with trace.range("sample_eval"), trainer.averaged_weights():
-        r = trainer.evaluate_samples(test.data, idx, n)
+        k = int(opts.prdc_k)
+        # the default call stays the call it was
+        r = trainer.evaluate_samples(test.data, idx, n, prdc_k=k) if k > 0 else trainer.evaluate_samples(test.data, idx, n)
         if device.type == "cuda":
             torch.cuda.synchronize(device)
     r["sample_s"] = round(time.perf_counter() - t, 6)
     print0(tag + "====> Test set samples: MMD2 {:.6f} 1-NN acc {:.4f} (real {:.4f} gen {:.4f})".format(
         r["mmd2"], r["nn_acc"], r["nn_acc_real"], r["nn_acc_fake"]), process_group=group)
+    out = dict(sample_report=r)
+    if k > 0:
+        p = r["prdc"]
+        print0(tag + "====> Test set PRDC-{}: precision {:.4f} recall {:.4f} density {:.4f} coverage {:.4f}".format(
+            p["k"], p["precision"], p["recall"], p["density"], p["coverage"]), process_group=group)
+        out["prdc"] = p
     metrics.log(event="sample_eval", **r)
-    return dict(sample_report=r)
+    return out
 
 
 # after a trial's last epoch and its wall time, in this order: (label, enabled(spec, opts), pass -> part of extra)

@@ -29,6 +29,7 @@ import torch
 from ..ops import native
 from .iw import check_iw_args, default_chunk, iw_eps, iw_reduce
 from .latent import check_latent_args, latent_eps, latent_report
+from .prdc import COLS as PRDC_COLS, check_prdc_args, prdc_rows, prdc_stats
 from .sample_report import (COLS, bandwidths_of, check_sample_args, mean_pair_d2, sample_rows, sample_stats,
                             sample_z)
 
@@ -360,20 +361,27 @@ class SampleEval:
     SAMPLE_CHUNK_ELEMS = 1 << 24
 
     @torch.no_grad()
-    def evaluate_samples(self, X: torch.Tensor, idx: torch.Tensor, n_samples=None, return_rows: bool = False) -> dict:
+    def evaluate_samples(self, X: torch.Tensor, idx: torch.Tensor, n_samples=None, return_rows: bool = False,
+                         prdc_k: int = 0) -> dict:
         """The sample report of ``n_samples`` decoded prior draws (default: as
         many as rows) against rows ``X[idx]``: ``dict(rows_real, rows_fake,
         mean_pair_d2, bandwidths, mmd2, mmd2_per_bandwidth, nn_acc, nn_acc_real,
         nn_acc_fake, nn_dist_real_to_fake, nn_dist_fake_to_real, rf_asym)``;
         with ``return_rows`` also ``table`` (float32 ``[rows_real + rows_fake,
-        8]``), ``real`` and ``fake``. Training, eval, iw and latent state are not
-        touched; the result depends on (weights, data, seed, n) only."""
+        8]``), ``real`` and ``fake``. ``prdc_k > 0`` adds ``prdc = dict(k,
+        precision, recall, density, coverage)`` of the same rows on k-NN radii
+        (models/prdc.py; csrc/kernels/prdc.hip on the hip backend), with
+        ``return_rows`` also ``prdc_table`` (float32 ``[rows_real + rows_fake,
+        3]``). Training, eval, iw and latent state are not touched; the result
+        depends on (weights, data, seed, n) only."""
         idx = idx.to(device=self.device, dtype=torch.int64).contiguous()
         na = idx.numel()
         nb = na if n_samples is None else int(n_samples)
         real = X[idx].to(self.device, torch.float32).reshape(na, -1).contiguous()
         D = real.shape[1]
         check_sample_args(na, nb, D)
+        if prdc_k:
+            check_prdc_args(na, nb, D, prdc_k)
         m = mean_pair_d2(real)
         h = bandwidths_of(m)
         z = torch.from_numpy(sample_z(nb, self.Z, self.seed)).to(self.device)
@@ -389,4 +397,15 @@ class SampleEval:
         out = dict(rows_real=na, rows_fake=nb, mean_pair_d2=m, bandwidths=list(h), **sample_stats(table, na, nb))
         if return_rows:
             out.update(table=table, real=real, fake=fake)
+        if prdc_k:
+            k = int(prdc_k)
+            if self.backend != "hip":
+                ptable = prdc_rows(real, fake, k, chunk=max(1, self.SAMPLE_CHUNK_ELEMS // (max(na, nb) * D)))
+            else:
+                ws = torch.empty(C.prdc_ws_numel(na, nb, D, k), dtype=torch.float32, device=self.device)
+                ptable = torch.empty(na + nb, PRDC_COLS, dtype=torch.float32, device=self.device)
+                C.prdc_rows(real, fake, k, ws, ptable)
+            out["prdc"] = prdc_stats(ptable, na, nb, k)
+            if return_rows:
+                out["prdc_table"] = ptable
         return out

@@ -114,7 +114,16 @@ def parse_args(argv=None):
     parser.add_argument("--sample-report", type=int, default=0, metavar="N",
                         help="after each trial's last epoch: kernel MMD and 1-NN two-sample test between N decoded "
                              "prior samples and the first N test rows (a score of the samples themselves; 0 = off)")
+    parser.add_argument("--prdc", type=int, default=0, metavar="K",
+                        help="with --sample-report N: also precision, recall, density and coverage of the same rows "
+                             "on K-nearest-neighbour radii (fidelity against diversity; 1 <= K <= 8 < N; 0 = off)")
     args = parser.parse_args(argv)
+    if args.prdc != 0:
+        from multidisttorch_amd.models.prdc import check_prdc_args
+
+        if args.sample_report == 0:
+            raise ValueError("--prdc K scores the rows of the sample pass: it needs --sample-report N")
+        check_prdc_args(args.sample_report, args.sample_report, 1, args.prdc)
     if args.sample_report != 0:
         from multidisttorch_amd.models.sample_report import check_sample_args
 
@@ -164,7 +173,8 @@ def main(argv=None):
                       model=args.model, image_size=args.image_size, bucket_mb=parse_bucket_mb(args.bucket_mb),
                       profile=args.profile, iw_samples=max(0, args.iw_samples), latent_report=args.latent_report,
                       au_threshold=args.au_threshold, binarize=args.binarize,
-                      report_objective=objective.reported(specs), sample_report=args.sample_report)
+                      report_objective=objective.reported(specs), sample_report=args.sample_report,
+                      prdc_k=args.prdc)
     results = []
     member = False
     for group_id, group in enumerate(processes_groups):
