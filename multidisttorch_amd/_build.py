@@ -107,6 +107,8 @@ FILE_FLAGS = {
     "conv_thin.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
     # no packed-f32 VALU forms: every d2 and list value is scalar f32, as the exactness argument assumes
     "prdc.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+    # likewise: every filter tap is one scalar fmaf, in the order the error analysis assumes
+    "recon.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
 }
 
 

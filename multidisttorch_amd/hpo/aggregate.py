@@ -14,6 +14,7 @@ LATENT_KEYS = ("kl", "active_units", "mi", "tc", "dwkl")
 SCORES = ("iw_nll", "latent", "test_loss_raw")
 SAMPLE_KEYS = ("mmd2", "nn_acc", "nn_acc_real", "nn_acc_fake")
 PRDC_KEYS = ("k", "precision", "recall", "density", "coverage")
+RECON_KEYS = ("mse", "psnr", "ssim", "ssim_l", "ssim_cs", "ssim_min")
 
 
 def trial_record(result, opts) -> dict:
@@ -24,13 +25,15 @@ def trial_record(result, opts) -> dict:
         rec["sample_report"] = result.extra.get("sample_report")
     if opts.prdc_k > 0:
         rec["prdc"] = result.extra.get("prdc")
+    if opts.recon_report:
+        rec["recon_report"] = result.extra.get("recon_report")
     return rec
 
 
 def summarize(gathered, specs, opts) -> dict:
     """``gathered``: per rank, the list of its ``trial_record``s (None or empty: an idle rank)."""
     per_trial, wall, failed = {}, 0.0, set()
-    scores = {k: {} for k in SCORES + ("sample_report", "prdc")}
+    scores = {k: {} for k in SCORES + ("sample_report", "prdc", "recon_report")}
     for lst in gathered:
         for r in lst or []:
             gid = r["group_id"]
@@ -79,4 +82,9 @@ def summarize(gathered, specs, opts) -> dict:
         # fidelity (precision, density) and diversity (recall, coverage) on k-NN radii: four numbers, no single order
         summary["prdc"] = {str(g): {k: (v[k] if k == "k" else round(v[k], 6)) for k in PRDC_KEYS}
                            for g, v in sorted(scores["prdc"].items())}
+    if opts.recon_report:
+        # test images against their reconstructions from the posterior mean: the largest mean SSIM is the best trial
+        recon = scores["recon_report"]
+        summary["recon_report"] = {str(g): {k: round(v[k], 6) for k in RECON_KEYS} for g, v in sorted(recon.items())}
+        summary["best_trial_by_ssim"] = (min(recon, key=lambda g: (-recon[g]["ssim"], g)) if recon else None)
     return summary

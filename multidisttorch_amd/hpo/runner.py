@@ -36,6 +36,7 @@ from ..ckpt import checkpoint as ckpt
 from ..data.binarize import Binarizer, check_mode
 from ..data.datasets import ImageSet
 from ..data.sampler import reference_num_replicas, shard_indices
+from ..models.recon_report import check_recon_args
 from ..models.trainer_base import LOSS_HIST as LOSS_RING  # per-step loss ring of the trainers
 from ..obs.metrics import TrialMetrics
 from ..obs import trace
@@ -81,6 +82,7 @@ class RunOptions:
     binarize: str = "none"                 # none | threshold | static | dynamic (data/binarize.py); one value per run
     report_objective: tuple = ()           # objective.reported(specs): knobs whose values the metrics carry
     prdc_k: int = 0                        # k > 0: the sample pass adds precision / recall / density / coverage on k-NN radii
+    recon_report: bool = False             # MSE / PSNR / SSIM of the test reconstructions after the last epoch
     sample_report: int = 0                 # N > 0: kernel MMD + 1-NN test of N prior samples against N test rows
 
 
@@ -504,11 +506,39 @@ def _sample_eval(trainer, test, opts: RunOptions, group, metrics, device, tag: s
     return out
 
 
-# after a trial's last epoch and its wall time, in this order: (label, enabled(spec, opts), pass -> part of extra)
+def _check_recon_data(opts: RunOptions, test):
+    """At run start: ``--recon-report`` needs square one-channel images the SSIM window fits."""
+    if opts.recon_report:
+        check_recon_args(max(len(test), 1), int(test.data.shape[1]))
+
+
+def _recon_eval(trainer, test, opts: RunOptions, group, metrics, device, tag: str = "") -> dict:
+    """One reconstruction report pass over the test set after a trial's last epoch
+    (``--recon-report``, models/recon_report.py): per-pixel MSE, its PSNR and the
+    SSIM of every test image against its reconstruction from the posterior mean,
+    with the SSIM's luminance and contrast-structure factors -- the distortion
+    side of the ELBO, free of the trial's beta. Like its siblings it runs after
+    the trial's wall time was taken."""
+    t = time.perf_counter()
+    idx = torch.arange(len(test), dtype=torch.int32, device=test.data.device)
+    with trace.range("recon_eval"), trainer.averaged_weights():
+        r = trainer.evaluate_recon(test.data, idx)
+        if device.type == "cuda":
+            torch.cuda.synchronize(device)
+    r["recon_s"] = round(time.perf_counter() - t, 6)
+    print0(tag + "====> Test set recon: MSE {:.6f} PSNR {:.2f} SSIM {:.4f} (l {:.4f} cs {:.4f})".format(
+        r["mse"], r["psnr"], r["ssim"], r["ssim_l"], r["ssim_cs"]), process_group=group)
+    metrics.log(event="recon_eval", **r)
+    return dict(recon_report=r)
+
+
+# after a trial's last epoch and its wall time, in this order: (label, enabled(spec, opts), pass -> part of extra).
+# The passes that judge the posterior come first (the recon pass the last of them), the prior's sample pass last.
 _AFTER_TRIAL = (
     ("IW pass", lambda spec, opts: opts.iw_samples > 0, _iw_eval),
     ("latent pass", lambda spec, opts: opts.latent_report, _latent_eval),
     ("raw-weight test pass", lambda spec, opts: spec.ema_decay > 0, _raw_test_eval),
+    ("recon pass", lambda spec, opts: opts.recon_report, _recon_eval),
     ("sample pass", lambda spec, opts: opts.sample_report > 0, _sample_eval),
 )
 
@@ -539,6 +569,7 @@ def run_trial(spec: TrialSpec, group, opts: RunOptions, data=None, num_trials: O
 
     train, test = data if data is not None else _load_data(opts, device)
     _check_sample_rows(opts, test)
+    _check_recon_data(opts, test)
     if grank == 0:  # stderr: stdout stays byte-compatible with the reference
         print(f"[mdt] trial {spec.group_id}: train data {train.name} ({'synthetic' if train.synthetic else 'IDX'}, "
               f"{len(train)} x {tuple(train.shape)})", file=sys.stderr, flush=True)
@@ -722,6 +753,7 @@ def run_packed_trials(specs, group, opts: RunOptions, data=None, num_trials: Opt
     device = bound_device()
     train, test = data if data is not None else _load_data(opts, device)
     _check_sample_rows(opts, test)
+    _check_recon_data(opts, test)
     D = int(train.data.shape[1])
     shape = (1, opts.image_size, opts.image_size)
     tr = []

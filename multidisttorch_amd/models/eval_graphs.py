@@ -30,10 +30,11 @@ from ..ops import native
 from .iw import check_iw_args, default_chunk, iw_eps, iw_reduce
 from .latent import check_latent_args, latent_eps, latent_report
 from .prdc import COLS as PRDC_COLS, check_prdc_args, prdc_rows, prdc_stats
+from .recon_report import COLS as RECON_COLS, check_recon_args, recon_rows, recon_stats
 from .sample_report import (COLS, bandwidths_of, check_sample_args, mean_pair_d2, sample_rows, sample_stats,
                             sample_z)
 
-__all__ = ["GraphedEval", "GraphedIwEval", "GraphedLatentEval", "SampleEval", "capture_replayable"]
+__all__ = ["GraphedEval", "GraphedIwEval", "GraphedLatentEval", "SampleEval", "ReconEval", "capture_replayable"]
 
 
 def capture_replayable(snapshot_tensors, launch, repeats: int):
@@ -275,6 +276,30 @@ class GraphedLatentEval:
                                 torch.zeros(nd, dtype=torch.float64, device=self.device)])
         return self._lat_ws[1]
 
+    def _lat_encode(self, X: torch.Tensor, idx: torch.Tensor, n: int) -> torch.Tensor:
+        """hip backend: the encoder over rows ``X[idx[:n]]`` on the pass state, eager or graph-replayed
+        -> the pass buffer, whose rows ``[:n]`` now hold ``mu | lv``."""
+        B = self.B
+        nb = -(-n // B)
+        pad = nb * B - n
+        if pad:
+            idx = torch.cat([idx, idx[:1].expand(pad)])  # never read (rows >= M)
+        self._lat_prepare()
+        ibuf, rows = self._lat_bind(idx)
+        self._lat_begin(nb)
+        if self.use_graphs:
+            self._lat_batch(min(B, n), X, ibuf, rows)
+            full, tail = n // B, n % B
+            if n > B:
+                if full > 1:
+                    self._lat_graph(full - 1, B, X, ibuf, rows).replay()
+                if tail:
+                    self._lat_graph(1, tail, X, ibuf, rows).replay()
+        else:
+            for b in range(nb):
+                self._lat_batch(min(B, n - b * B), X, ibuf, rows)
+        return rows
+
     @torch.no_grad()
     def evaluate_latent(self, X: torch.Tensor, idx: torch.Tensor, au_threshold: float = 0.01,
                         return_rows: bool = False) -> dict:
@@ -300,23 +325,7 @@ class GraphedLatentEval:
             self._lat_last = dict(mulv=mulv.clone(), eps=eps, z=mu + eps * torch.exp(0.5 * lv))
             return out
         C = native.require()
-        pad = nb * B - n
-        if pad:
-            idx = torch.cat([idx, idx[:1].expand(pad)])  # never read (rows >= M)
-        self._lat_prepare()
-        ibuf, rows = self._lat_bind(idx)
-        self._lat_begin(nb)
-        if self.use_graphs:
-            self._lat_batch(min(B, n), X, ibuf, rows)
-            full, tail = n // B, n % B
-            if n > B:
-                if full > 1:
-                    self._lat_graph(full - 1, B, X, ibuf, rows).replay()
-                if tail:
-                    self._lat_graph(1, tail, X, ibuf, rows).replay()
-        else:
-            for b in range(nb):
-                self._lat_batch(min(B, n - b * B), X, ibuf, rows)
+        rows = self._lat_encode(X, idx, n)
         ws = self._lat_workspaces(n)
         st = self._lat_state()
         C.latent_report(rows, n, Z, st, self._lat_hparams(), ws)
@@ -408,4 +417,51 @@ class SampleEval:
             out["prdc"] = prdc_stats(ptable, na, nb, k)
             if return_rows:
                 out["prdc_table"] = ptable
+        return out
+
+
+class ReconEval:
+    """Mixin: ``evaluate_recon``, the reconstruction report (models/recon_report.py):
+    squared error and SSIM, with its luminance and contrast-structure factors, of
+    rows ``X[idx]`` against ``decode(mu(x))``. The posterior means come from the
+    latent pass's encoder loop (``GraphedLatentEval``: its index buffer, graphs and
+    device state), the reconstructions from the trainer's ``decode``; the per-row
+    table comes from the HIP kernels (csrc/kernels/recon.hip) on the hip backend
+    and from the oracle's torch ops otherwise.
+
+    Requires ``GraphedLatentEval``'s hooks and ``self.decode(z) -> [n, D]``; a
+    trainer with a ``channels`` attribute must have one channel."""
+
+    @torch.no_grad()
+    def evaluate_recon(self, X: torch.Tensor, idx: torch.Tensor, return_rows: bool = False) -> dict:
+        """The reconstruction report over rows ``X[idx]``: ``dict(rows, side, mse,
+        psnr, ssim, ssim_l, ssim_cs, ssim_min)``; with ``return_rows`` also
+        ``table`` (float32 ``[n, 4]``: se, ssim, l, cs), ``real``, ``recon`` and
+        ``mu``. Training, eval and iw state are not touched; the pass runs on the
+        latent pass's state, so ``latent_buffers()`` raises until the next
+        ``evaluate_latent``. The result depends on (weights, data) only."""
+        if getattr(self, "channels", 1) != 1:
+            raise ValueError(f"the reconstruction report supports one-channel images, got {self.channels} channels")
+        idx = idx.to(device=self.device, dtype=torch.int32).contiguous()
+        n = idx.numel()
+        X = X.contiguous()
+        real = X[idx.long()].to(self.device, torch.float32).reshape(n, -1).contiguous()
+        side = check_recon_args(n, real.shape[1])
+        B, Z = self.B, self.Z
+        if self.backend != "hip":
+            mu = torch.cat([self._lat_encode_torch(X[idx[b: b + B].long()])[0] for b in range(0, n, B)]).float()
+        else:
+            mu = self._lat_encode(X, idx, n)[:n, :Z].clone()
+        self._lat_last = None  # the pass buffer no longer holds an evaluate_latent pass
+        recon = self.decode(mu).to(torch.float32).reshape(n, -1).contiguous()
+        if self.backend != "hip":
+            table = recon_rows(real, recon, side)
+        else:
+            C = native.require()
+            ws = torch.empty(C.recon_ws_numel(n, side), dtype=torch.float32, device=self.device)
+            table = torch.empty(n, RECON_COLS, dtype=torch.float32, device=self.device)
+            C.recon_rows(real, recon, side, ws, table)
+        out = recon_stats(table, side)
+        if return_rows:
+            out.update(table=table, real=real, recon=recon, mu=mu)
         return out

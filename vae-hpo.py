@@ -25,7 +25,9 @@ split of the KL term over the test set), ``--binarize {none,threshold,static,dyn
 (train and test on {0, 1} pixels, redrawn on the device: the test loss and the
 IW bound are then negative log-likelihoods of binarized data; one value per run),
 ``--sample-report N`` (after each trial's last epoch: the kernel MMD and the 1-NN
-two-sample test between N decoded prior samples and N test rows).
+two-sample test between N decoded prior samples and N test rows),
+``--recon-report`` (after each trial's last epoch: MSE, PSNR and SSIM of the test
+images against their reconstructions).
 """
 
 import argparse
@@ -117,6 +119,10 @@ def parse_args(argv=None):
     parser.add_argument("--prdc", type=int, default=0, metavar="K",
                         help="with --sample-report N: also precision, recall, density and coverage of the same rows "
                              "on K-nearest-neighbour radii (fidelity against diversity; 1 <= K <= 8 < N; 0 = off)")
+    parser.add_argument("--recon-report", action="store_true",
+                        help="after each trial's last epoch: per-pixel MSE, PSNR and SSIM (with its luminance and "
+                             "contrast-structure factors) of the test images against their reconstructions from the "
+                             "posterior mean: the distortion, comparable across a --beta sweep")
     args = parser.parse_args(argv)
     if args.prdc != 0:
         from multidisttorch_amd.models.prdc import check_prdc_args
@@ -174,7 +180,7 @@ def main(argv=None):
                       profile=args.profile, iw_samples=max(0, args.iw_samples), latent_report=args.latent_report,
                       au_threshold=args.au_threshold, binarize=args.binarize,
                       report_objective=objective.reported(specs), sample_report=args.sample_report,
-                      prdc_k=args.prdc)
+                      prdc_k=args.prdc, recon_report=args.recon_report)
     results = []
     member = False
     for group_id, group in enumerate(processes_groups):
