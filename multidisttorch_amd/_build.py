@@ -109,6 +109,8 @@ FILE_FLAGS = {
     "prdc.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
     # likewise: every filter tap is one scalar fmaf, in the order the error analysis assumes
     "recon.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+    # likewise: a projection is one scalar fma chain, a compare-exchange moves values and never rounds them
+    "swd.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
 }
 
 

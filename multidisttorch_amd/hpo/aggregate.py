@@ -14,6 +14,7 @@ LATENT_KEYS = ("kl", "active_units", "mi", "tc", "dwkl")
 SCORES = ("iw_nll", "latent", "test_loss_raw")
 SAMPLE_KEYS = ("mmd2", "nn_acc", "nn_acc_real", "nn_acc_fake")
 PRDC_KEYS = ("k", "precision", "recall", "density", "coverage")
+SWD_KEYS = ("dirs", "swd1", "swd1_se", "swd2", "max_w1")
 RECON_KEYS = ("mse", "psnr", "ssim", "ssim_l", "ssim_cs", "ssim_min")
 
 
@@ -27,13 +28,15 @@ def trial_record(result, opts) -> dict:
         rec["prdc"] = result.extra.get("prdc")
     if opts.recon_report:
         rec["recon_report"] = result.extra.get("recon_report")
+    if opts.swd_dirs > 0:
+        rec["swd"] = result.extra.get("swd")
     return rec
 
 
 def summarize(gathered, specs, opts) -> dict:
     """``gathered``: per rank, the list of its ``trial_record``s (None or empty: an idle rank)."""
     per_trial, wall, failed = {}, 0.0, set()
-    scores = {k: {} for k in SCORES + ("sample_report", "prdc", "recon_report")}
+    scores = {k: {} for k in SCORES + ("sample_report", "prdc", "recon_report", "swd")}
     for lst in gathered:
         for r in lst or []:
             gid = r["group_id"]
@@ -87,4 +90,9 @@ def summarize(gathered, specs, opts) -> dict:
         recon = scores["recon_report"]
         summary["recon_report"] = {str(g): {k: round(v[k], 6) for k in RECON_KEYS} for g, v in sorted(recon.items())}
         summary["best_trial_by_ssim"] = (min(recon, key=lambda g: (-recon[g]["ssim"], g)) if recon else None)
+    if opts.swd_dirs > 0:
+        # a distance in the units of the data with its Monte-Carlo error over the directions: the lowest is the best trial
+        w = scores["swd"]
+        summary["swd"] = {str(g): {k: (v[k] if k == "dirs" else round(v[k], 6)) for k in SWD_KEYS} for g, v in sorted(w.items())}
+        summary["best_trial_by_swd"] = min(w, key=lambda g: (w[g]["swd1"], g)) if w else None
     return summary

@@ -83,6 +83,7 @@ class RunOptions:
     report_objective: tuple = ()           # objective.reported(specs): knobs whose values the metrics carry
     prdc_k: int = 0                        # k > 0: the sample pass adds precision / recall / density / coverage on k-NN radii
     recon_report: bool = False             # MSE / PSNR / SSIM of the test reconstructions after the last epoch
+    swd_dirs: int = 0                      # P > 0: the sample pass adds the sliced Wasserstein distance over P directions
     sample_report: int = 0                 # N > 0: kernel MMD + 1-NN test of N prior samples against N test rows
 
 
@@ -490,7 +491,11 @@ def _sample_eval(trainer, test, opts: RunOptions, group, metrics, device, tag: s
     with trace.range("sample_eval"), trainer.averaged_weights():
         k = int(opts.prdc_k)
         # the default call stays the call it was
-        r = trainer.evaluate_samples(test.data, idx, n, prdc_k=k) if k > 0 else trainer.evaluate_samples(test.data, idx, n)
+        kw = dict(prdc_k=k) if k > 0 else {}
+        P = int(opts.swd_dirs)
+        if P > 0:
+            kw["swd_dirs"] = P
+        r = trainer.evaluate_samples(test.data, idx, n, **kw)
         if device.type == "cuda":
             torch.cuda.synchronize(device)
     r["sample_s"] = round(time.perf_counter() - t, 6)
@@ -502,6 +507,11 @@ def _sample_eval(trainer, test, opts: RunOptions, group, metrics, device, tag: s
         print0(tag + "====> Test set PRDC-{}: precision {:.4f} recall {:.4f} density {:.4f} coverage {:.4f}".format(
             p["k"], p["precision"], p["recall"], p["density"], p["coverage"]), process_group=group)
         out["prdc"] = p
+    if P > 0:
+        w = r["swd"]
+        print0(tag + "====> Test set SWD-{}: W1 {:.6f} +- {:.6f} W2 {:.6f} max {:.6f}".format(
+            w["dirs"], w["swd1"], w["swd1_se"], w["swd2"], w["max_w1"]), process_group=group)
+        out["swd"] = w
     metrics.log(event="sample_eval", **r)
     return out
 

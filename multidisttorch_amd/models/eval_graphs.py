@@ -33,6 +33,7 @@ from .prdc import COLS as PRDC_COLS, check_prdc_args, prdc_rows, prdc_stats
 from .recon_report import COLS as RECON_COLS, check_recon_args, recon_rows, recon_stats
 from .sample_report import (COLS, bandwidths_of, check_sample_args, mean_pair_d2, sample_rows, sample_stats,
                             sample_z)
+from .swd import COLS as SWD_COLS, check_swd_args, swd_directions, swd_rows, swd_stats
 
 __all__ = ["GraphedEval", "GraphedIwEval", "GraphedLatentEval", "SampleEval", "ReconEval", "capture_replayable"]
 
@@ -371,7 +372,7 @@ class SampleEval:
 
     @torch.no_grad()
     def evaluate_samples(self, X: torch.Tensor, idx: torch.Tensor, n_samples=None, return_rows: bool = False,
-                         prdc_k: int = 0) -> dict:
+                         prdc_k: int = 0, swd_dirs: int = 0) -> dict:
         """The sample report of ``n_samples`` decoded prior draws (default: as
         many as rows) against rows ``X[idx]``: ``dict(rows_real, rows_fake,
         mean_pair_d2, bandwidths, mmd2, mmd2_per_bandwidth, nn_acc, nn_acc_real,
@@ -381,8 +382,14 @@ class SampleEval:
         precision, recall, density, coverage)`` of the same rows on k-NN radii
         (models/prdc.py; csrc/kernels/prdc.hip on the hip backend), with
         ``return_rows`` also ``prdc_table`` (float32 ``[rows_real + rows_fake,
-        3]``). Training, eval, iw and latent state are not touched; the result
-        depends on (weights, data, seed, n) only."""
+        3]``). ``swd_dirs > 0`` adds ``swd = dict(dirs, swd1, swd1_se, swd2,
+        max_w1)``, the sliced Wasserstein distance of the same rows over that
+        many random directions (models/swd.py; csrc/kernels/swd.hip on the hip
+        backend), with ``return_rows`` also ``swd_table`` (float32 ``[dirs,
+        2]``: w1, w2sq) and ``swd_proj`` (float32 ``[dirs, rows_real +
+        rows_fake]``: per direction the sorted real | the sorted generated
+        projections). Training, eval, iw and latent state are not touched; the
+        result depends on (weights, data, seed, n, directions) only."""
         idx = idx.to(device=self.device, dtype=torch.int64).contiguous()
         na = idx.numel()
         nb = na if n_samples is None else int(n_samples)
@@ -391,6 +398,8 @@ class SampleEval:
         check_sample_args(na, nb, D)
         if prdc_k:
             check_prdc_args(na, nb, D, prdc_k)
+        if swd_dirs:
+            check_swd_args(na, nb, D, swd_dirs)
         m = mean_pair_d2(real)
         h = bandwidths_of(m)
         z = torch.from_numpy(sample_z(nb, self.Z, self.seed)).to(self.device)
@@ -417,6 +426,18 @@ class SampleEval:
             out["prdc"] = prdc_stats(ptable, na, nb, k)
             if return_rows:
                 out["prdc_table"] = ptable
+        if swd_dirs:
+            P = int(swd_dirs)
+            dirs = torch.from_numpy(swd_directions(P, D, self.seed)).to(self.device)
+            if self.backend != "hip":
+                sproj, stable = swd_rows(real, fake, dirs)
+            else:
+                sproj = torch.empty(P, na + nb, dtype=torch.float32, device=self.device)
+                stable = torch.empty(P, SWD_COLS, dtype=torch.float32, device=self.device)
+                C.swd_rows(real, fake, dirs, sproj, stable)
+            out["swd"] = swd_stats(stable)
+            if return_rows:
+                out.update(swd_table=stable, swd_proj=sproj)
         return out
 
 

@@ -119,6 +119,10 @@ def parse_args(argv=None):
     parser.add_argument("--prdc", type=int, default=0, metavar="K",
                         help="with --sample-report N: also precision, recall, density and coverage of the same rows "
                              "on K-nearest-neighbour radii (fidelity against diversity; 1 <= K <= 8 < N; 0 = off)")
+    parser.add_argument("--swd", type=int, default=0, metavar="P",
+                        help="with --sample-report N: also the sliced Wasserstein distance of the same rows over P "
+                             "random unit directions, with its standard error (a distance in the units of the data; "
+                             "2 <= N <= 16384, 1 <= P <= 4096; 0 = off)")
     parser.add_argument("--recon-report", action="store_true",
                         help="after each trial's last epoch: per-pixel MSE, PSNR and SSIM (with its luminance and "
                              "contrast-structure factors) of the test images against their reconstructions from the "
@@ -130,6 +134,12 @@ def parse_args(argv=None):
         if args.sample_report == 0:
             raise ValueError("--prdc K scores the rows of the sample pass: it needs --sample-report N")
         check_prdc_args(args.sample_report, args.sample_report, 1, args.prdc)
+    if args.swd != 0:
+        from multidisttorch_amd.models.swd import check_swd_args
+
+        if args.sample_report == 0:
+            raise ValueError("--swd P scores the rows of the sample pass: it needs --sample-report N")
+        check_swd_args(args.sample_report, args.sample_report, 1, args.swd)
     if args.sample_report != 0:
         from multidisttorch_amd.models.sample_report import check_sample_args
 
@@ -180,7 +190,7 @@ def main(argv=None):
                       profile=args.profile, iw_samples=max(0, args.iw_samples), latent_report=args.latent_report,
                       au_threshold=args.au_threshold, binarize=args.binarize,
                       report_objective=objective.reported(specs), sample_report=args.sample_report,
-                      prdc_k=args.prdc, recon_report=args.recon_report)
+                      prdc_k=args.prdc, recon_report=args.recon_report, swd_dirs=args.swd)
     results = []
     member = False
     for group_id, group in enumerate(processes_groups):
