@@ -111,6 +111,8 @@ FILE_FLAGS = {
     "recon.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
     # likewise: a projection is one scalar fma chain, a compare-exchange moves values and never rounds them
     "swd.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+    # likewise: the factorisation, the substitution and every fold are scalar f32 chains in one fixed order
+    "gmm.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
 }
 
 

@@ -15,6 +15,7 @@ SCORES = ("iw_nll", "latent", "test_loss_raw")
 SAMPLE_KEYS = ("mmd2", "nn_acc", "nn_acc_real", "nn_acc_fake")
 PRDC_KEYS = ("k", "precision", "recall", "density", "coverage")
 SWD_KEYS = ("dirs", "swd1", "swd1_se", "swd2", "max_w1")
+GMM_KEYS = ("k", "iters", "rows_fit", "ll_fit", "ll_test", "lp_test", "gap", "min_weight")
 RECON_KEYS = ("mse", "psnr", "ssim", "ssim_l", "ssim_cs", "ssim_min")
 
 
@@ -30,13 +31,15 @@ def trial_record(result, opts) -> dict:
         rec["recon_report"] = result.extra.get("recon_report")
     if opts.swd_dirs > 0:
         rec["swd"] = result.extra.get("swd")
+    if opts.gmm_k > 0:
+        rec["gmm"] = result.extra.get("gmm")
     return rec
 
 
 def summarize(gathered, specs, opts) -> dict:
     """``gathered``: per rank, the list of its ``trial_record``s (None or empty: an idle rank)."""
     per_trial, wall, failed = {}, 0.0, set()
-    scores = {k: {} for k in SCORES + ("sample_report", "prdc", "recon_report", "swd")}
+    scores = {k: {} for k in SCORES + ("sample_report", "prdc", "recon_report", "swd", "gmm")}
     for lst in gathered:
         for r in lst or []:
             gid = r["group_id"]
@@ -95,4 +98,11 @@ def summarize(gathered, specs, opts) -> dict:
         w = scores["swd"]
         summary["swd"] = {str(g): {k: (v[k] if k == "dirs" else round(v[k], 6)) for k in SWD_KEYS} for g, v in sorted(w.items())}
         summary["best_trial_by_swd"] = min(w, key=lambda g: (w[g]["swd1"], g)) if w else None
+    if opts.gmm_k > 0:
+        # samples of the fitted mixture against the same test rows: the order by MMD with the prior hole taken out
+        m = scores["gmm"]
+        summary["gmm"] = {str(g): dict({k: (v[k] if k in ("k", "iters", "rows_fit") else round(v[k], 6)) for k in GMM_KEYS},
+                                       **{k: round(v["sample_report"][k], 6) for k in SAMPLE_KEYS})
+                          for g, v in sorted(m.items())}
+        summary["best_trial_by_gmm_mmd2"] = min(m, key=lambda g: (m[g]["sample_report"]["mmd2"], g)) if m else None
     return summary

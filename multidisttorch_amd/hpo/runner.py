@@ -36,6 +36,7 @@ from ..ckpt import checkpoint as ckpt
 from ..data.binarize import Binarizer, check_mode
 from ..data.datasets import ImageSet
 from ..data.sampler import reference_num_replicas, shard_indices
+from ..models.gmm import MAX_ROWS as MAX_GMM_ROWS
 from ..models.recon_report import check_recon_args
 from ..models.trainer_base import LOSS_HIST as LOSS_RING  # per-step loss ring of the trainers
 from ..obs.metrics import TrialMetrics
@@ -84,6 +85,8 @@ class RunOptions:
     prdc_k: int = 0                        # k > 0: the sample pass adds precision / recall / density / coverage on k-NN radii
     recon_report: bool = False             # MSE / PSNR / SSIM of the test reconstructions after the last epoch
     swd_dirs: int = 0                      # P > 0: the sample pass adds the sliced Wasserstein distance over P directions
+    gmm_k: int = 0                         # K > 0: the sample pass fits a K-component mixture prior and scores its samples
+    gmm_iters: int = 50                    # its EM iterations
     sample_report: int = 0                 # N > 0: kernel MMD + 1-NN test of N prior samples against N test rows
 
 
@@ -495,6 +498,11 @@ def _sample_eval(trainer, test, opts: RunOptions, group, metrics, device, tag: s
         P = int(opts.swd_dirs)
         if P > 0:
             kw["swd_dirs"] = P
+        G = int(opts.gmm_k)
+        if G > 0:
+            # the mixture is fitted to codes of the rows the trial trained on
+            Xf, fidx = trainer._data[0], trainer._data[1]
+            kw.update(gmm_k=G, gmm_iters=int(opts.gmm_iters), fit_rows=(Xf, fidx[:MAX_GMM_ROWS]))
         r = trainer.evaluate_samples(test.data, idx, n, **kw)
         if device.type == "cuda":
             torch.cuda.synchronize(device)
@@ -512,6 +520,21 @@ def _sample_eval(trainer, test, opts: RunOptions, group, metrics, device, tag: s
         print0(tag + "====> Test set SWD-{}: W1 {:.6f} +- {:.6f} W2 {:.6f} max {:.6f}".format(
             w["dirs"], w["swd1"], w["swd1_se"], w["swd2"], w["max_w1"]), process_group=group)
         out["swd"] = w
+    if G > 0:
+        g = r["gmm"]
+        gs = g["sample_report"]
+        name = "GMM-{} ".format(g["k"])
+        print0(tag + "====> Test set GMM-{}: ll {:.4f} prior {:.4f} gap {:.4f} MMD2 {:.6f} 1-NN acc {:.4f}".format(
+            g["k"], g["ll_test"], g["lp_test"], g["gap"], gs["mmd2"], gs["nn_acc"]), process_group=group)
+        if k > 0:
+            p = g["prdc"]
+            print0(tag + "====> Test set " + name + "PRDC-{}: precision {:.4f} recall {:.4f} density {:.4f} coverage {:.4f}"
+                   .format(p["k"], p["precision"], p["recall"], p["density"], p["coverage"]), process_group=group)
+        if P > 0:
+            w = g["swd"]
+            print0(tag + "====> Test set " + name + "SWD-{}: W1 {:.6f} +- {:.6f} W2 {:.6f} max {:.6f}".format(
+                w["dirs"], w["swd1"], w["swd1_se"], w["swd2"], w["max_w1"]), process_group=group)
+        out["gmm"] = g
     metrics.log(event="sample_eval", **r)
     return out
 

@@ -27,6 +27,7 @@ import numpy as np
 import torch
 
 from ..ops import native
+from .gmm import check_gmm_args, gmm_fit, gmm_fit_rows, gmm_sample, gmm_score, prior_score
 from .iw import check_iw_args, default_chunk, iw_eps, iw_reduce
 from .latent import check_latent_args, latent_eps, latent_report
 from .prdc import COLS as PRDC_COLS, check_prdc_args, prdc_rows, prdc_stats
@@ -372,7 +373,8 @@ class SampleEval:
 
     @torch.no_grad()
     def evaluate_samples(self, X: torch.Tensor, idx: torch.Tensor, n_samples=None, return_rows: bool = False,
-                         prdc_k: int = 0, swd_dirs: int = 0) -> dict:
+                         prdc_k: int = 0, swd_dirs: int = 0, gmm_k: int = 0, gmm_iters: int = 50,
+                         fit_rows=None) -> dict:
         """The sample report of ``n_samples`` decoded prior draws (default: as
         many as rows) against rows ``X[idx]``: ``dict(rows_real, rows_fake,
         mean_pair_d2, bandwidths, mmd2, mmd2_per_bandwidth, nn_acc, nn_acc_real,
@@ -388,8 +390,18 @@ class SampleEval:
         backend), with ``return_rows`` also ``swd_table`` (float32 ``[dirs,
         2]``: w1, w2sq) and ``swd_proj`` (float32 ``[dirs, rows_real +
         rows_fake]``: per direction the sorted real | the sorted generated
-        projections). Training, eval, iw and latent state are not touched; the
-        result depends on (weights, data, seed, n, directions) only."""
+        projections). ``gmm_k > 0`` (with ``fit_rows=(X_train, idx_train)``)
+        adds ``gmm = dict(k, iters, rows_fit, ll_fit, ll_history, ll_test,
+        lp_test, gap, min_weight, sample_report[, prdc][, swd])``: a
+        ``gmm_k``-component mixture fitted by ``gmm_iters`` EM iterations to one
+        posterior draw per fit row (models/gmm.py; csrc/kernels/gmm.hip on the hip
+        backend), the mean log-density of the rows' own codes under it and under
+        N(0, I) with their difference ``gap``, and the same tables a second time
+        for decoded draws from the mixture; with ``return_rows`` also
+        ``gmm_params``, ``gmm_fake``, ``gmm_fit_z`` and ``gmm_test_z``. That part
+        runs on the latent pass's state, so ``latent_buffers()`` raises until the
+        next ``evaluate_latent``. Training, eval and iw state are not touched; the
+        result depends on (weights, data, seed, n, directions, mixture) only."""
         idx = idx.to(device=self.device, dtype=torch.int64).contiguous()
         na = idx.numel()
         nb = na if n_samples is None else int(n_samples)
@@ -400,10 +412,24 @@ class SampleEval:
             check_prdc_args(na, nb, D, prdc_k)
         if swd_dirs:
             check_swd_args(na, nb, D, swd_dirs)
+        if gmm_k:
+            if fit_rows is None:
+                raise ValueError("evaluate_samples(gmm_k=K) fits the mixture to training rows: pass fit_rows=(X, idx)")
+            check_gmm_args(int(fit_rows[1].numel()), self.Z, gmm_k, gmm_iters)
+            check_gmm_args(na, self.Z, gmm_k, gmm_iters)  # the scored rows
         m = mean_pair_d2(real)
         h = bandwidths_of(m)
         z = torch.from_numpy(sample_z(nb, self.Z, self.seed)).to(self.device)
         fake = self.decode(z).to(torch.float32).reshape(nb, -1).contiguous()
+        out = self._sample_tables(real, fake, m, h, prdc_k, swd_dirs, return_rows)
+        if gmm_k:
+            out.update(self._gmm_report(X, idx, real, nb, m, h, prdc_k, swd_dirs, int(gmm_k), int(gmm_iters), fit_rows,
+                                        return_rows))
+        return out
+
+    def _sample_tables(self, real, fake, m, h, prdc_k, swd_dirs, return_rows) -> dict:
+        """The tables of ``evaluate_samples`` for ``fake`` against ``real`` and their statistics."""
+        (na, D), nb = real.shape, fake.shape[0]
         if self.backend != "hip":
             table = sample_rows(real, fake, h, chunk=max(1, self.SAMPLE_CHUNK_ELEMS // ((na + nb) * D)))
         else:
@@ -438,6 +464,45 @@ class SampleEval:
             out["swd"] = swd_stats(stable)
             if return_rows:
                 out.update(swd_table=stable, swd_proj=sproj)
+        return out
+
+    def _gmm_codes(self, X, idx, step: int) -> torch.Tensor:
+        """One posterior draw per row of ``X[idx]`` (``gmm_fit_rows``), through the latent pass's encoder loop."""
+        idx = idx.to(device=self.device, dtype=torch.int32).contiguous()
+        n, B, Z = idx.numel(), self.B, self.Z
+        X = X.contiguous()
+        if self.backend != "hip":
+            mulv = torch.cat([torch.cat(self._lat_encode_torch(X[idx[b: b + B].long()]), 1)
+                              for b in range(0, n, B)]).float()
+        else:
+            mulv = self._lat_encode(X, idx, n)[:n].clone()
+        self._lat_last = None  # the pass buffer no longer holds an evaluate_latent pass
+        return gmm_fit_rows(mulv[:, :Z], mulv[:, Z:], self.seed, step).contiguous()
+
+    def _gmm_report(self, X, idx, real, nb, m, h, prdc_k, swd_dirs, K, iters, fit_rows, return_rows) -> dict:
+        zf, zt = self._gmm_codes(fit_rows[0], fit_rows[1], 1), self._gmm_codes(X, idx, 2)
+        (nf, Z), nt = zf.shape, zt.shape[0]
+        if self.backend != "hip":
+            fit = gmm_fit(zf, K, iters)
+            params, hist = {k: fit[k] for k in ("pi", "mu", "cov")}, fit["ll_history"]
+            ll = gmm_score(zt, params)
+        else:
+            C = native.require()
+            new = lambda numel: torch.empty(numel, dtype=torch.float32, device=self.device)
+            flat, hist, ll = new(K * (1 + Z + Z * Z)), new(iters + 1), new(nt)
+            C.gmm_fit(zf, K, iters, new(C.gmm_ws_numel(nf, Z, K)), flat, hist)
+            params = dict(pi=flat[:K], mu=flat[K: K + K * Z].view(K, Z), cov=flat[K + K * Z:].view(K, Z, Z))
+            C.gmm_score(zt, params["pi"], params["mu"], params["cov"], new(C.gmm_ws_numel(nt, Z, K)), ll)
+        ll_test, lp_test = float(ll.double().mean()), float(prior_score(zt.double()).mean())
+        gfake = self.decode(gmm_sample(params, nb, self.seed).to(self.device)).to(torch.float32).reshape(nb, -1).contiguous()
+        rep = self._sample_tables(real, gfake, m, h, prdc_k, swd_dirs, False)
+        extra = {k: rep.pop(k) for k in ("prdc", "swd") if k in rep}
+        hist = [float(v) for v in hist.double().cpu()]
+        gmm = dict(k=K, iters=iters, rows_fit=nf, ll_fit=hist[-1], ll_history=hist, ll_test=ll_test, lp_test=lp_test,
+                   gap=ll_test - lp_test, min_weight=float(params["pi"].min()), sample_report=rep, **extra)
+        out = dict(gmm=gmm)
+        if return_rows:
+            out.update(gmm_params=params, gmm_fake=gfake, gmm_fit_z=zf, gmm_test_z=zt)
         return out
 
 

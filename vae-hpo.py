@@ -123,6 +123,12 @@ def parse_args(argv=None):
                         help="with --sample-report N: also the sliced Wasserstein distance of the same rows over P "
                              "random unit directions, with its standard error (a distance in the units of the data; "
                              "2 <= N <= 16384, 1 <= P <= 4096; 0 = off)")
+    parser.add_argument("--gmm", type=int, default=0, metavar="K",
+                        help="with --sample-report N: also fit a K-component full-covariance Gaussian mixture to latent "
+                             "codes of the training rows, report the test codes' log-density under it against N(0, I), "
+                             "and score N decoded draws from it with the same tables (1 <= K <= 32; 0 = off)")
+    parser.add_argument("--gmm-iters", type=int, default=50, metavar="T",
+                        help="EM iterations of the --gmm fit (a fixed count, 0 <= T <= 1000)")
     parser.add_argument("--recon-report", action="store_true",
                         help="after each trial's last epoch: per-pixel MSE, PSNR and SSIM (with its luminance and "
                              "contrast-structure factors) of the test images against their reconstructions from the "
@@ -140,6 +146,12 @@ def parse_args(argv=None):
         if args.sample_report == 0:
             raise ValueError("--swd P scores the rows of the sample pass: it needs --sample-report N")
         check_swd_args(args.sample_report, args.sample_report, 1, args.swd)
+    if args.gmm != 0:
+        from multidisttorch_amd.models.gmm import check_gmm_args
+
+        if args.sample_report == 0:
+            raise ValueError("--gmm K scores samples of a mixture prior in the sample pass: it needs --sample-report N")
+        check_gmm_args(args.sample_report, 1, args.gmm, args.gmm_iters)
     if args.sample_report != 0:
         from multidisttorch_amd.models.sample_report import check_sample_args
 
@@ -190,7 +202,8 @@ def main(argv=None):
                       profile=args.profile, iw_samples=max(0, args.iw_samples), latent_report=args.latent_report,
                       au_threshold=args.au_threshold, binarize=args.binarize,
                       report_objective=objective.reported(specs), sample_report=args.sample_report,
-                      prdc_k=args.prdc, recon_report=args.recon_report, swd_dirs=args.swd)
+                      prdc_k=args.prdc, recon_report=args.recon_report, swd_dirs=args.swd,
+                      gmm_k=args.gmm, gmm_iters=args.gmm_iters)
     results = []
     member = False
     for group_id, group in enumerate(processes_groups):
