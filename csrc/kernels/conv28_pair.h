@@ -83,6 +83,36 @@ struct StepKargs {
 using g64 = __attribute__((address_space(1))) unsigned long long;
 using g32i = __attribute__((address_space(1))) int;
 
+// Kernel-argument segment of the running kernel (f28_step_k: a StepKargs),
+// through an address the compiler cannot match with the entry loads of the
+// formal arguments: a value loaded through it is loaded where it is used
+// instead of living in SGPRs from the kernel's entry on.
+using kseg = const __attribute__((address_space(4))) char;
+__device__ __forceinline__ kseg* kargs() {
+  kseg* k = (kseg*)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(k));
+  return k;
+}
+
+// Scalar member at byte offset `off` of the segment.
+template <class T>
+__device__ __forceinline__ T kval(size_t off) {
+  return *(const __attribute__((address_space(4))) T*)(kargs() + off);
+}
+
+// Pointer member at byte offset `off`, advanced `stride` bytes per sample to
+// sample n; a null argument stays null (the bodies test the optional ones).
+template <class T>
+__device__ __forceinline__ T* kptr(size_t off, size_t stride = 0, int n = 0) {
+  const unsigned long long v = kval<unsigned long long>(off);
+  // through a global-address-space pointer, so the accesses stay global_* (a
+  // generic pointer would make them flat_*, which also count in lgkmcnt and
+  // so hold every later LDS wait until the global access completes)
+  auto* g = (__attribute__((address_space(1))) T*)(v ? v + stride * (unsigned long long)n : 0ull);
+  return (T*)g;
+}
+#define F28_KP(T, member, stride) kptr<T>(offsetof(StepKargs, member), (stride), n)
+
 // `near`: both workgroups of the pair run on ONE XCD (their HW_REG_XCC_ID
 // match, exchanged in X1), so they share one L2: the granule goes out as a
 // plain (workgroup-scope) store that stays in that L2 instead of an sc1
@@ -116,7 +146,7 @@ __device__ __forceinline__ void xput(unsigned long long* g, uint32_t tag, uint32
 // carry `tag`, returns their payloads in v and clears them. Wave-uniform loop.
 template <int N>
 __device__ __forceinline__ void xget(unsigned long long* base, const int (&gi)[N], uint32_t tag, uint32_t (&v)[N],
-                                     unsigned* err, bool near) {
+                                     bool near) {
   uint32_t pend = 0;
 #pragma unroll
   for (int k = 0; k < N; ++k) {
@@ -137,7 +167,7 @@ __device__ __forceinline__ void xget(unsigned long long* base, const int (&gi)[N
     }
     if (!__any(pend != 0)) break;
     if ((spin & 15) == 15 && __builtin_amdgcn_s_memrealtime() - t0 > kSpinTicks) {
-      if (pend) atomicOr(err, 1u);
+      if (pend) atomicOr(kptr<unsigned>(offsetof(StepKargs, pc.err)), 1u);
       break;
     }
     __builtin_amdgcn_s_sleep(1);
@@ -152,35 +182,6 @@ __device__ __forceinline__ void xget(unsigned long long* base, const int (&gi)[N
     }
 }
 
-// Kernel-argument segment of the running kernel (f28_step_k: a StepKargs),
-// through an address the compiler cannot match with the entry loads of the
-// formal arguments: a value loaded through it is loaded where it is used
-// instead of living in SGPRs from the kernel's entry on.
-using kseg = const __attribute__((address_space(4))) char;
-__device__ __forceinline__ kseg* kargs() {
-  kseg* k = (kseg*)__builtin_amdgcn_kernarg_segment_ptr();
-  asm volatile("" : "+s"(k));
-  return k;
-}
-
-// Scalar member at byte offset `off` of the segment.
-template <class T>
-__device__ __forceinline__ T kval(size_t off) {
-  return *(const __attribute__((address_space(4))) T*)(kargs() + off);
-}
-
-// Pointer member at byte offset `off`, advanced `stride` bytes per sample to
-// sample n; a null argument stays null (the bodies test the optional ones).
-template <class T>
-__device__ __forceinline__ T* kptr(size_t off, size_t stride = 0, int n = 0) {
-  const unsigned long long v = kval<unsigned long long>(off);
-  // through a global-address-space pointer, so the accesses stay global_* (a
-  // generic pointer would make them flat_*, which also count in lgkmcnt and
-  // so hold every later LDS wait until the global access completes)
-  auto* g = (__attribute__((address_space(1))) T*)(v ? v + stride * (unsigned long long)n : 0ull);
-  return (T*)g;
-}
-#define F28_KP(T, member, stride) kptr<T>(offsetof(StepKargs, member), (stride), n)
 
 __device__ __forceinline__ uint32_t fbits(float f) { return __builtin_bit_cast(uint32_t, f); }
 __device__ __forceinline__ float bitsf(uint32_t u) { return __builtin_bit_cast(float, u); }
@@ -314,23 +315,51 @@ __device__ __forceinline__ void pair_rest(uint8_t* lds, int n, int r) {
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  // the role as one scalar word: derived from the caller's compare, `r == 0` lived as a 64-bit lane
+  // mask from entry to Q4 (an SGPR pair the allocator spilled)
+  r = __builtin_amdgcn_readfirstlane(r);
   const bool train = kval<int>(offsetof(StepKargs, fa.train)) != 0;
-  auto stamps = [&] { return kptr<unsigned long long>(offsetof(StepKargs, fa.stamps), 16 * 8, (int)blockIdx.x); };
-  auto state = [&] { return F28_KP(const TrainState, fa.st, 0); };
+  // The step's scalars, loaded ONCE here (nothing writes TrainState / HParams
+  // during this launch): the state's words and the Philox key go out with the
+  // `step` load the tags need anyway, so P4 and Q4 start no load chain of
+  // their own (pointer from the segment -> state -> hyper-parameters, one
+  // round trip each, issued by 32 lanes while everyone else sat at the
+  // barrier). Thread 0 leaves them in six LDS words (Scr[24 .. 30): kept in
+  // SGPRs to P3 they cost spills); eps is drawn in P3, under its weight loads. Whether
+  // stamps are on is ONE SGPR (the row's address as a live pair spilled), so a
+  // phase stamp with stamps off is a scalar branch instead of a segment load.
+  // (a scalar word, not a lane mask merged with tid == 0)
+  const int st_on = __builtin_amdgcn_readfirstlane((int)(kval<unsigned long long>(offsetof(StepKargs, fa.stamps)) != 0ull));
+  auto strow = [&] { return kptr<unsigned long long>(offsetof(StepKargs, fa.stamps), 16 * 8, (int)blockIdx.x); };
   auto pstamp = [&](int k) {
-    if (tid == 0) {
-      unsigned long long* st = stamps();
-      if (st) st[k] = __builtin_amdgcn_s_memrealtime();
+    if (st_on) {
+      if (tid == 0) strow()[k] = __builtin_amdgcn_s_memrealtime();
     }
   };
   const int p0 = r ? 24 : 0, p1 = r ? 49 : 24;  // own pixels of the 7x7 maps
   const int q0 = r ? 0 : 24, q1 = r ? 24 : 49;  // the partner's
   const int k0 = 64 * p0, klen = 64 * (p1 - p0);
-  const uint32_t tg = (uint32_t)state()->step * 8u;  // tags tg+1 .. tg+6 (never 0)
+  const TrainState* const stt = F28_KP(const TrainState, fa.st, 0);
+  const HParams* const hpp = F28_KP(const HParams, fa.hp, 0);
+  const unsigned long long stp = (unsigned long long)stt->step;
+  const float fbv = stt->fb_t, klv = stt->kl_next;
+  const uint32_t seed_lo = hpp->seed_lo, seed_hi = hpp->seed_hi;
+  // all five loads in flight together (sunk into thread 0's block below they
+  // started only after the wait for `step`: a second round trip)
+  asm volatile("" ::"v"(fbv), "v"(klv), "v"(seed_lo), "v"(seed_hi));
+  if (tid == 0) {
+    uint32_t* const key = reinterpret_cast<uint32_t*>(Scr) + 24;  // P3's Philox draw: step, seed
+    key[0] = (uint32_t)(stp & 0xffffffffu);
+    key[1] = (uint32_t)(stp >> 32);
+    key[2] = seed_lo;
+    key[3] = seed_hi;
+    Scr[28] = fbv;  // the step's free-bits floor (P4, Q4)
+    Scr[29] = klv;  // the KL weight of the step being computed (Q4)
+  }
+  const uint32_t tg = (uint32_t)stp * 8u;  // tags tg+1 .. tg+6 (never 0)
   unsigned long long* const xg = F28_KP(unsigned long long, pc.xg, 2 * kXW * 8);
   unsigned long long* xo = xg + r * kXW;        // own slab (written)
   unsigned long long* xi = xg + (r ^ 1) * kXW;  // partner's (read, cleared)
-  unsigned* err = F28_KP(unsigned, pc.err, 0);
   const float* Bias = reinterpret_cast<const float*>(lds + L::Bias);
   const uint8_t* Zero = lds + L::Bias + 4 * kZero;
   unsigned xcc;
@@ -379,6 +408,14 @@ __device__ __forceinline__ void pair_rest(uint8_t* lds, int n, int r) {
     ld_rows(wh, 1, wr[1]);
     ld_rows(wh, 2, wr[2]);
     ld_rows(wh, 3, wr[3]);
+    // eps for P4, drawn here: it needs nothing of this phase, and the wave
+    // waits for its weight rows anyway (keyed as before: element, stream, step)
+    if (tid < 32) {
+      const uint32_t stream = kval<uint32_t>(offsetof(StepKargs, fa.stream));
+      const uint32_t* const key = reinterpret_cast<const uint32_t*>(Scr) + 24;  // step, seed (thread 0, at entry)
+      const u32x4 bits = philox4x32_10(u32x4{(uint32_t)(n * 32 + tid), stream, key[0], key[1]}, key[2], key[3]);
+      Eps[tid] = normal_from_bits(bits.x, bits.y);
+    }
     float d[8];
 #pragma unroll
     for (int c2 = 0; c2 < 4; ++c2)
@@ -403,13 +440,16 @@ __device__ __forceinline__ void pair_rest(uint8_t* lds, int n, int r) {
       }
 #pragma unroll
     for (int i = 0; i < 8; ++i) d[i] = wave_sum(d[i]);
-    if (lane == 0) {
+    // wave_sum is a butterfly: every lane holds the same eight sums. Lane i < 8
+    // takes sum i, so the wave publishes its rows in ONE store instruction
+    // (lane 0 used to issue eight, one after another).
+    float dv = d[0];
 #pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const int o = w + 16 * (i >> 1) + 8 * (i & 1);
-        Hs[o] = d[i];
-        xput(xo + kX1 + o, tg + 1, fbits(d[i]), false);
-      }
+    for (int i = 1; i < 8; ++i) dv = lane == i ? d[i] : dv;
+    if (lane < 8) {
+      const int o = w + 16 * (lane >> 1) + 8 * (lane & 1);
+      Hs[o] = dv;
+      xput(xo + kX1 + o, tg + 1, fbits(dv), false);
     }
   }
   TapImageRegs w3r;
@@ -432,20 +472,16 @@ __device__ __forceinline__ void pair_rest(uint8_t* lds, int n, int r) {
     float kl = 0.f;
     if (tid < 32) {
       const int c = tid;
-      // eps first: it needs nothing from the partner, so it overlaps the X1 wait
-      // (so does the load of the free-bits floor, issued with the step's)
-      const TrainState* stt = state();
-      const unsigned long long stp = (unsigned long long)stt->step;
-      const float fb = stt->fb_t;
-      const HParams* hp = F28_KP(const HParams, fa.hp, 0);
-      const uint32_t stream = kval<uint32_t>(offsetof(StepKargs, fa.stream));
-      const u32x4 bits = philox4x32_10(u32x4{(uint32_t)(n * 32 + c), stream, (uint32_t)(stp & 0xffffffffu),
-                                             (uint32_t)(stp >> 32)},
-                                       hp->seed_lo, hp->seed_hi);
-      const float ep = normal_from_bits(bits.x, bits.y);
+      // eps (drawn in P3) and the free-bits floor are in LDS; the output
+      // pointers are fetched before the poll, so nothing but arithmetic and
+      // the stores themselves follows the partner's granules
+      const float ep = Eps[c], fb = Scr[28];
+      float* const mulvp = F28_KP(float, fa.mulv, 64 * 4);
+      float* const epsp = F28_KP(float, fa.eps, 32 * 4);
+      __bf16* const z16p = F28_KP(__bf16, fa.z16, 32 * 2);
       const int gi[2] = {kX1 + c, kX1 + 32 + c};
       uint32_t pv[2];
-      xget<2>(xi, gi, tg + 1, pv, err, false);
+      xget<2>(xi, gi, tg + 1, pv, false);
       const float m0 = Hs[c], l0 = Hs[32 + c], mp = bitsf(pv[0]), lp = bitsf(pv[1]);
       const float mu = (r ? mp + m0 : m0 + mp) + Bias[kBh + c];
       const float lv = (r ? lp + l0 : l0 + lp) + Bias[kBh + 32 + c];
@@ -455,30 +491,28 @@ __device__ __forceinline__ void pair_rest(uint8_t* lds, int n, int r) {
       const float zz = fmaf(ep, sd, mu);
       // explicit: one rounding sequence in both bodies and in Q4 (free bits, common.h)
       kl = fb_fwd(kl_sum_fma(mu, lv, sd), fb);
-      Zs[c] = (__bf16)zz;
-      Eps[c] = ep;
+      Zs[c] = (__bf16)zz;  // (Eps[c] keeps eps for Q4)
       if (train && r == 0) {
-        float* const mulvp = F28_KP(float, fa.mulv, 64 * 4);
         mulvp[c] = mu;
         mulvp[32 + c] = lv;
-        F28_KP(float, fa.eps, 32 * 4)[c] = ep;
-        F28_KP(__bf16, fa.z16, 32 * 2)[c] = (__bf16)zz;
+        epsp[c] = ep;
+        z16p[c] = (__bf16)zz;
       }
-    }
-    if (tid == 32) {
-      const int gi[1] = {kX1 + 64};
-      uint32_t pv[1];
-      xget<1>(xi, gi, tg + 1, pv, err, false);
-      reinterpret_cast<int*>(Scr)[30] = pv[0] == xcc;
     }
     kl = wave_sum(kl);
     if (tid == 0) Scr[0] = -0.5f * kl;
+  } else if (tid == 64) {
+    // the partner's XCD id, polled by a lane of wave 1 (idle here): in wave 0,
+    // behind the 32 lanes above, it was a second poll loop after the first
+    const int gi[1] = {kX1 + 64};
+    uint32_t pv[1];
+    xget<1>(xi, gi, tg + 1, pv, false);
+    reinterpret_cast<int*>(Scr)[30] = pv[0] == xcc;
   }
   lds_barrier();
   const bool near = __builtin_amdgcn_readfirstlane(reinterpret_cast<const int*>(Scr)[30]) != 0;
-  if (tid == 0) {  // slot 15: mode | near << 4
-    unsigned long long* st = stamps();
-    if (st) st[15] |= (unsigned long long)near << 4;
+  if (st_on) {  // slot 15: mode | near << 4
+    if (tid == 0) strow()[15] |= (unsigned long long)near << 4;
   }
 
   pstamp(5);
@@ -506,7 +540,7 @@ __device__ __forceinline__ void pair_rest(uint8_t* lds, int n, int r) {
     const int cnt = 32 * (q1 - q0);
     const int gi[2] = {tid < cnt ? kX2 + tid : -1, tid + 512 < cnt ? kX2 + tid + 512 : -1};
     uint32_t pv[2];
-    xget<2>(xi, gi, tg + 2, pv, err, near);
+    xget<2>(xi, gi, tg + 2, pv, near);
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
       if (gi[k] >= 0) {
@@ -568,7 +602,7 @@ __device__ __forceinline__ void pair_rest(uint8_t* lds, int n, int r) {
     }
     const int gi[2] = {tid < 784 ? kX3 + tid : -1, tid + 512 < 784 ? kX3 + tid + 512 : -1};
     uint32_t pv[2];
-    xget<2>(xi, gi, tg + 3, pv, err, near);
+    xget<2>(xi, gi, tg + 3, pv, near);
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
       const int pix = tid + 512 * k;
@@ -594,20 +628,31 @@ __device__ __forceinline__ void pair_rest(uint8_t* lds, int n, int r) {
     Scr[16 + w] = gsum;
   }
   lds_barrier();
-  if (tid == 0 && r == 0) {
-    float sl = 0.f, sg = 0.f;
+  // The sample's BCE / KLD / dec2-bias partials: nobody in the kernel waits for
+  // them, so the thread that sums and stores them is the first of wave 7
+  // (one pixel tile in Q1 where waves 0-4 have two), after its Q1 work has
+  // been issued. Thread 0 used to do it here, three pointer fetches and all,
+  // with the training path queued behind it. Scr[0], Scr[8 .. 24) stay
+  // untouched until then.
+  auto loss_parts = [&] {
+    if (tid == 448 && r == 0) {
+      float sl = 0.f, sg = 0.f;
 #pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      sl += Scr[8 + i];
-      sg += Scr[16 + i];
+      for (int i = 0; i < 8; ++i) {
+        sl += Scr[8 + i];
+        sg += Scr[16 + i];
+      }
+      F28_KP(float, fa.bce_part, 4)[0] = sl;
+      F28_KP(float, fa.kld_part, 4)[0] = Scr[0];
+      if (float* d4 = F28_KP(float, fa.db4_part, 4)) d4[0] = sg;
     }
-    F28_KP(float, fa.bce_part, 4)[0] = sl;
-    F28_KP(float, fa.kld_part, 4)[0] = Scr[0];
-    if (float* d4 = F28_KP(float, fa.db4_part, 4)) d4[0] = sg;
-  }
+  };
   // eval (forward only): both halves end here; X1-X3 are consumed (cleared),
   // X4-X6 never written, so the granules are zero for the next launch
-  if (!train) return;
+  if (!train) {
+    loss_parts();
+    return;
+  }
 
   pstamp(8);
   // ---- Q1: dec2 backward-data on own channels x dec1 ReLU mask; X4 publishes gd1.
@@ -673,22 +718,18 @@ __device__ __forceinline__ void pair_rest(uint8_t* lds, int n, int r) {
   bf16x8 wd0[13];
 #pragma unroll
   for (int i = 0; i < 13; ++i) wd0[i] = wd_ld(i);
-  lds_barrier();
-  if (tid < 128) {  // dec1 bias partials of own channels: 8 lanes per channel, fixed order
-    const int c = tid >> 3, part = tid & 7;
-    float s = 0.f;
-    for (int p = part; p < 196; p += 8) s += CSB[c * 197 + p];
-    s += __shfl_xor(s, 1, 64);
-    s += __shfl_xor(s, 2, 64);
-    s += __shfl_xor(s, 4, 64);
-    if (part == 0) F28_KP(float, ba.db3_part, 32 * 4)[16 * r + c] = s;
-  }
+  loss_parts();
+  // No barrier here: the only reader of other threads' Q1 output before Q2 was
+  // the dec1 bias partial sum over CSB, and no phase of the kernel reads its
+  // result. It now runs in X5 + Q4, on waves that only wait there (CSB is not
+  // written again before Q5). X4's arrivals go to the partner's channel chunks
+  // of GD1, which no own Q1 store touches.
   {  // X4: the partner's gd1 channels into the img14 image
     int gi[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) gi[k] = tid + 512 * k < 1568 ? kX4 + tid + 512 * k : -1;
     uint32_t pv[4];
-    xget<4>(xi, gi, tg + 4, pv, err, near);
+    xget<4>(xi, gi, tg + 4, pv, near);
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       if (gi[k] >= 0) {
@@ -770,29 +811,45 @@ __device__ __forceinline__ void pair_rest(uint8_t* lds, int n, int r) {
 #pragma unroll
     for (int i = 0; i < 8; ++i) mine += DZR[i * 32 + c];
     xput(xo + kX5 + c, tg + 5, fbits(mine), near);
-    const int gi[1] = {kX5 + c};
-    uint32_t pv[1];
-    xget<1>(xi, gi, tg + 5, pv, err, near);
-    const float dz = r ? bitsf(pv[0]) + mine : mine + bitsf(pv[0]);
-    // the KL weight of the step being computed (t = step + 1: the step is advanced by a later launch)
-    const TrainState* const stt = state();
-    const float beta = stt->kl_next, fb = stt->fb_t;
+    // everything that does not need the partner's half, before the poll: the
+    // KL weight of the step being computed (t = step + 1: the step is advanced
+    // by a later launch) and the free-bits floor from their LDS words (no
+    // state load behind the poll), the KL terms, the output pointers
+    const float beta = Scr[29], fb = Scr[28];
     const float mu = Hs[c], lv = Hs[32 + c], ep = Eps[c];
     const float sd = expf(0.5f * lv);
     const float ks = kl_sum_fma(mu, lv, sd);  // as X1 + P4 formed it
     const float be = fb_bwd(ks, fb, beta);
+    float* const dmp = F28_KP(float, ba.dmulv, 64 * 4);
+    __bf16* const dm16p = F28_KP(__bf16, ba.dmulv16, 64 * 2);
+    const int gi[1] = {kX5 + c};
+    uint32_t pv[1];
+    xget<1>(xi, gi, tg + 5, pv, near);
+    const float dz = r ? bitsf(pv[0]) + mine : mine + bitsf(pv[0]);
     const float dm = kl_dmu(dz, be, mu);
     const float dl = kl_dlv(dz, ep, sd, be);
     DMs[c] = dm;
     DMs[32 + c] = dl;
     if (r == 0) {
-      float* const dmp = F28_KP(float, ba.dmulv, 64 * 4);
-      __bf16* const dm16p = F28_KP(__bf16, ba.dmulv16, 64 * 2);
       dmp[c] = dm;
       dmp[32 + c] = dl;
       dm16p[c] = (__bf16)dm;
       dm16p[32 + c] = (__bf16)dl;
     }
+  } else if (tid >= 64 && tid < 192) {
+    // dec1 bias partials of own channels (Q1 left them in CSB): 8 lanes per
+    // channel, fixed order, on waves 1 and 2, which only wait for wave 0 here
+    const int c = (tid - 64) >> 3, part = tid & 7;
+    float v[25];  // every read first, then the sum in the order p = part, part + 8, ..
+#pragma unroll
+    for (int k = 0; k < 25; ++k) v[k] = part + 8 * k < 196 ? CSB[c * 197 + part + 8 * k] : 0.f;
+    float s = 0.f;
+#pragma unroll
+    for (int k = 0; k < 25; ++k) s = part + 8 * k < 196 ? s + v[k] : s;
+    s += __shfl_xor(s, 1, 64);
+    s += __shfl_xor(s, 2, 64);
+    s += __shfl_xor(s, 4, 64);
+    if (part == 0) F28_KP(float, ba.db3_part, 32 * 4)[16 * r + c] = s;
   }
   lds_barrier();
 
@@ -847,7 +904,7 @@ __device__ __forceinline__ void pair_rest(uint8_t* lds, int n, int r) {
       gi[k] = g < 800 && c < nckp ? kX6 + g : -1;
     }
     uint32_t pv[2];
-    xget<2>(xi, gi, tg + 6, pv, err, near);
+    xget<2>(xi, gi, tg + 6, pv, near);
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
       if (gi[k] >= 0) {
