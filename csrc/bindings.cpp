@@ -26,6 +26,7 @@ void bind_two_sample(pybind11::module& m);
 void bind_prdc(pybind11::module& m);
 void bind_recon(pybind11::module& m);
 void bind_swd(pybind11::module& m);
+void bind_sinkhorn(pybind11::module& m);
 void bind_gmm(pybind11::module& m);
 }  // namespace mdt
 
@@ -51,6 +52,7 @@ PYBIND11_MODULE(_C, m) {
   mdt::bind_prdc(m);
   mdt::bind_recon(m);
   mdt::bind_swd(m);
+  mdt::bind_sinkhorn(m);
   mdt::bind_gmm(m);
 
   // the trial-state owner of both trainers (runtime/trial_state.h); kLossHist: the length of its loss rings

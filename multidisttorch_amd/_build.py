@@ -113,6 +113,8 @@ FILE_FLAGS = {
     "swd.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
     # likewise: the factorisation, the substitution and every fold are scalar f32 chains in one fixed order
     "gmm.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+    # likewise: a cost is one scalar fma on the Gram chain, a running (max, sum) one scalar chain per row or column
+    "sinkhorn.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
 }
 
 

@@ -15,6 +15,7 @@ SCORES = ("iw_nll", "latent", "test_loss_raw")
 SAMPLE_KEYS = ("mmd2", "nn_acc", "nn_acc_real", "nn_acc_fake")
 PRDC_KEYS = ("k", "precision", "recall", "density", "coverage")
 SWD_KEYS = ("dirs", "swd1", "swd1_se", "swd2", "max_w1")
+SINKHORN_KEYS = ("blur", "iters", "scale", "sinkhorn", "w2", "ot", "marg_err")
 GMM_KEYS = ("k", "iters", "rows_fit", "ll_fit", "ll_test", "lp_test", "gap", "min_weight")
 RECON_KEYS = ("mse", "psnr", "ssim", "ssim_l", "ssim_cs", "ssim_min")
 
@@ -33,13 +34,15 @@ def trial_record(result, opts) -> dict:
         rec["swd"] = result.extra.get("swd")
     if opts.gmm_k > 0:
         rec["gmm"] = result.extra.get("gmm")
+    if opts.sinkhorn_blur > 0:
+        rec["sinkhorn"] = result.extra.get("sinkhorn")
     return rec
 
 
 def summarize(gathered, specs, opts) -> dict:
     """``gathered``: per rank, the list of its ``trial_record``s (None or empty: an idle rank)."""
     per_trial, wall, failed = {}, 0.0, set()
-    scores = {k: {} for k in SCORES + ("sample_report", "prdc", "recon_report", "swd", "gmm")}
+    scores = {k: {} for k in SCORES + ("sample_report", "prdc", "recon_report", "swd", "gmm", "sinkhorn")}
     for lst in gathered:
         for r in lst or []:
             gid = r["group_id"]
@@ -105,4 +108,10 @@ def summarize(gathered, specs, opts) -> dict:
                                        **{k: round(v["sample_report"][k], 6) for k in SAMPLE_KEYS})
                           for g, v in sorted(m.items())}
         summary["best_trial_by_gmm_mmd2"] = min(m, key=lambda g: (m[g]["sample_report"]["mmd2"], g)) if m else None
+    if opts.sinkhorn_blur > 0:
+        # the debiased entropic transport distance in the squared units of the data: the lowest is the best trial
+        w = scores["sinkhorn"]
+        summary["sinkhorn"] = {str(g): {k: (v[k] if k in ("blur", "iters") else float(f"{v[k]:.6g}")) for k in SINKHORN_KEYS}
+                               for g, v in sorted(w.items())}
+        summary["best_trial_by_sinkhorn"] = min(w, key=lambda g: (w[g]["sinkhorn"], g)) if w else None
     return summary

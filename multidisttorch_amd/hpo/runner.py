@@ -87,6 +87,8 @@ class RunOptions:
     swd_dirs: int = 0                      # P > 0: the sample pass adds the sliced Wasserstein distance over P directions
     gmm_k: int = 0                         # K > 0: the sample pass fits a K-component mixture prior and scores its samples
     gmm_iters: int = 50                    # its EM iterations
+    sinkhorn_blur: float = 0.0             # E > 0: the sample pass adds the Sinkhorn divergence at blur E (a fraction of the scale)
+    sinkhorn_iters: int = 100              # its annealed iterations
     sample_report: int = 0                 # N > 0: kernel MMD + 1-NN test of N prior samples against N test rows
 
 
@@ -503,6 +505,9 @@ def _sample_eval(trainer, test, opts: RunOptions, group, metrics, device, tag: s
             # the mixture is fitted to codes of the rows the trial trained on
             Xf, fidx = trainer._data[0], trainer._data[1]
             kw.update(gmm_k=G, gmm_iters=int(opts.gmm_iters), fit_rows=(Xf, fidx[:MAX_GMM_ROWS]))
+        E = float(opts.sinkhorn_blur)
+        if E > 0:
+            kw.update(sinkhorn_blur=E, sinkhorn_iters=int(opts.sinkhorn_iters))
         r = trainer.evaluate_samples(test.data, idx, n, **kw)
         if device.type == "cuda":
             torch.cuda.synchronize(device)
@@ -520,6 +525,12 @@ def _sample_eval(trainer, test, opts: RunOptions, group, metrics, device, tag: s
         print0(tag + "====> Test set SWD-{}: W1 {:.6f} +- {:.6f} W2 {:.6f} max {:.6f}".format(
             w["dirs"], w["swd1"], w["swd1_se"], w["swd2"], w["max_w1"]), process_group=group)
         out["swd"] = w
+    sink_line = "Sinkhorn-{:g}: S {:.6f} W2 {:.6f} OT {:.6f} marg err {:.3e} ({} iters)"
+    if E > 0:
+        w = r["sinkhorn"]
+        print0(tag + "====> Test set " + sink_line.format(w["blur"], w["sinkhorn"], w["w2"], w["ot"], w["marg_err"], w["iters"]),
+               process_group=group)
+        out["sinkhorn"] = w
     if G > 0:
         g = r["gmm"]
         gs = g["sample_report"]
@@ -534,6 +545,10 @@ def _sample_eval(trainer, test, opts: RunOptions, group, metrics, device, tag: s
             w = g["swd"]
             print0(tag + "====> Test set " + name + "SWD-{}: W1 {:.6f} +- {:.6f} W2 {:.6f} max {:.6f}".format(
                 w["dirs"], w["swd1"], w["swd1_se"], w["swd2"], w["max_w1"]), process_group=group)
+        if E > 0:
+            w = g["sinkhorn"]
+            print0(tag + "====> Test set " + name + sink_line.format(w["blur"], w["sinkhorn"], w["w2"], w["ot"], w["marg_err"],
+                                                                    w["iters"]), process_group=group)
         out["gmm"] = g
     metrics.log(event="sample_eval", **r)
     return out

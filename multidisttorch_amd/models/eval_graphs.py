@@ -34,6 +34,7 @@ from .prdc import COLS as PRDC_COLS, check_prdc_args, prdc_rows, prdc_stats
 from .recon_report import COLS as RECON_COLS, check_recon_args, recon_rows, recon_stats
 from .sample_report import (COLS, bandwidths_of, check_sample_args, mean_pair_d2, sample_rows, sample_stats,
                             sample_z)
+from .sinkhorn import COLS as SINKHORN_COLS, check_sinkhorn_args, sinkhorn_rows, sinkhorn_stats
 from .swd import COLS as SWD_COLS, check_swd_args, swd_directions, swd_rows, swd_stats
 
 __all__ = ["GraphedEval", "GraphedIwEval", "GraphedLatentEval", "SampleEval", "ReconEval", "capture_replayable"]
@@ -374,7 +375,7 @@ class SampleEval:
     @torch.no_grad()
     def evaluate_samples(self, X: torch.Tensor, idx: torch.Tensor, n_samples=None, return_rows: bool = False,
                          prdc_k: int = 0, swd_dirs: int = 0, gmm_k: int = 0, gmm_iters: int = 50,
-                         fit_rows=None) -> dict:
+                         fit_rows=None, sinkhorn_blur: float = 0.0, sinkhorn_iters: int = 100) -> dict:
         """The sample report of ``n_samples`` decoded prior draws (default: as
         many as rows) against rows ``X[idx]``: ``dict(rows_real, rows_fake,
         mean_pair_d2, bandwidths, mmd2, mmd2_per_bandwidth, nn_acc, nn_acc_real,
@@ -390,9 +391,15 @@ class SampleEval:
         backend), with ``return_rows`` also ``swd_table`` (float32 ``[dirs,
         2]``: w1, w2sq) and ``swd_proj`` (float32 ``[dirs, rows_real +
         rows_fake]``: per direction the sorted real | the sorted generated
-        projections). ``gmm_k > 0`` (with ``fit_rows=(X_train, idx_train)``)
+        projections). ``sinkhorn_blur > 0`` adds ``sinkhorn = dict(blur, iters,
+        scale, sinkhorn, w2, ot, marg_err)``, the debiased entropic transport
+        distance of the same rows after ``sinkhorn_iters`` annealed iterations
+        at that blur, a fraction of the real rows' mean squared distance
+        (models/sinkhorn.py; csrc/kernels/sinkhorn.hip on the hip backend), with
+        ``return_rows`` also ``sinkhorn_pot`` (float32 ``[rows_real + rows_fake,
+        2]``: the pair's and the debiasing potentials). ``gmm_k > 0`` (with ``fit_rows=(X_train, idx_train)``)
         adds ``gmm = dict(k, iters, rows_fit, ll_fit, ll_history, ll_test,
-        lp_test, gap, min_weight, sample_report[, prdc][, swd])``: a
+        lp_test, gap, min_weight, sample_report[, prdc][, swd][, sinkhorn])``: a
         ``gmm_k``-component mixture fitted by ``gmm_iters`` EM iterations to one
         posterior draw per fit row (models/gmm.py; csrc/kernels/gmm.hip on the hip
         backend), the mean log-density of the rows' own codes under it and under
@@ -401,7 +408,8 @@ class SampleEval:
         ``gmm_params``, ``gmm_fake``, ``gmm_fit_z`` and ``gmm_test_z``. That part
         runs on the latent pass's state, so ``latent_buffers()`` raises until the
         next ``evaluate_latent``. Training, eval and iw state are not touched; the
-        result depends on (weights, data, seed, n, directions, mixture) only."""
+        result depends on (weights, data, seed, n, directions, mixture, blur,
+        iterations) only."""
         idx = idx.to(device=self.device, dtype=torch.int64).contiguous()
         na = idx.numel()
         nb = na if n_samples is None else int(n_samples)
@@ -412,6 +420,8 @@ class SampleEval:
             check_prdc_args(na, nb, D, prdc_k)
         if swd_dirs:
             check_swd_args(na, nb, D, swd_dirs)
+        if sinkhorn_blur:
+            check_sinkhorn_args(na, nb, D, sinkhorn_blur, sinkhorn_iters)
         if gmm_k:
             if fit_rows is None:
                 raise ValueError("evaluate_samples(gmm_k=K) fits the mixture to training rows: pass fit_rows=(X, idx)")
@@ -421,13 +431,14 @@ class SampleEval:
         h = bandwidths_of(m)
         z = torch.from_numpy(sample_z(nb, self.Z, self.seed)).to(self.device)
         fake = self.decode(z).to(torch.float32).reshape(nb, -1).contiguous()
-        out = self._sample_tables(real, fake, m, h, prdc_k, swd_dirs, return_rows)
+        sink = (float(sinkhorn_blur), int(sinkhorn_iters)) if sinkhorn_blur else None
+        out = self._sample_tables(real, fake, m, h, prdc_k, swd_dirs, return_rows, sink)
         if gmm_k:
             out.update(self._gmm_report(X, idx, real, nb, m, h, prdc_k, swd_dirs, int(gmm_k), int(gmm_iters), fit_rows,
-                                        return_rows))
+                                        return_rows, sink))
         return out
 
-    def _sample_tables(self, real, fake, m, h, prdc_k, swd_dirs, return_rows) -> dict:
+    def _sample_tables(self, real, fake, m, h, prdc_k, swd_dirs, return_rows, sink=None) -> dict:
         """The tables of ``evaluate_samples`` for ``fake`` against ``real`` and their statistics."""
         (na, D), nb = real.shape, fake.shape[0]
         if self.backend != "hip":
@@ -464,6 +475,19 @@ class SampleEval:
             out["swd"] = swd_stats(stable)
             if return_rows:
                 out.update(swd_table=stable, swd_proj=sproj)
+        if sink:
+            E, T = sink
+            if self.backend != "hip":
+                spot, scale, merr = sinkhorn_rows(real, fake, E, T)
+            else:
+                new = lambda numel, dtype=torch.float32: torch.empty(numel, dtype=dtype, device=self.device)
+                # the three stored cost matrices: 4 (na^2 + na nb + nb^2) bytes (1.2 GB at 20000 rows), for this pass only
+                spot, sout = new((na + nb) * SINKHORN_COLS).view(na + nb, SINKHORN_COLS), new(2, torch.float64)
+                C.sinkhorn_rows(real, fake, E, T, new(C.sinkhorn_ws_numel(na, nb)), spot, sout)
+                scale, merr = sout.cpu()
+            out["sinkhorn"] = sinkhorn_stats(spot, na, scale, merr, E, T)
+            if return_rows:
+                out["sinkhorn_pot"] = spot
         return out
 
     def _gmm_codes(self, X, idx, step: int) -> torch.Tensor:
@@ -479,7 +503,7 @@ class SampleEval:
         self._lat_last = None  # the pass buffer no longer holds an evaluate_latent pass
         return gmm_fit_rows(mulv[:, :Z], mulv[:, Z:], self.seed, step).contiguous()
 
-    def _gmm_report(self, X, idx, real, nb, m, h, prdc_k, swd_dirs, K, iters, fit_rows, return_rows) -> dict:
+    def _gmm_report(self, X, idx, real, nb, m, h, prdc_k, swd_dirs, K, iters, fit_rows, return_rows, sink=None) -> dict:
         zf, zt = self._gmm_codes(fit_rows[0], fit_rows[1], 1), self._gmm_codes(X, idx, 2)
         (nf, Z), nt = zf.shape, zt.shape[0]
         if self.backend != "hip":
@@ -495,8 +519,8 @@ class SampleEval:
             C.gmm_score(zt, params["pi"], params["mu"], params["cov"], new(C.gmm_ws_numel(nt, Z, K)), ll)
         ll_test, lp_test = float(ll.double().mean()), float(prior_score(zt.double()).mean())
         gfake = self.decode(gmm_sample(params, nb, self.seed).to(self.device)).to(torch.float32).reshape(nb, -1).contiguous()
-        rep = self._sample_tables(real, gfake, m, h, prdc_k, swd_dirs, False)
-        extra = {k: rep.pop(k) for k in ("prdc", "swd") if k in rep}
+        rep = self._sample_tables(real, gfake, m, h, prdc_k, swd_dirs, False, sink)
+        extra = {k: rep.pop(k) for k in ("prdc", "swd", "sinkhorn") if k in rep}
         hist = [float(v) for v in hist.double().cpu()]
         gmm = dict(k=K, iters=iters, rows_fit=nf, ll_fit=hist[-1], ll_history=hist, ll_test=ll_test, lp_test=lp_test,
                    gap=ll_test - lp_test, min_weight=float(params["pi"].min()), sample_report=rep, **extra)

@@ -129,6 +129,13 @@ def parse_args(argv=None):
                              "and score N decoded draws from it with the same tables (1 <= K <= 32; 0 = off)")
     parser.add_argument("--gmm-iters", type=int, default=50, metavar="T",
                         help="EM iterations of the --gmm fit (a fixed count, 0 <= T <= 1000)")
+    parser.add_argument("--sinkhorn", type=float, default=0.0, metavar="E",
+                        help="with --sample-report N: also the Sinkhorn divergence (debiased entropic optimal transport) "
+                             "of the same rows at blur E, a fraction of the test rows' mean squared distance: a "
+                             "full-dimensional transport distance in the squared units of the data "
+                             "(2 <= N <= 16384, 0 < E <= 4; 0 = off)")
+    parser.add_argument("--sinkhorn-iters", type=int, default=100, metavar="T",
+                        help="annealed iterations of --sinkhorn (a fixed count, 1 <= T <= 10000)")
     parser.add_argument("--recon-report", action="store_true",
                         help="after each trial's last epoch: per-pixel MSE, PSNR and SSIM (with its luminance and "
                              "contrast-structure factors) of the test images against their reconstructions from the "
@@ -146,6 +153,12 @@ def parse_args(argv=None):
         if args.sample_report == 0:
             raise ValueError("--swd P scores the rows of the sample pass: it needs --sample-report N")
         check_swd_args(args.sample_report, args.sample_report, 1, args.swd)
+    if args.sinkhorn != 0:
+        from multidisttorch_amd.models.sinkhorn import check_sinkhorn_args
+
+        if args.sample_report == 0:
+            raise ValueError("--sinkhorn E scores the rows of the sample pass: it needs --sample-report N")
+        check_sinkhorn_args(args.sample_report, args.sample_report, 1, args.sinkhorn, args.sinkhorn_iters)
     if args.gmm != 0:
         from multidisttorch_amd.models.gmm import check_gmm_args
 
@@ -203,7 +216,8 @@ def main(argv=None):
                       au_threshold=args.au_threshold, binarize=args.binarize,
                       report_objective=objective.reported(specs), sample_report=args.sample_report,
                       prdc_k=args.prdc, recon_report=args.recon_report, swd_dirs=args.swd,
-                      gmm_k=args.gmm, gmm_iters=args.gmm_iters)
+                      gmm_k=args.gmm, gmm_iters=args.gmm_iters, sinkhorn_blur=args.sinkhorn,
+                      sinkhorn_iters=args.sinkhorn_iters)
     results = []
     member = False
     for group_id, group in enumerate(processes_groups):
