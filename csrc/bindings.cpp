@@ -28,6 +28,7 @@ void bind_recon(pybind11::module& m);
 void bind_swd(pybind11::module& m);
 void bind_sinkhorn(pybind11::module& m);
 void bind_gmm(pybind11::module& m);
+void bind_kmeans(pybind11::module& m);
 }  // namespace mdt
 
 PYBIND11_MODULE(_C, m) {
@@ -54,6 +55,7 @@ PYBIND11_MODULE(_C, m) {
   mdt::bind_swd(m);
   mdt::bind_sinkhorn(m);
   mdt::bind_gmm(m);
+  mdt::bind_kmeans(m);
 
   // the trial-state owner of both trainers (runtime/trial_state.h); kLossHist: the length of its loss rings
   m.attr("kLossHist") = (int64_t)mdt::kLossHist;

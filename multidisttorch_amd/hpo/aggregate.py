@@ -16,6 +16,7 @@ SAMPLE_KEYS = ("mmd2", "nn_acc", "nn_acc_real", "nn_acc_fake")
 PRDC_KEYS = ("k", "precision", "recall", "density", "coverage")
 SWD_KEYS = ("dirs", "swd1", "swd1_se", "swd2", "max_w1")
 SINKHORN_KEYS = ("blur", "iters", "scale", "sinkhorn", "w2", "ot", "marg_err")
+NDB_KEYS = ("K", "iters", "ndb", "ndb_over_k", "jsd", "missing", "inertia", "moved")
 GMM_KEYS = ("k", "iters", "rows_fit", "ll_fit", "ll_test", "lp_test", "gap", "min_weight")
 RECON_KEYS = ("mse", "psnr", "ssim", "ssim_l", "ssim_cs", "ssim_min")
 
@@ -36,13 +37,15 @@ def trial_record(result, opts) -> dict:
         rec["gmm"] = result.extra.get("gmm")
     if opts.sinkhorn_blur > 0:
         rec["sinkhorn"] = result.extra.get("sinkhorn")
+    if opts.ndb_k > 0:
+        rec["ndb"] = result.extra.get("ndb")
     return rec
 
 
 def summarize(gathered, specs, opts) -> dict:
     """``gathered``: per rank, the list of its ``trial_record``s (None or empty: an idle rank)."""
     per_trial, wall, failed = {}, 0.0, set()
-    scores = {k: {} for k in SCORES + ("sample_report", "prdc", "recon_report", "swd", "gmm", "sinkhorn")}
+    scores = {k: {} for k in SCORES + ("sample_report", "prdc", "recon_report", "swd", "gmm", "sinkhorn", "ndb")}
     for lst in gathered:
         for r in lst or []:
             gid = r["group_id"]
@@ -114,4 +117,10 @@ def summarize(gathered, specs, opts) -> dict:
         summary["sinkhorn"] = {str(g): {k: (v[k] if k in ("blur", "iters") else float(f"{v[k]:.6g}")) for k in SINKHORN_KEYS}
                                for g, v in sorted(w.items())}
         summary["best_trial_by_sinkhorn"] = min(w, key=lambda g: (w[g]["sinkhorn"], g)) if w else None
+    if opts.ndb_k > 0:
+        # mode coverage on k-means bins of the test rows: the lowest divergence of the two histograms is the best trial
+        w = scores["ndb"]
+        summary["ndb"] = {str(g): {k: (float(f"{v[k]:.6g}") if k in ("ndb_over_k", "jsd", "inertia") else v[k]) for k in NDB_KEYS}
+                          for g, v in sorted(w.items())}
+        summary["best_trial_by_ndb_jsd"] = min(w, key=lambda g: (w[g]["jsd"], g)) if w else None
     return summary

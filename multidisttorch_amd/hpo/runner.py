@@ -89,6 +89,8 @@ class RunOptions:
     gmm_iters: int = 50                    # its EM iterations
     sinkhorn_blur: float = 0.0             # E > 0: the sample pass adds the Sinkhorn divergence at blur E (a fraction of the scale)
     sinkhorn_iters: int = 100              # its annealed iterations
+    ndb_k: int = 0                         # K > 0: the sample pass adds NDB / JSD mode coverage on K k-means bins
+    ndb_iters: int = 20                    # its Lloyd iterations
     sample_report: int = 0                 # N > 0: kernel MMD + 1-NN test of N prior samples against N test rows
 
 
@@ -508,6 +510,10 @@ def _sample_eval(trainer, test, opts: RunOptions, group, metrics, device, tag: s
         E = float(opts.sinkhorn_blur)
         if E > 0:
             kw.update(sinkhorn_blur=E, sinkhorn_iters=int(opts.sinkhorn_iters))
+        B = int(opts.ndb_k)
+        if B > 0:
+            # the starting rows of the bins come from the run seed and the trial: both backends see the same indices
+            kw.update(ndb=B, ndb_iters=int(opts.ndb_iters), ndb_group=int(metrics.group_id))
         r = trainer.evaluate_samples(test.data, idx, n, **kw)
         if device.type == "cuda":
             torch.cuda.synchronize(device)
@@ -531,6 +537,11 @@ def _sample_eval(trainer, test, opts: RunOptions, group, metrics, device, tag: s
         print0(tag + "====> Test set " + sink_line.format(w["blur"], w["sinkhorn"], w["w2"], w["ot"], w["marg_err"], w["iters"]),
                process_group=group)
         out["sinkhorn"] = w
+    ndb_line = "NDB-{}: ndb {} ({:.3f}) JSD {:.4f} missing {} inertia {:.6g} moved {} ({} iters)"
+    ndb_args = lambda w: (w["K"], w["ndb"], w["ndb_over_k"], w["jsd"], w["missing"], w["inertia"], w["moved"], w["iters"])
+    if B > 0:
+        print0(tag + "====> Test set " + ndb_line.format(*ndb_args(r["ndb"])), process_group=group)
+        out["ndb"] = r["ndb"]
     if G > 0:
         g = r["gmm"]
         gs = g["sample_report"]
@@ -549,6 +560,8 @@ def _sample_eval(trainer, test, opts: RunOptions, group, metrics, device, tag: s
             w = g["sinkhorn"]
             print0(tag + "====> Test set " + name + sink_line.format(w["blur"], w["sinkhorn"], w["w2"], w["ot"], w["marg_err"],
                                                                     w["iters"]), process_group=group)
+        if B > 0:
+            print0(tag + "====> Test set " + name + ndb_line.format(*ndb_args(g["ndb"])), process_group=group)
         out["gmm"] = g
     metrics.log(event="sample_eval", **r)
     return out

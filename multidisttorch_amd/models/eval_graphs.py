@@ -30,6 +30,7 @@ from ..ops import native
 from .gmm import check_gmm_args, gmm_fit, gmm_fit_rows, gmm_sample, gmm_score, prior_score
 from .iw import check_iw_args, default_chunk, iw_eps, iw_reduce
 from .latent import check_latent_args, latent_eps, latent_report
+from .ndb import check_ndb_args, kmeans_assign, kmeans_rows, ndb_init_idx, ndb_stats
 from .prdc import COLS as PRDC_COLS, check_prdc_args, prdc_rows, prdc_stats
 from .recon_report import COLS as RECON_COLS, check_recon_args, recon_rows, recon_stats
 from .sample_report import (COLS, bandwidths_of, check_sample_args, mean_pair_d2, sample_rows, sample_stats,
@@ -375,7 +376,8 @@ class SampleEval:
     @torch.no_grad()
     def evaluate_samples(self, X: torch.Tensor, idx: torch.Tensor, n_samples=None, return_rows: bool = False,
                          prdc_k: int = 0, swd_dirs: int = 0, gmm_k: int = 0, gmm_iters: int = 50,
-                         fit_rows=None, sinkhorn_blur: float = 0.0, sinkhorn_iters: int = 100) -> dict:
+                         fit_rows=None, sinkhorn_blur: float = 0.0, sinkhorn_iters: int = 100, ndb: int = 0,
+                         ndb_iters: int = 20, ndb_group: int = 0) -> dict:
         """The sample report of ``n_samples`` decoded prior draws (default: as
         many as rows) against rows ``X[idx]``: ``dict(rows_real, rows_fake,
         mean_pair_d2, bandwidths, mmd2, mmd2_per_bandwidth, nn_acc, nn_acc_real,
@@ -397,9 +399,17 @@ class SampleEval:
         at that blur, a fraction of the real rows' mean squared distance
         (models/sinkhorn.py; csrc/kernels/sinkhorn.hip on the hip backend), with
         ``return_rows`` also ``sinkhorn_pot`` (float32 ``[rows_real + rows_fake,
-        2]``: the pair's and the debiasing potentials). ``gmm_k > 0`` (with ``fit_rows=(X_train, idx_train)``)
+        2]``: the pair's and the debiasing potentials). ``ndb > 0`` adds ``ndb =
+        dict(K, iters, ndb, ndb_over_k, jsd, missing, inertia, moved,
+        counts_real, counts_fake)``: the real rows clustered into that many
+        k-means cells by ``ndb_iters`` Lloyd iterations from rows that the seed
+        and ``ndb_group`` pick, the number of cells whose real and generated
+        shares differ significantly, the Jensen-Shannon divergence of the two
+        histograms and the cells without a generated row (models/ndb.py;
+        csrc/kernels/kmeans.hip on the hip backend), with ``return_rows`` also
+        ``ndb_labels`` (``[rows_real + rows_fake]``) and ``ndb_centroids``. ``gmm_k > 0`` (with ``fit_rows=(X_train, idx_train)``)
         adds ``gmm = dict(k, iters, rows_fit, ll_fit, ll_history, ll_test,
-        lp_test, gap, min_weight, sample_report[, prdc][, swd][, sinkhorn])``: a
+        lp_test, gap, min_weight, sample_report[, prdc][, swd][, sinkhorn][, ndb])``: a
         ``gmm_k``-component mixture fitted by ``gmm_iters`` EM iterations to one
         posterior draw per fit row (models/gmm.py; csrc/kernels/gmm.hip on the hip
         backend), the mean log-density of the rows' own codes under it and under
@@ -422,6 +432,8 @@ class SampleEval:
             check_swd_args(na, nb, D, swd_dirs)
         if sinkhorn_blur:
             check_sinkhorn_args(na, nb, D, sinkhorn_blur, sinkhorn_iters)
+        if ndb:
+            check_ndb_args(na, nb, D, ndb, ndb_iters)
         if gmm_k:
             if fit_rows is None:
                 raise ValueError("evaluate_samples(gmm_k=K) fits the mixture to training rows: pass fit_rows=(X, idx)")
@@ -432,13 +444,15 @@ class SampleEval:
         z = torch.from_numpy(sample_z(nb, self.Z, self.seed)).to(self.device)
         fake = self.decode(z).to(torch.float32).reshape(nb, -1).contiguous()
         sink = (float(sinkhorn_blur), int(sinkhorn_iters)) if sinkhorn_blur else None
-        out = self._sample_tables(real, fake, m, h, prdc_k, swd_dirs, return_rows, sink)
+        # the bins are fitted to the real rows once: the mixture's draws are assigned to the same centroids
+        bins = dict(K=int(ndb), T=int(ndb_iters), init=ndb_init_idx(na, ndb, self.seed, ndb_group)) if ndb else None
+        out = self._sample_tables(real, fake, m, h, prdc_k, swd_dirs, return_rows, sink, bins)
         if gmm_k:
             out.update(self._gmm_report(X, idx, real, nb, m, h, prdc_k, swd_dirs, int(gmm_k), int(gmm_iters), fit_rows,
-                                        return_rows, sink))
+                                        return_rows, sink, bins))
         return out
 
-    def _sample_tables(self, real, fake, m, h, prdc_k, swd_dirs, return_rows, sink=None) -> dict:
+    def _sample_tables(self, real, fake, m, h, prdc_k, swd_dirs, return_rows, sink=None, bins=None) -> dict:
         """The tables of ``evaluate_samples`` for ``fake`` against ``real`` and their statistics."""
         (na, D), nb = real.shape, fake.shape[0]
         if self.backend != "hip":
@@ -488,6 +502,24 @@ class SampleEval:
             out["sinkhorn"] = sinkhorn_stats(spot, na, scale, merr, E, T)
             if return_rows:
                 out["sinkhorn_pot"] = spot
+        if bins:
+            K, T = bins["K"], bins["T"]
+            if self.backend == "hip":
+                ws = torch.empty(C.kmeans_ws_numel(na, nb, D, K), dtype=torch.float32, device=self.device)
+            if "cent" not in bins:
+                init = bins["init"].to(self.device)
+                if self.backend != "hip":
+                    labels, _, cent, moved, inertia = kmeans_rows(real, fake, K, T, init)
+                else:
+                    labels, _, cent, moved, inertia = C.kmeans_rows(real, fake, K, T, init, ws)
+                bins.update(cent=cent, moved=int(moved[-1]), inertia=float(inertia))
+            elif self.backend != "hip":
+                labels = kmeans_assign(torch.cat([real, fake]), bins["cent"])[0]
+            else:
+                labels = C.kmeans_assign(real, fake, bins["cent"], ws)[0]
+            out["ndb"] = ndb_stats(labels, na, K, bins["inertia"], bins["moved"], T)
+            if return_rows:
+                out.update(ndb_labels=labels, ndb_centroids=bins["cent"])
         return out
 
     def _gmm_codes(self, X, idx, step: int) -> torch.Tensor:
@@ -503,7 +535,8 @@ class SampleEval:
         self._lat_last = None  # the pass buffer no longer holds an evaluate_latent pass
         return gmm_fit_rows(mulv[:, :Z], mulv[:, Z:], self.seed, step).contiguous()
 
-    def _gmm_report(self, X, idx, real, nb, m, h, prdc_k, swd_dirs, K, iters, fit_rows, return_rows, sink=None) -> dict:
+    def _gmm_report(self, X, idx, real, nb, m, h, prdc_k, swd_dirs, K, iters, fit_rows, return_rows, sink=None,
+                    bins=None) -> dict:
         zf, zt = self._gmm_codes(fit_rows[0], fit_rows[1], 1), self._gmm_codes(X, idx, 2)
         (nf, Z), nt = zf.shape, zt.shape[0]
         if self.backend != "hip":
@@ -519,8 +552,8 @@ class SampleEval:
             C.gmm_score(zt, params["pi"], params["mu"], params["cov"], new(C.gmm_ws_numel(nt, Z, K)), ll)
         ll_test, lp_test = float(ll.double().mean()), float(prior_score(zt.double()).mean())
         gfake = self.decode(gmm_sample(params, nb, self.seed).to(self.device)).to(torch.float32).reshape(nb, -1).contiguous()
-        rep = self._sample_tables(real, gfake, m, h, prdc_k, swd_dirs, False, sink)
-        extra = {k: rep.pop(k) for k in ("prdc", "swd", "sinkhorn") if k in rep}
+        rep = self._sample_tables(real, gfake, m, h, prdc_k, swd_dirs, False, sink, bins)
+        extra = {k: rep.pop(k) for k in ("prdc", "swd", "sinkhorn", "ndb") if k in rep}
         hist = [float(v) for v in hist.double().cpu()]
         gmm = dict(k=K, iters=iters, rows_fit=nf, ll_fit=hist[-1], ll_history=hist, ll_test=ll_test, lp_test=lp_test,
                    gap=ll_test - lp_test, min_weight=float(params["pi"].min()), sample_report=rep, **extra)

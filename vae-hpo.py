@@ -136,6 +136,13 @@ def parse_args(argv=None):
                              "(2 <= N <= 16384, 0 < E <= 4; 0 = off)")
     parser.add_argument("--sinkhorn-iters", type=int, default=100, metavar="T",
                         help="annealed iterations of --sinkhorn (a fixed count, 1 <= T <= 10000)")
+    parser.add_argument("--ndb", type=int, default=0, metavar="K",
+                        help="with --sample-report N: also which kinds of image are missing: the N test rows are "
+                             "clustered into K k-means bins in pixel space, and the number of bins whose real and "
+                             "generated shares differ significantly (NDB), the Jensen-Shannon divergence of the two "
+                             "histograms and the bins without a generated row are reported (2 <= K <= 256, K <= N; 0 = off)")
+    parser.add_argument("--ndb-iters", type=int, default=20, metavar="T",
+                        help="Lloyd iterations of the --ndb bins (a fixed count, 1 <= T <= 1000)")
     parser.add_argument("--recon-report", action="store_true",
                         help="after each trial's last epoch: per-pixel MSE, PSNR and SSIM (with its luminance and "
                              "contrast-structure factors) of the test images against their reconstructions from the "
@@ -159,6 +166,12 @@ def parse_args(argv=None):
         if args.sample_report == 0:
             raise ValueError("--sinkhorn E scores the rows of the sample pass: it needs --sample-report N")
         check_sinkhorn_args(args.sample_report, args.sample_report, 1, args.sinkhorn, args.sinkhorn_iters)
+    if args.ndb != 0:
+        from multidisttorch_amd.models.ndb import check_ndb_args
+
+        if args.sample_report == 0:
+            raise ValueError("--ndb K bins the rows of the sample pass: it needs --sample-report N")
+        check_ndb_args(args.sample_report, args.sample_report, 1, args.ndb, args.ndb_iters)
     if args.gmm != 0:
         from multidisttorch_amd.models.gmm import check_gmm_args
 
@@ -217,7 +230,7 @@ def main(argv=None):
                       report_objective=objective.reported(specs), sample_report=args.sample_report,
                       prdc_k=args.prdc, recon_report=args.recon_report, swd_dirs=args.swd,
                       gmm_k=args.gmm, gmm_iters=args.gmm_iters, sinkhorn_blur=args.sinkhorn,
-                      sinkhorn_iters=args.sinkhorn_iters)
+                      sinkhorn_iters=args.sinkhorn_iters, ndb_k=args.ndb, ndb_iters=args.ndb_iters)
     results = []
     member = False
     for group_id, group in enumerate(processes_groups):
