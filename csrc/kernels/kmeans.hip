@@ -43,6 +43,7 @@
 // Every sum has one order and no workgroup waits for another: a fit repeats
 // bitwise.
 #include "common.h"
+#include "pair_tile.h"
 #include "kmeans.h"
 
 namespace mdt {
@@ -53,22 +54,6 @@ enum : int { kKmGather = 1, kKmFold = 2, kKmC2 = 4, kKmMoved = 8, kKmInertia = 1
 
 constexpr float kKmInf = __builtin_huge_valf();
 constexpr int kKmNone = 0x7fffffff;
-
-// Four consecutive columns of one row, zero past the row's end (and for a row that does not exist)
-template <bool VEC>
-__device__ __forceinline__ float4 km_load4(const float* p, int k, int D) {
-  float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (p == nullptr) return v;
-  if (VEC) {  // D % 4 == 0 and 16-byte aligned rows: k < D covers all four
-    if (k < D) v = *reinterpret_cast<const float4*>(p + k);
-  } else {
-    if (k < D) v.x = p[k];
-    if (k + 1 < D) v.y = p[k + 1];
-    if (k + 2 < D) v.z = p[k + 2];
-    if (k + 3 < D) v.w = p[k + 3];
-  }
-  return v;
-}
 
 // the better of two (score, cell): the lower score, the lower cell on a tie
 __device__ __forceinline__ void km_better(float& v, int& i, float ov, int oi) {
@@ -119,7 +104,7 @@ __global__ __launch_bounds__(kKmThreads) void kmeans_assign_k(KmeansArgs a, int 
   auto load = [&](int k0) {
 #pragma unroll
     for (int i = 0; i < RT; ++i) {
-      rx[i] = km_load4<VEC>(px[i], k0 + sk, D);
+      rx[i] = pair_load4<VEC>(px[i], k0 + sk, D);
       x2p[i] = fmaf(rx[i].x, rx[i].x, x2p[i]);
       x2p[i] = fmaf(rx[i].y, rx[i].y, x2p[i]);
       x2p[i] = fmaf(rx[i].z, rx[i].z, x2p[i]);
@@ -127,7 +112,7 @@ __global__ __launch_bounds__(kKmThreads) void kmeans_assign_k(KmeansArgs a, int 
     }
 #pragma unroll
     for (int i = 0; i < 8; ++i)
-      if (i < kt) rc[i] = km_load4<VEC>(srow + 32 * i < K ? pc + (size_t)(32 * i) * D : nullptr, k0 + sk, D);
+      if (i < kt) rc[i] = pair_load4<VEC>(srow + 32 * i < K ? pc + (size_t)(32 * i) * D : nullptr, k0 + sk, D);
   };
   auto store = [&](float* dst) {
 #pragma unroll

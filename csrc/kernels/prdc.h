@@ -7,23 +7,21 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "pair_tile.h"  // kPairTile: rows per operand tile
+
 namespace mdt {
 
 constexpr int kPrdcMaxK = 8;       // slots of a row's k-list
 constexpr int kPrdcCols = 3;       // a table row: rad, cnt, dminx
 constexpr int kPrdcMaxRows = 32768;  // per set
 constexpr int kPrdcMaxD = 65536;
-constexpr int kPrdcTile = 128;     // rows per operand tile
-constexpr int kPrdcBK = 32;        // k per LDS chunk
-constexpr int kPrdcLd = kPrdcBK + 4;  // LDS row stride (floats): 16-lane groups of a 16-byte read hit 16 slots
-constexpr int kPrdcThreads = 256;
 constexpr int kPrdcRowThreads = 256;  // the per-row kernels
 constexpr int kPrdcMaxStrips = 64;
 // workgroups the radius kernel's strip count aims at: 4 resident rounds of 2 per CU on 256 CUs
 constexpr int kPrdcBlocks = 2048;
 
 __host__ __device__ inline long long prdc_cdiv(long long a, long long b) { return (a + b - 1) / b; }
-__host__ __device__ inline int prdc_tiles(long long rows) { return (int)prdc_cdiv(rows, kPrdcTile); }
+__host__ __device__ inline int prdc_tiles(long long rows) { return (int)prdc_cdiv(rows, kPairTile); }
 // Strips of a row tile's column tiles: a function of (na, nb) alone, never of the
 // device's load. Strip s of a set of T tiles takes the column tiles
 // [s * per, min(T, (s + 1) * per)) with per = ceil(T / strips); the set with

@@ -1,11 +1,9 @@
 // Precision, recall, density and coverage on k-NN radii (models/prdc.py): the
 // per-row table (rad, cnt, dminx) of real [na, D] against fake [nb, D].
 //
-// d2 = max(0, fma(-2, G, q_i + q_j)) with G a tile of X Y^T on the exact-f32
-// MFMA 32x32x2 (a k-ordered fma chain per element) and q the rows' squared
-// norms: a 128 x 128 tile per 256 threads, 2 x 2 MFMA tiles per wave, K in LDS
-// chunks of 32 with the tail of D zero-filled. The workgroup's own 128 rows are
-// the MFMA's B operand, so an own row sits on a lane (two per lane) and the 32
+// d2 = max(0, fma(-2, G, q_i + q_j)) with G a tile of X Y^T, the exact-f32
+// 128 x 128 Gram tile of pair_tile.h, and q the rows' squared norms. The
+// workgroup's own 128 rows are the MFMA's B operand, so an own row sits on a lane (two per lane) and the 32
 // accumulator registers of a lane are 32 rows of the current column tile.
 //
 //   prdc_norms_k    q[u], one wave per row; clears cnt and sets dminx to +inf.
@@ -35,6 +33,7 @@
 //                   not depend on their order.
 //   prdc_out_k      out[u] = (rad, cnt, dminx) as float32; cnt < 2^15 is exact.
 #include "common.h"
+#include "pair_tile.h"
 #include "prdc.h"
 
 namespace mdt {
@@ -51,90 +50,11 @@ __device__ __forceinline__ const float* prdc_row(const PrdcArgs& a, int u) {
 __global__ __launch_bounds__(kPrdcRowThreads) void prdc_norms_k(PrdcArgs a) {
   const int u = blockIdx.x * (kPrdcRowThreads / kWave) + wave_id();
   if (u >= a.na + a.nb) return;
-  const float* p = prdc_row(a, u);
-  float s = 0.f;
-  for (int k = lane_id(); k < a.D; k += kWave) s = fmaf(p[k], p[k], s);
-  s = wave_sum(s);
+  const float s = pair_row_norm(prdc_row(a, u), a.D);
   if (lane_id() == 0) {
     a.q[u] = s;
     a.cnt[u] = 0;
     a.dminx[u] = kPrdcInfBits;
-  }
-}
-
-// Four consecutive k of one row, zero past the row's end (and for a row past the set's)
-template <bool VEC>
-__device__ __forceinline__ float4 prdc_load4(const float* p, int k, int D) {
-  float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (p == nullptr) return v;
-  if (VEC) {  // D % 4 == 0 and 16-byte aligned rows: k < D covers all four
-    if (k < D) v = *reinterpret_cast<const float4*>(p + k);
-  } else {
-    if (k < D) v.x = p[k];
-    if (k + 1 < D) v.y = p[k + 1];
-    if (k + 2 < D) v.z = p[k + 2];
-    if (k + 3 < D) v.w = p[k + 3];
-  }
-  return v;
-}
-
-// acc = A B^T of the two staged 128-row tiles. pa / pb: this thread's four rows
-// of each (rows srow + 32 i, four k at sk of a chunk), null past the set's end.
-// Enters through a barrier (LDS readers of the previous tile are done) and
-// leaves with the last chunk's fragments read by this wave only.
-template <bool VEC>
-__device__ __forceinline__ void prdc_gram(const float* const (&pa)[4], const float* const (&pb)[4], int D, float* As,
-                                          float* Bs, int tid, f32x16 (&acc)[2][2]) {
-  const int lane = tid & 63, wave = tid >> 6;
-  const int wr = wave >> 1, wc = wave & 1, r = lane & 31, h = lane >> 5;
-  const int srow = tid >> 3, sk = (tid & 7) * 4;
-#pragma unroll
-  for (int m = 0; m < 2; ++m)
-#pragma unroll
-    for (int n = 0; n < 2; ++n)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[m][n][e] = 0.f;
-  float4 ra[4], rb[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    ra[i] = prdc_load4<VEC>(pa[i], sk, D);
-    rb[i] = prdc_load4<VEC>(pb[i], sk, D);
-  }
-  for (int k0 = 0; k0 < D; k0 += kPrdcBK) {
-    __syncthreads();  // the previous chunk's fragments are read
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      *reinterpret_cast<float4*>(As + (srow + 32 * i) * kPrdcLd + sk) = ra[i];
-      *reinterpret_cast<float4*>(Bs + (srow + 32 * i) * kPrdcLd + sk) = rb[i];
-    }
-    __syncthreads();
-    if (k0 + kPrdcBK < D) {  // the next chunk's loads fly under this chunk's MFMAs
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        ra[i] = prdc_load4<VEC>(pa[i], k0 + kPrdcBK + sk, D);
-        rb[i] = prdc_load4<VEC>(pb[i], k0 + kPrdcBK + sk, D);
-      }
-    }
-    // lane half h takes k = 8 c + 4 h + j of the chunk in MFMA step (c, j), from both
-    // operands alike: one 16-byte read feeds four steps
-#pragma unroll
-    for (int c = 0; c < kPrdcBK / 8; ++c) {
-      float4 av[2], bv[2];
-#pragma unroll
-      for (int m = 0; m < 2; ++m)
-        av[m] = *reinterpret_cast<const float4*>(As + (wr * 64 + m * 32 + r) * kPrdcLd + 8 * c + 4 * h);
-#pragma unroll
-      for (int n = 0; n < 2; ++n)
-        bv[n] = *reinterpret_cast<const float4*>(Bs + (wc * 64 + n * 32 + r) * kPrdcLd + 8 * c + 4 * h);
-      const float af[2][4] = {{av[0].x, av[0].y, av[0].z, av[0].w}, {av[1].x, av[1].y, av[1].z, av[1].w}};
-      const float bf[2][4] = {{bv[0].x, bv[0].y, bv[0].z, bv[0].w}, {bv[1].x, bv[1].y, bv[1].z, bv[1].w}};
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int m = 0; m < 2; ++m)
-#pragma unroll
-          for (int n = 0; n < 2; ++n) acc[m][n] = mfma32x32x2(af[m][j], bf[n][j], acc[m][n]);
-    }
   }
 }
 
@@ -174,13 +94,13 @@ __device__ __forceinline__ void prdc_list_store(const PrdcList& l, float* p) {
 }
 
 template <bool VEC>
-__global__ __launch_bounds__(kPrdcThreads, 2) void prdc_radius_k(PrdcArgs a) {
-  // A: the strip's current tile, B: the own tile, [row][kPrdcLd]; qs: norms of A's rows.
+__global__ __launch_bounds__(kPairThreads, 2) void prdc_radius_k(PrdcArgs a) {
+  // A: the strip's current tile, B: the own tile, [row][kPairLd]; qs: norms of A's rows.
   // After the strip the A | B region carries the four lists of every own row.
-  __shared__ __attribute__((aligned(16))) float lds[2 * kPrdcTile * kPrdcLd + kPrdcTile];
+  __shared__ __attribute__((aligned(16))) float lds[2 * kPairTile * kPairLd + kPairTile];
   float* As = lds;
-  float* Bs = lds + kPrdcTile * kPrdcLd;
-  float* qs = lds + 2 * kPrdcTile * kPrdcLd;
+  float* Bs = lds + kPairTile * kPairLd;
+  float* qs = lds + 2 * kPairTile * kPairLd;
 
   const int D = a.D, N = a.na + a.nb;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -190,7 +110,7 @@ __global__ __launch_bounds__(kPrdcThreads, 2) void prdc_radius_k(PrdcArgs a) {
   const bool in_real = (int)blockIdx.x < ta;
   const float* X = in_real ? a.real : a.fake;
   const int ns = in_real ? a.na : a.nb, base = in_real ? 0 : a.na;
-  const int own0 = (in_real ? blockIdx.x : blockIdx.x - ta) * kPrdcTile;
+  const int own0 = (in_real ? blockIdx.x : blockIdx.x - ta) * kPairTile;
   const int tiles = prdc_tiles(ns);
   const int per = (tiles + (int)gridDim.y - 1) / (int)gridDim.y;
   const int c_begin = blockIdx.y * per;
@@ -215,7 +135,7 @@ __global__ __launch_bounds__(kPrdcThreads, 2) void prdc_radius_k(PrdcArgs a) {
   }
 
   for (int ct = c_begin; ct < c_end; ++ct) {
-    const int t0 = ct * kPrdcTile;
+    const int t0 = ct * kPairTile;
     const float* pa[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -223,10 +143,10 @@ __global__ __launch_bounds__(kPrdcThreads, 2) void prdc_radius_k(PrdcArgs a) {
       pa[i] = u < ns ? X + (size_t)u * D : nullptr;
     }
     __syncthreads();  // the previous tile's epilogue has read qs
-    if (tid < kPrdcTile) qs[tid] = t0 + tid < ns ? a.q[base + t0 + tid] : 0.f;
+    if (tid < kPairTile) qs[tid] = t0 + tid < ns ? a.q[base + t0 + tid] : 0.f;
 
     f32x16 acc[2][2];
-    prdc_gram<VEC>(pa, pb, D, As, Bs, tid, acc);
+    pair_gram128<VEC>(pa, pb, D, As, Bs, tid, acc);
 
 #pragma unroll
     for (int m = 0; m < 2; ++m) {
@@ -240,7 +160,7 @@ __global__ __launch_bounds__(kPrdcThreads, 2) void prdc_radius_k(PrdcArgs a) {
           const int t = t0 + tl + e;
 #pragma unroll
           for (int n = 0; n < 2; ++n) {
-            const float d2 = fmaxf(0.f, fmaf(-2.f, acc[m][n][4 * g + e], qo[n] + qt[e]));
+            const float d2 = pair_d2(acc[m][n][4 * g + e], qo[n], qt[e]);
             prdc_list_insert(st[n], t < ns && t != o[n] ? d2 : kPrdcInf);
           }
         }
@@ -250,16 +170,16 @@ __global__ __launch_bounds__(kPrdcThreads, 2) void prdc_radius_k(PrdcArgs a) {
 
   // The four holders of an own row, (wave row, lane half): lists through LDS, merged by one thread per row.
   __syncthreads();  // every wave is done with As and Bs
-  float* red = lds;  // [4][kPrdcTile][kPrdcMaxK]
+  float* red = lds;  // [4][kPairTile][kPrdcMaxK]
 #pragma unroll
   for (int n = 0; n < 2; ++n)
-    prdc_list_store(st[n], red + ((size_t)(wr * 2 + h) * kPrdcTile + wc * 64 + n * 32 + r) * kPrdcMaxK);
+    prdc_list_store(st[n], red + ((size_t)(wr * 2 + h) * kPairTile + wc * 64 + n * 32 + r) * kPrdcMaxK);
   __syncthreads();
-  if (tid < kPrdcTile && own0 + tid < ns) {
+  if (tid < kPairTile && own0 + tid < ns) {
     PrdcList l;
     prdc_list_init(l, a.k);
 #pragma unroll
-    for (int c = 0; c < 4; ++c) prdc_list_merge(l, red + ((size_t)c * kPrdcTile + tid) * kPrdcMaxK, a.k);
+    for (int c = 0; c < 4; ++c) prdc_list_merge(l, red + ((size_t)c * kPairTile + tid) * kPrdcMaxK, a.k);
     prdc_list_store(l, a.lists + ((size_t)blockIdx.y * N + base + own0 + tid) * kPrdcMaxK);
   }
 }
@@ -281,18 +201,18 @@ __device__ __forceinline__ void prdc_min_to(unsigned* p, float d2) {
 }
 
 template <bool VEC>
-__global__ __launch_bounds__(kPrdcThreads, 2) void prdc_member_k(PrdcArgs a) {
+__global__ __launch_bounds__(kPairThreads, 2) void prdc_member_k(PrdcArgs a) {
   // A: the strip's current fake tile, B: the own real tile; qs, rs: norms and radii of A's rows
-  __shared__ __attribute__((aligned(16))) float lds[2 * kPrdcTile * kPrdcLd + 2 * kPrdcTile];
+  __shared__ __attribute__((aligned(16))) float lds[2 * kPairTile * kPairLd + 2 * kPairTile];
   float* As = lds;
-  float* Bs = lds + kPrdcTile * kPrdcLd;
-  float* qs = lds + 2 * kPrdcTile * kPrdcLd;
-  float* rs = qs + kPrdcTile;
+  float* Bs = lds + kPairTile * kPairLd;
+  float* qs = lds + 2 * kPairTile * kPairLd;
+  float* rs = qs + kPairTile;
 
   const int D = a.D, na = a.na, nb = a.nb;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wr = wave >> 1, wc = wave & 1, r = lane & 31, h = lane >> 5;
-  const int own0 = blockIdx.x * kPrdcTile;
+  const int own0 = blockIdx.x * kPairTile;
   const int tiles = prdc_tiles(nb);
   const int per = (tiles + (int)gridDim.y - 1) / (int)gridDim.y;
   const int c_begin = blockIdx.y * per;
@@ -320,7 +240,7 @@ __global__ __launch_bounds__(kPrdcThreads, 2) void prdc_member_k(PrdcArgs a) {
   }
 
   for (int ct = c_begin; ct < c_end; ++ct) {
-    const int t0 = ct * kPrdcTile;
+    const int t0 = ct * kPairTile;
     const float* pa[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -328,14 +248,14 @@ __global__ __launch_bounds__(kPrdcThreads, 2) void prdc_member_k(PrdcArgs a) {
       pa[i] = u < nb ? a.fake + (size_t)u * D : nullptr;
     }
     __syncthreads();  // the previous tile's epilogue has read qs and rs
-    if (tid < kPrdcTile) {
+    if (tid < kPairTile) {
       const bool v = t0 + tid < nb;
       qs[tid] = v ? a.q[na + t0 + tid] : 0.f;
       rs[tid] = v ? a.rad[na + t0 + tid] : 0.f;
     }
 
     f32x16 acc[2][2];
-    prdc_gram<VEC>(pa, pb, D, As, Bs, tid, acc);
+    pair_gram128<VEC>(pa, pb, D, As, Bs, tid, acc);
 
     float mv[32];  // per accumulator slot 16 m + reg: the nearest of this lane's two real rows
     int keepc = 0;
@@ -355,7 +275,7 @@ __global__ __launch_bounds__(kPrdcThreads, 2) void prdc_member_k(PrdcArgs a) {
           int c_lo = 0, c_hi = 0;
 #pragma unroll
           for (int n = 0; n < 2; ++n) {
-            d[n] = fmaxf(0.f, fmaf(-2.f, acc[m][n][4 * g + e], qo[n] + qt[e]));
+            d[n] = pair_d2(acc[m][n][4 * g + e], qo[n], qt[e]);
             // the real row on the lane against the fake row's radius
             cnt_o[n] += vt && d[n] <= rt[e] ? 1 : 0;
             dmin_o[n] = fminf(dmin_o[n], vt ? d[n] : kPrdcInf);
@@ -433,7 +353,7 @@ extern "C" int mdt_prdc_rows(const mdt::PrdcArgs* a, hipStream_t s) {
   if (rc) return rc;
   const int N = a->na + a->nb;
   const int ta = prdc_tiles(a->na), tb = prdc_tiles(a->nb);
-  const dim3 rows((unsigned)prdc_cdiv(N, kPrdcRowThreads)), tile(kPrdcThreads);
+  const dim3 rows((unsigned)prdc_cdiv(N, kPrdcRowThreads)), tile(kPairThreads);
   hipLaunchKernelGGL(prdc_norms_k, dim3((unsigned)prdc_cdiv(N, kPrdcRowThreads / kWave)), dim3(kPrdcRowThreads), 0, s, *a);
   const bool vec = a->D % 4 == 0 && (reinterpret_cast<uintptr_t>(a->real) & 15) == 0 &&
                    (reinterpret_cast<uintptr_t>(a->fake) & 15) == 0;

@@ -7,6 +7,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "pair_tile.h"
+
 namespace mdt {
 
 constexpr int kSkCols = 2;          // a table row: the pair's potential, the debiasing potential
@@ -14,12 +16,9 @@ constexpr int kSkMaxRows = 16384;   // per set: the cost matrices are stored (3.
 constexpr int kSkMaxD = 65536;
 constexpr int kSkMaxIters = 10000;
 constexpr double kSkMaxBlur = 4.0;
-// cost kernel: a 128 x 128 tile per workgroup, 2 x 2 MFMA tiles per wave, K in LDS chunks
-constexpr int kSkTile = 128;
-constexpr int kSkBK = 32;
-constexpr int kSkLd = kSkBK + 4;    // LDS row stride (floats): 16-lane groups of a 16-byte read hit 16 slots
+// cost kernel: one kPairTile x kPairTile tile of pair_tile.h per workgroup
 constexpr int kSkTLd = 64 + 4;      // the transposing store's row stride: a wave's 32 columns of 64 rows
-constexpr int kSkThreads = 256;
+constexpr int kSkThreads = 256;     // every other kernel
 // iteration kernel: a wave keeps kSkWaveRows rows' running (max, sum) in registers, a workgroup's four waves
 // own a band of kSkBand rows and walk its columns together, 256 per step (a 16-byte load per lane and row)
 constexpr int kSkWaveRows = 16;
@@ -51,7 +50,7 @@ struct SkLayout {
 __host__ __device__ inline SkLayout sk_layout(int na, int nb) {
   SkLayout L;
   L.lda = sk_pad4(na); L.ldb = sk_pad4(nb);
-  L.ta = sk_cdiv(na, kSkTile); L.tb = sk_cdiv(nb, kSkTile);
+  L.ta = sk_cdiv(na, kPairTile); L.tb = sk_cdiv(nb, kPairTile);
   L.bands_a = sk_cdiv(na, kSkBand); L.bands_b = sk_cdiv(nb, kSkBand);
   size_t o = 0;
   L.cxy = o; o += (size_t)na * L.ldb;

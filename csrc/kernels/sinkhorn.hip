@@ -5,12 +5,9 @@
 //
 // Cost phase, three launches:
 //   sk_norms_k   n[u] of real | fake, one wave per row.
-//   sk_cost_k    one workgroup per 128 x 128 tile of one matrix: the Gram tile on
-//                the exact-f32 MFMA 32x32x2 (a k-ordered fma chain per element,
-//                so inputs whose products and partial sums are exact give exact
-//                costs), 2 x 2 MFMA tiles per wave, K in LDS chunks of 32 with
-//                the tail of D zero-filled and the next chunk's global loads in
-//                flight under the current chunk's MFMAs; C = max(n_i + n_j - 2 G,
+//   sk_cost_k    one workgroup per 128 x 128 tile of one matrix: the exact-f32
+//                Gram tile of pair_tile.h (inputs whose products and partial
+//                sums are exact give exact costs); C = max(n_i + n_j - 2 G,
 //                0). Of Cxx and Cyy only the tiles on or above the diagonal are
 //                computed (the workgroups below it leave at once). Such a tile
 //                is stored as it is, the diagonal as exact 0, and, off the
@@ -48,6 +45,7 @@
 // repeat bitwise. Masked elements are selected away, never multiplied away, so
 // the padding of a row or vector may hold anything.
 #include "common.h"
+#include "pair_tile.h"
 #include "sinkhorn.h"
 
 #include <cmath>
@@ -63,37 +61,18 @@ __global__ __launch_bounds__(kSkThreads) void sk_norms_k(SinkhornArgs a) {
   const SkLayout L = sk_layout(a.na, a.nb);
   const int u = blockIdx.x * (kSkThreads / kWave) + wave_id();
   if (u >= a.na + a.nb) return;
-  const float* p = u < a.na ? a.real + (size_t)u * a.D : a.fake + (size_t)(u - a.na) * a.D;
-  float s = 0.f;
-  for (int k = lane_id(); k < a.D; k += kWave) s = fmaf(p[k], p[k], s);
-  s = wave_sum(s);
+  const float s = pair_row_norm(u < a.na ? a.real + (size_t)u * a.D : a.fake + (size_t)(u - a.na) * a.D, a.D);
   if (lane_id() == 0) a.ws[L.norms + (u < a.na ? u : L.lda + (u - a.na))] = s;
 }
 
-// Four consecutive k of one row, zero past the row's end (and for a row past the operand's)
 template <bool VEC>
-__device__ __forceinline__ float4 sk_load4(const float* p, int k, int D) {
-  float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (p == nullptr) return v;
-  if (VEC) {  // D % 4 == 0 and 16-byte aligned rows: k < D covers all four
-    if (k < D) v = *reinterpret_cast<const float4*>(p + k);
-  } else {
-    if (k < D) v.x = p[k];
-    if (k + 1 < D) v.y = p[k + 1];
-    if (k + 2 < D) v.z = p[k + 2];
-    if (k + 3 < D) v.w = p[k + 3];
-  }
-  return v;
-}
-
-template <bool VEC>
-__global__ __launch_bounds__(kSkThreads, 2) void sk_cost_k(SinkhornArgs a) {
-  // A: the tile's rows, B: its columns, [row][kSkLd]; afterwards a wave's [32][kSkTLd] transposing buffer
-  __shared__ __attribute__((aligned(16))) float lds[2 * kSkTile * kSkLd];
-  __shared__ double red[kSkThreads / kWave];
-  static_assert(4 * 32 * kSkTLd <= 2 * kSkTile * kSkLd, "the transposing buffers fit the operand tiles");
+__global__ __launch_bounds__(kPairThreads, 2) void sk_cost_k(SinkhornArgs a) {
+  // A: the tile's rows, B: its columns, [row][kPairLd]; afterwards a wave's [32][kSkTLd] transposing buffer
+  __shared__ __attribute__((aligned(16))) float lds[2 * kPairTile * kPairLd];
+  __shared__ double red[kPairThreads / kWave];
+  static_assert(4 * 32 * kSkTLd <= 2 * kPairTile * kPairLd, "the transposing buffers fit the operand tiles");
   float* As = lds;
-  float* Bs = lds + kSkTile * kSkLd;
+  float* Bs = lds + kPairTile * kPairLd;
 
   const SkLayout L = sk_layout(a.na, a.nb);
   int b = blockIdx.x, prob, ti, tj;
@@ -117,10 +96,9 @@ __global__ __launch_bounds__(kSkThreads, 2) void sk_cost_k(SinkhornArgs a) {
   const int D = a.D;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wr = wave >> 1, wc = wave & 1, r = lane & 31, h = lane >> 5;
-  const int i0 = ti * kSkTile, j0 = tj * kSkTile;
+  const int i0 = ti * kPairTile, j0 = tj * kPairTile;
 
-  // staging: thread -> rows srow + 32 i (i < 4), four k at sk of the chunk
-  const int srow = tid >> 3, sk = (tid & 7) * 4;
+  const int srow = tid >> 3;  // staging: thread -> rows srow + 32 i (i < 4) of each operand tile
   const float* pa[4];
   const float* pb[4];
 #pragma unroll
@@ -131,54 +109,7 @@ __global__ __launch_bounds__(kSkThreads, 2) void sk_cost_k(SinkhornArgs a) {
   }
 
   f32x16 acc[2][2];
-#pragma unroll
-  for (int m = 0; m < 2; ++m)
-#pragma unroll
-    for (int n = 0; n < 2; ++n)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[m][n][e] = 0.f;
-
-  float4 ra[4], rb[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    ra[i] = sk_load4<VEC>(pa[i], sk, D);
-    rb[i] = sk_load4<VEC>(pb[i], sk, D);
-  }
-  for (int k0 = 0; k0 < D; k0 += kSkBK) {
-    __syncthreads();  // the previous chunk's fragments are read
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      *reinterpret_cast<float4*>(As + (srow + 32 * i) * kSkLd + sk) = ra[i];
-      *reinterpret_cast<float4*>(Bs + (srow + 32 * i) * kSkLd + sk) = rb[i];
-    }
-    __syncthreads();
-    if (k0 + kSkBK < D) {  // the next chunk's loads fly under this chunk's MFMAs
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        ra[i] = sk_load4<VEC>(pa[i], k0 + kSkBK + sk, D);
-        rb[i] = sk_load4<VEC>(pb[i], k0 + kSkBK + sk, D);
-      }
-    }
-    // lane half h takes k = 8 c + 4 h + j of the chunk in MFMA step (c, j), from both operands alike
-#pragma unroll
-    for (int c = 0; c < kSkBK / 8; ++c) {
-      float4 av[2], bv[2];
-#pragma unroll
-      for (int m = 0; m < 2; ++m)
-        av[m] = *reinterpret_cast<const float4*>(As + (wr * 64 + m * 32 + r) * kSkLd + 8 * c + 4 * h);
-#pragma unroll
-      for (int n = 0; n < 2; ++n)
-        bv[n] = *reinterpret_cast<const float4*>(Bs + (wc * 64 + n * 32 + r) * kSkLd + 8 * c + 4 * h);
-      const float af[2][4] = {{av[0].x, av[0].y, av[0].z, av[0].w}, {av[1].x, av[1].y, av[1].z, av[1].w}};
-      const float bf[2][4] = {{bv[0].x, bv[0].y, bv[0].z, bv[0].w}, {bv[1].x, bv[1].y, bv[1].z, bv[1].w}};
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int m = 0; m < 2; ++m)
-#pragma unroll
-          for (int n = 0; n < 2; ++n) acc[m][n] = mfma32x32x2(af[m][j], bf[n][j], acc[m][n]);
-    }
-  }
+  pair_gram128<VEC>(pa, pb, D, As, Bs, tid, acc);
 
   // accumulator register reg of lane (r, h): row 32 m + (reg & 3) + 8 (reg >> 2) + 4 h of the wave's 64, column
   // 32 n + r. The cost takes the register's place; a half wave stores 32 consecutive floats.
@@ -193,7 +124,7 @@ __global__ __launch_bounds__(kSkThreads, 2) void sk_cost_k(SinkhornArgs a) {
       for (int reg = 0; reg < 16; ++reg) {
         const int i = i0 + wr * 64 + m * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * h;
         const float qi = i < nX ? qX[i] : 0.f;
-        float c = fmaxf(0.f, fmaf(-2.f, acc[m][n][reg], qi + qj));
+        float c = pair_d2(acc[m][n][reg], qi, qj);
         if (prob != 0 && i == j) c = 0.f;
         acc[m][n][reg] = c;
         if (i < nX && j < nY) {
@@ -476,8 +407,8 @@ extern "C" int mdt_sinkhorn_cost(const mdt::SinkhornArgs* a, hipStream_t s) {
   hipLaunchKernelGGL(sk_norms_k, dim3((unsigned)sk_cdiv(a->na + a->nb, kSkThreads / kWave)), dim3(kSkThreads), 0, s, *a);
   const bool vec = a->D % 4 == 0 && ((reinterpret_cast<uintptr_t>(a->real) | reinterpret_cast<uintptr_t>(a->fake)) & 15) == 0;
   const dim3 grid((unsigned)(L.ta * L.tb + L.ta * L.ta + L.tb * L.tb));
-  if (vec) hipLaunchKernelGGL(sk_cost_k<true>, grid, dim3(kSkThreads), 0, s, *a);
-  else hipLaunchKernelGGL(sk_cost_k<false>, grid, dim3(kSkThreads), 0, s, *a);
+  if (vec) hipLaunchKernelGGL(sk_cost_k<true>, grid, dim3(kPairThreads), 0, s, *a);
+  else hipLaunchKernelGGL(sk_cost_k<false>, grid, dim3(kPairThreads), 0, s, *a);
   hipLaunchKernelGGL(sk_scale_k, dim3(1), dim3(kSkThreads), 0, s, *a);
   return hipGetLastError() == hipSuccess ? 0 : 9;
 }

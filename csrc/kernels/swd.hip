@@ -33,6 +33,7 @@
 //                   fixed-order wave and workgroup reduction ends in one
 //                   division by na nb. No atomics: calls repeat bitwise.
 #include "common.h"
+#include "pair_tile.h"
 #include "swd.h"
 
 namespace mdt {
@@ -40,22 +41,6 @@ namespace mdt {
 namespace {
 
 constexpr float kSwdInf = __builtin_huge_valf();
-
-// Four consecutive k of one row, zero past the row's end (and for a row past the operand's)
-template <bool VEC>
-__device__ __forceinline__ float4 swd_load4(const float* p, int k, int D) {
-  float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (p == nullptr) return v;
-  if (VEC) {  // D % 4 == 0 and 16-byte aligned rows: k < D covers all four
-    if (k < D) v = *reinterpret_cast<const float4*>(p + k);
-  } else {
-    if (k < D) v.x = p[k];
-    if (k + 1 < D) v.y = p[k + 1];
-    if (k + 2 < D) v.z = p[k + 2];
-    if (k + 3 < D) v.w = p[k + 3];
-  }
-  return v;
-}
 
 template <bool VEC>
 __global__ __launch_bounds__(kSwdThreads, 2) void swd_project_k(SwdArgs a) {
@@ -91,9 +76,9 @@ __global__ __launch_bounds__(kSwdThreads, 2) void swd_project_k(SwdArgs a) {
     for (int e = 0; e < 16; ++e) acc[m][e] = 0.f;
   float4 ra[4], rb[2];
 #pragma unroll
-  for (int i = 0; i < 4; ++i) ra[i] = swd_load4<VEC>(pa[i], sk, D);
+  for (int i = 0; i < 4; ++i) ra[i] = pair_load4<VEC>(pa[i], sk, D);
 #pragma unroll
-  for (int i = 0; i < 2; ++i) rb[i] = swd_load4<VEC>(pb[i], sk, D);
+  for (int i = 0; i < 2; ++i) rb[i] = pair_load4<VEC>(pb[i], sk, D);
 
   for (int k0 = 0; k0 < D; k0 += kSwdBK) {
     __syncthreads();  // the previous chunk's fragments are read
@@ -104,9 +89,9 @@ __global__ __launch_bounds__(kSwdThreads, 2) void swd_project_k(SwdArgs a) {
     __syncthreads();
     if (k0 + kSwdBK < D) {  // the next chunk's loads fly under this chunk's MFMAs
 #pragma unroll
-      for (int i = 0; i < 4; ++i) ra[i] = swd_load4<VEC>(pa[i], k0 + kSwdBK + sk, D);
+      for (int i = 0; i < 4; ++i) ra[i] = pair_load4<VEC>(pa[i], k0 + kSwdBK + sk, D);
 #pragma unroll
-      for (int i = 0; i < 2; ++i) rb[i] = swd_load4<VEC>(pb[i], k0 + kSwdBK + sk, D);
+      for (int i = 0; i < 2; ++i) rb[i] = pair_load4<VEC>(pb[i], k0 + kSwdBK + sk, D);
     }
     // lane half h takes k = 8 c + 4 h + j of the chunk in MFMA step (c, j), from both operands alike
 #pragma unroll

@@ -6,16 +6,14 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "pair_tile.h"  // kPairTile: union rows per operand tile of the pair kernel
+
 namespace mdt {
 
 constexpr int kTsBandwidths = 3;
 constexpr int kTsCols = 2 + 2 * kTsBandwidths;  // dmin_r, dmin_f, ksum_r[3], ksum_f[3]
 constexpr int kTsMaxRows = 32768;               // per set
 constexpr int kTsMaxD = 65536;
-constexpr int kTsTile = 128;                    // union rows per operand tile of the pair kernel
-constexpr int kTsBK = 32;                       // k per LDS chunk
-constexpr int kTsLd = kTsBK + 4;                // LDS row stride (floats): 16-lane groups of a 16-byte read hit 16 slots
-constexpr int kTsThreads = 256;
 constexpr int kTsNormThreads = 256;             // one wave per row
 constexpr int kTsFoldThreads = 256;
 constexpr int kTsMaxStrips = 64;
@@ -29,7 +27,7 @@ __host__ __device__ inline long long ts_cdiv(long long a, long long b) { return 
 // rows of J (at 2 d = T both workgroups meet the pair and each keeps its own
 // rows). ts_offsets: the offsets of a row tile; ts_toffsets: those it also
 // reduces the other way, one partial per (offset, row).
-__host__ __device__ inline int ts_tiles(long long rows) { return (int)ts_cdiv(rows, kTsTile); }
+__host__ __device__ inline int ts_tiles(long long rows) { return (int)ts_cdiv(rows, kPairTile); }
 __host__ __device__ inline int ts_offsets(long long rows) { return ts_tiles(rows) / 2 + 1; }
 __host__ __device__ inline int ts_toffsets(long long rows) { return (ts_tiles(rows) - 1) / 2; }
 // Strips of a row tile's offsets: a function of the union's rows alone (never

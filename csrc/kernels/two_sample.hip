@@ -8,9 +8,7 @@
 //
 //   ts_norms_k  q[i], one wave per row.
 //   ts_pair_k   one workgroup per (row tile, strip of column tiles). G comes from the
-//               exact-f32 MFMA 32x32x2 (a k-ordered fma chain per element): a
-//               128 x 128 tile per 256 threads, 2 x 2 MFMA tiles per wave, K in
-//               LDS chunks of 32 with the tail of D zero-filled. Both operands
+//               exact-f32 128 x 128 Gram tile of pair_tile.h. Both operands
 //               are tiles of U, read in place through the two base pointers.
 //               The workgroup's own 128 rows are the MFMA's B operand, so an
 //               own row sits on a lane (two per lane) with its two minima and
@@ -31,6 +29,7 @@
 // No atomics and a strip count that depends on na + nb alone: results repeat
 // bitwise. The (na + nb)^2 matrix never exists.
 #include "common.h"
+#include "pair_tile.h"
 #include "two_sample.h"
 
 namespace mdt {
@@ -46,27 +45,8 @@ __device__ __forceinline__ const float* ts_row(const TwoSampleArgs& a, int u) {
 __global__ __launch_bounds__(kTsNormThreads) void ts_norms_k(TwoSampleArgs a) {
   const int u = blockIdx.x * (kTsNormThreads / kWave) + wave_id();
   if (u >= a.na + a.nb) return;
-  const float* p = ts_row(a, u);
-  float s = 0.f;
-  for (int k = lane_id(); k < a.D; k += kWave) s = fmaf(p[k], p[k], s);
-  s = wave_sum(s);
+  const float s = pair_row_norm(ts_row(a, u), a.D);
   if (lane_id() == 0) a.q[u] = s;
-}
-
-// Four consecutive k of one row, zero past the row's end (and for a row past the union's)
-template <bool VEC>
-__device__ __forceinline__ float4 ts_load4(const float* p, int k, int D) {
-  float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (p == nullptr) return v;
-  if (VEC) {  // D % 4 == 0 and 16-byte aligned rows: k < D covers all four
-    if (k < D) v = *reinterpret_cast<const float4*>(p + k);
-  } else {
-    if (k < D) v.x = p[k];
-    if (k + 1 < D) v.y = p[k + 1];
-    if (k + 2 < D) v.z = p[k + 2];
-    if (k + 3 < D) v.w = p[k + 3];
-  }
-  return v;
 }
 
 // The running state of one own row
@@ -112,7 +92,7 @@ __device__ __forceinline__ void ts_epilogue(const TwoSampleArgs& a, const f32x16
         for (int s = 0; s < kTsBandwidths; ++s) row.ksum[0][s] = row.ksum[1][s] = 0.f;
 #pragma unroll
         for (int n = 0; n < 2; ++n) {
-          const float d2 = fmaxf(0.f, fmaf(-2.f, acc[m][n][4 * g + e], qo[n] + qt[e]));
+          const float d2 = pair_d2(acc[m][n][4 * g + e], qo[n], qt[e]);
           float k[kTsBandwidths];
 #pragma unroll
           for (int s = 0; s < kTsBandwidths; ++s) k[s] = ts_kernel_value(d2, a.c_hi[s], a.c_lo[s]);
@@ -163,27 +143,26 @@ __device__ __forceinline__ void ts_epilogue(const TwoSampleArgs& a, const f32x16
 }
 
 template <bool VEC>
-__global__ __launch_bounds__(kTsThreads, 2) void ts_pair_k(TwoSampleArgs a) {
-  // A: the strip's current tile, B: the own tile, [row][kTsLd]; qs: norms of A's rows;
+__global__ __launch_bounds__(kPairThreads, 2) void ts_pair_k(TwoSampleArgs a) {
+  // A: the strip's current tile, B: the own tile, [row][kPairLd]; qs: norms of A's rows;
   // tr: per wave column, A's rows reduced over that wave's own rows.
   // After the strip the A region carries the cross-wave combine of the own rows.
-  __shared__ __attribute__((aligned(16))) float lds[2 * kTsTile * kTsLd + kTsTile + 2 * kTsTile * kTsCols];
+  __shared__ __attribute__((aligned(16))) float lds[2 * kPairTile * kPairLd + kPairTile + 2 * kPairTile * kTsCols];
   float* As = lds;
-  float* Bs = lds + kTsTile * kTsLd;
-  float* qs = lds + 2 * kTsTile * kTsLd;
-  float* tr = qs + kTsTile;
+  float* Bs = lds + kPairTile * kPairLd;
+  float* qs = lds + 2 * kPairTile * kPairLd;
+  float* tr = qs + kPairTile;
 
   const int N = a.na + a.nb, D = a.D;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wr = wave >> 1, wc = wave & 1, r = lane & 31, h = lane >> 5;
-  const int own0 = blockIdx.x * kTsTile;
-  const int tiles = (N + kTsTile - 1) / kTsTile, offs = tiles / 2 + 1;
+  const int own0 = blockIdx.x * kPairTile;
+  const int tiles = (N + kPairTile - 1) / kPairTile, offs = tiles / 2 + 1;
   const int per = (offs + (int)gridDim.y - 1) / (int)gridDim.y;
   const int d_begin = blockIdx.y * per;
   const int d_end = min(offs, d_begin + per);
 
-  // staging: thread -> rows srow + 32 i (i < 4), four k at sk of the chunk
-  const int srow = tid >> 3, sk = (tid & 7) * 4;
+  const int srow = tid >> 3;  // staging: thread -> rows srow + 32 i (i < 4) of each operand tile
   const float* pb[4];
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
@@ -205,7 +184,7 @@ __global__ __launch_bounds__(kTsThreads, 2) void ts_pair_k(TwoSampleArgs a) {
 
   for (int d = d_begin; d < d_end; ++d) {
     const int ct = blockIdx.x + d < tiles ? blockIdx.x + d : blockIdx.x + d - tiles;
-    const int t0 = ct * kTsTile;
+    const int t0 = ct * kPairTile;
     const bool trans = d >= 1 && 2 * d < tiles;  // the tile serves the rows of tile ct as well
     const float* pa[4];
 #pragma unroll
@@ -214,58 +193,10 @@ __global__ __launch_bounds__(kTsThreads, 2) void ts_pair_k(TwoSampleArgs a) {
       pa[i] = u < N ? ts_row(a, u) : nullptr;
     }
     __syncthreads();  // the previous tile's epilogue has read qs
-    if (tid < kTsTile) qs[tid] = t0 + tid < N ? a.q[t0 + tid] : 0.f;
+    if (tid < kPairTile) qs[tid] = t0 + tid < N ? a.q[t0 + tid] : 0.f;
 
     f32x16 acc[2][2];
-#pragma unroll
-    for (int m = 0; m < 2; ++m)
-#pragma unroll
-      for (int n = 0; n < 2; ++n)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[m][n][e] = 0.f;
-
-    float4 ra[4], rb[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      ra[i] = ts_load4<VEC>(pa[i], sk, D);
-      rb[i] = ts_load4<VEC>(pb[i], sk, D);
-    }
-    for (int k0 = 0; k0 < D; k0 += kTsBK) {
-      __syncthreads();  // the previous chunk's fragments are read
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        *reinterpret_cast<float4*>(As + (srow + 32 * i) * kTsLd + sk) = ra[i];
-        *reinterpret_cast<float4*>(Bs + (srow + 32 * i) * kTsLd + sk) = rb[i];
-      }
-      __syncthreads();
-      if (k0 + kTsBK < D) {  // the next chunk's loads fly under this chunk's MFMAs
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          ra[i] = ts_load4<VEC>(pa[i], k0 + kTsBK + sk, D);
-          rb[i] = ts_load4<VEC>(pb[i], k0 + kTsBK + sk, D);
-        }
-      }
-      // lane half h takes k = 8 c + 4 h + j of the chunk in MFMA step (c, j), from both
-      // operands alike: one 16-byte read feeds four steps
-#pragma unroll
-      for (int c = 0; c < kTsBK / 8; ++c) {
-        float4 av[2], bv[2];
-#pragma unroll
-        for (int m = 0; m < 2; ++m)
-          av[m] = *reinterpret_cast<const float4*>(As + (wr * 64 + m * 32 + r) * kTsLd + 8 * c + 4 * h);
-#pragma unroll
-        for (int n = 0; n < 2; ++n)
-          bv[n] = *reinterpret_cast<const float4*>(Bs + (wc * 64 + n * 32 + r) * kTsLd + 8 * c + 4 * h);
-        const float af[2][4] = {{av[0].x, av[0].y, av[0].z, av[0].w}, {av[1].x, av[1].y, av[1].z, av[1].w}};
-        const float bf[2][4] = {{bv[0].x, bv[0].y, bv[0].z, bv[0].w}, {bv[1].x, bv[1].y, bv[1].z, bv[1].w}};
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-          for (int m = 0; m < 2; ++m)
-#pragma unroll
-            for (int n = 0; n < 2; ++n) acc[m][n] = mfma32x32x2(af[m][j], bf[n][j], acc[m][n]);
-      }
-    }
+    pair_gram128<VEC>(pa, pb, D, As, Bs, tid, acc);
 
     TsRow keep;
     if (!trans) {
@@ -278,14 +209,14 @@ __global__ __launch_bounds__(kTsThreads, 2) void ts_pair_k(TwoSampleArgs a) {
     ts_epilogue<true>(a, acc, qs, t0, wr, h, r, o, qo, st, keep);
     {  // lane (r, h) holds row (r >> 4) * 32 + rowmap(r & 15, h) of its wave's 64: through LDS to the other wave column
       const int tl = wr * 64 + (r >> 4) * 32 + 8 * ((r & 15) >> 2) + 4 * h + (r & 3);
-      float4* p = reinterpret_cast<float4*>(tr + (wc * kTsTile + tl) * kTsCols);
+      float4* p = reinterpret_cast<float4*>(tr + (wc * kPairTile + tl) * kTsCols);
       p[0] = make_float4(keep.dmin[0], keep.dmin[1], keep.ksum[0][0], keep.ksum[0][1]);
       p[1] = make_float4(keep.ksum[0][2], keep.ksum[1][0], keep.ksum[1][1], keep.ksum[1][2]);
     }
     __syncthreads();  // the next write of tr follows the next tile's k loop and its barriers
-    if (tid < kTsTile && t0 + tid < N) {
+    if (tid < kPairTile && t0 + tid < N) {
       const float4* p0 = reinterpret_cast<const float4*>(tr + tid * kTsCols);
-      const float4* p1 = reinterpret_cast<const float4*>(tr + (kTsTile + tid) * kTsCols);
+      const float4* p1 = reinterpret_cast<const float4*>(tr + (kPairTile + tid) * kTsCols);
       const float4 x0 = p0[0], x1 = p0[1], y0 = p1[0], y1 = p1[1];
       float4* dst = reinterpret_cast<float4*>(a.tpart + ((size_t)(d - 1) * N + t0 + tid) * kTsCols);
       dst[0] = make_float4(fminf(x0.x, y0.x), fminf(x0.y, y0.y), x0.z + y0.z, x0.w + y0.w);
@@ -304,7 +235,7 @@ __global__ __launch_bounds__(kTsThreads, 2) void ts_pair_k(TwoSampleArgs a) {
     }
   }
   __syncthreads();  // every wave is done with As
-  float* red = As;  // [kTsTile][kTsCols]
+  float* red = As;  // [kPairTile][kTsCols]
   if (wr == 1 && h == 0) {
 #pragma unroll
     for (int n = 0; n < 2; ++n) {
@@ -390,8 +321,8 @@ extern "C" int mdt_two_sample_rows(const mdt::TwoSampleArgs* a, hipStream_t s) {
   const bool vec = a->D % 4 == 0 && (reinterpret_cast<uintptr_t>(a->real) & 15) == 0 &&
                    (reinterpret_cast<uintptr_t>(a->fake) & 15) == 0;
   const dim3 grid((unsigned)tiles, (unsigned)a->strips);
-  if (vec) hipLaunchKernelGGL(ts_pair_k<true>, grid, dim3(kTsThreads), 0, s, *a);
-  else hipLaunchKernelGGL(ts_pair_k<false>, grid, dim3(kTsThreads), 0, s, *a);
+  if (vec) hipLaunchKernelGGL(ts_pair_k<true>, grid, dim3(kPairThreads), 0, s, *a);
+  else hipLaunchKernelGGL(ts_pair_k<false>, grid, dim3(kPairThreads), 0, s, *a);
   hipLaunchKernelGGL(ts_fold_k, dim3((unsigned)ts_cdiv(N, kTsFoldThreads)), dim3(kTsFoldThreads), 0, s, *a);
   return hipGetLastError() == hipSuccess ? 0 : 9;
 }

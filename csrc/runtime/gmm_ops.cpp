@@ -9,6 +9,7 @@
 #include <stdexcept>
 
 #include "../kernels/gmm.h"
+#include "ops_common.h"
 
 namespace mdt {
 
@@ -24,12 +25,7 @@ const char* gmm_reason(int rc) {
   }
 }
 
-void gmm_rc(int rc, const char* what) {
-  if (rc == 0) return;
-  const std::string msg = std::string("mdt: ") + what + ": " + gmm_reason(rc) + " (code " + std::to_string(rc) + ")";
-  if ((rc >= 1 && rc <= 3) || rc == 5) throw std::invalid_argument(msg);
-  throw std::runtime_error(msg);
-}
+void gmm_rc(int rc, const char* what) { throw_rc(rc, what, gmm_reason(rc), rc == 4 ? 3 : 5); }
 
 bool f32_on(const at::Tensor& t, const at::Tensor& like) {
   return t.is_cuda() && t.scalar_type() == torch::kFloat32 && t.is_contiguous() && t.device() == like.device();
@@ -45,7 +41,7 @@ void gmm_domain(int64_t n, int64_t Z, int64_t K, int64_t iters, const char* what
 
 // z and ws checked, the workspace pointers set; r and ll point into ws
 GmmArgs gmm_base(const at::Tensor& z, int64_t K, const at::Tensor& ws, double reg, const char* what) {
-  TORCH_CHECK(z.is_cuda() && z.scalar_type() == torch::kFloat32 && z.dim() == 2 && z.is_contiguous(), what,
+  TORCH_CHECK(f32_mat(z), what,
               ": z must be a contiguous CUDA float32 matrix");
   const int64_t n = z.size(0), Z = z.size(1);
   gmm_domain(n, Z, K, 0, what);

@@ -11,6 +11,7 @@
 #include <tuple>
 
 #include "../kernels/kmeans.h"
+#include "ops_common.h"
 
 namespace mdt {
 
@@ -26,16 +27,7 @@ const char* km_reason(int rc) {
   }
 }
 
-void km_rc(int rc, const char* what) {
-  if (rc == 0) return;
-  const std::string msg = std::string("mdt: ") + what + ": " + km_reason(rc) + " (code " + std::to_string(rc) + ")";
-  if (rc >= 1 && rc <= 4) throw std::invalid_argument(msg);
-  throw std::runtime_error(msg);
-}
-
-bool km_f32(const at::Tensor& t, int64_t dim) {
-  return t.is_cuda() && t.scalar_type() == torch::kFloat32 && t.dim() == dim && t.is_contiguous();
-}
+void km_rc(int rc, const char* what) { throw_rc(rc, what, km_reason(rc), 4); }
 
 // The domain, before any size is computed from the arguments. nb == 0: no second set. fit: K starts from real rows.
 void km_domain(int64_t na, int64_t nb, int64_t D, int64_t K, int64_t T, bool fit, const char* what) {
@@ -47,17 +39,17 @@ void km_domain(int64_t na, int64_t nb, int64_t D, int64_t K, int64_t T, bool fit
 
 KmeansArgs km_inputs(const at::Tensor& real, const c10::optional<at::Tensor>& fake, int64_t K, int64_t T, bool fit,
                      const at::Tensor& ws, const char* what) {
-  TORCH_CHECK(real.is_cuda() && real.scalar_type() == torch::kFloat32 && real.dim() == 2 && real.is_contiguous(), what,
+  TORCH_CHECK(f32_mat(real), what,
               ": the rows must be a contiguous CUDA float32 matrix");
   const int64_t na = real.size(0), D = real.size(1), nb = fake ? fake->size(0) : 0;
   if (fake) {
-    TORCH_CHECK(km_f32(*fake, 2) && fake->device() == real.device(), what,
+    TORCH_CHECK(f32_dense(*fake, 2) && fake->device() == real.device(), what,
                 ": the second set must be a contiguous CUDA float32 matrix on the first's device");
     TORCH_CHECK(fake->size(1) == D, what, ": both sets must have the same width");
     if (nb < 2) km_rc(1, what);
   }
   km_domain(na, nb, D, K, T, fit, what);
-  TORCH_CHECK(km_f32(ws, 1) && ws.device() == real.device() &&
+  TORCH_CHECK(f32_dense(ws, 1) && ws.device() == real.device() &&
                   (uint64_t)ws.numel() >= km_layout((int)na, (int)nb, (int)D, (int)K).total,
               what, ": ws must be a contiguous CUDA float32 vector of at least kmeans_ws_numel(na, nb, D, K) elements");
   KmeansArgs a;
@@ -125,7 +117,7 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor> kmeans_ro
 std::tuple<at::Tensor, at::Tensor, at::Tensor> kmeans_assign(const at::Tensor& x, const c10::optional<at::Tensor>& y,
                                                              const at::Tensor& cent, at::Tensor ws,
                                                              const c10::optional<at::Tensor>& prev) {
-  TORCH_CHECK(km_f32(cent, 2), "kmeans_assign: the centroids must be a contiguous CUDA float32 matrix");
+  TORCH_CHECK(f32_dense(cent, 2), "kmeans_assign: the centroids must be a contiguous CUDA float32 matrix");
   KmeansArgs a = km_inputs(x, y, cent.size(0), 1, false, ws, "kmeans_assign");
   TORCH_CHECK(cent.size(1) == a.D && cent.device() == x.device(), "kmeans_assign: the centroids must have the rows' width and device");
   const int64_t n = a.na + a.nb;
@@ -149,7 +141,7 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> kmeans_assign(const at::Tensor& x
 // One update from given labels: (centroids [K, D], counts [K] int32); a cell without rows keeps its row of `cent`.
 std::tuple<at::Tensor, at::Tensor> kmeans_update(const at::Tensor& x, const at::Tensor& labels, const at::Tensor& cent,
                                                  at::Tensor ws) {
-  TORCH_CHECK(km_f32(cent, 2), "kmeans_update: the centroids must be a contiguous CUDA float32 matrix");
+  TORCH_CHECK(f32_dense(cent, 2), "kmeans_update: the centroids must be a contiguous CUDA float32 matrix");
   KmeansArgs a = km_inputs(x, c10::nullopt, cent.size(0), 1, false, ws, "kmeans_update");
   TORCH_CHECK(cent.size(1) == a.D && cent.device() == x.device(), "kmeans_update: the centroids must have the rows' width and device");
   TORCH_CHECK(labels.is_cuda() && labels.scalar_type() == torch::kInt32 && labels.dim() == 1 && labels.numel() == a.na &&

@@ -9,12 +9,11 @@
 #include <stdexcept>
 
 #include "../kernels/prdc.h"
+#include "ops_common.h"
 
 namespace mdt {
 
 namespace {
-inline int64_t align64(int64_t v) { return (v + 63) / 64 * 64; }
-
 const char* prdc_reason(int rc) {
   switch (rc) {
     case 1: return "na and nb must be in [k + 1, 32768]";
@@ -26,12 +25,7 @@ const char* prdc_reason(int rc) {
   }
 }
 
-void prdc_rc(int rc, const char* what) {
-  if (rc == 0) return;
-  const std::string msg = std::string("mdt: ") + what + ": " + prdc_reason(rc) + " (code " + std::to_string(rc) + ")";
-  if (rc >= 1 && rc <= 4) throw std::invalid_argument(msg);
-  throw std::runtime_error(msg);
-}
+void prdc_rc(int rc, const char* what) { throw_rc(rc, what, prdc_reason(rc), 4); }
 
 // The domain, before any size is computed from the arguments.
 int64_t prdc_domain(int64_t na, int64_t nb, int64_t D, int64_t k) {
@@ -42,17 +36,14 @@ int64_t prdc_domain(int64_t na, int64_t nb, int64_t D, int64_t k) {
 }
 
 // 32-bit workspace words: every segment starts on a 256-byte boundary
-struct PrdcLayout {
-  int64_t q, rad, cnt, dminx, lists, total;
+struct PrdcLayout : Segments {
+  int64_t q, rad, cnt, dminx, lists;
   PrdcLayout(int64_t rows, int64_t strips) {
-    int64_t o = 0;
-    auto seg = [&](int64_t numel) { const int64_t at = o; o = align64(o + numel); return at; };
     q = seg(rows);
     rad = seg(rows);
     cnt = seg(rows);
     dminx = seg(rows);
     lists = seg(strips * rows * kPrdcMaxK);
-    total = o;
   }
 };
 
@@ -60,10 +51,6 @@ int64_t prdc_strips_of(int64_t na, int64_t nb) { return prdc_domain(na, nb, 1, 1
 
 int64_t prdc_ws_numel(int64_t na, int64_t nb, int64_t D, int64_t k) {
   return PrdcLayout(na + nb, prdc_domain(na, nb, D, k)).total;
-}
-
-bool f32_mat(const at::Tensor& t) {
-  return t.is_cuda() && t.scalar_type() == torch::kFloat32 && t.dim() == 2 && t.is_contiguous();
 }
 }  // namespace
 

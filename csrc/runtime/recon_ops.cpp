@@ -9,6 +9,7 @@
 #include <stdexcept>
 
 #include "../kernels/recon.h"
+#include "ops_common.h"
 
 namespace mdt {
 
@@ -23,12 +24,7 @@ const char* recon_reason(int rc) {
   }
 }
 
-void recon_rc(int rc, const char* what) {
-  if (rc == 0) return;
-  const std::string msg = std::string("mdt: ") + what + ": " + recon_reason(rc) + " (code " + std::to_string(rc) + ")";
-  if (rc >= 1 && rc <= 3) throw std::invalid_argument(msg);
-  throw std::runtime_error(msg);
-}
+void recon_rc(int rc, const char* what) { throw_rc(rc, what, recon_reason(rc), 3); }
 
 // The domain, before any size is computed from the arguments -> bands.
 int64_t recon_domain(int64_t n, int64_t side) {
@@ -41,10 +37,6 @@ int64_t recon_domain(int64_t n, int64_t side) {
 int64_t recon_ws_numel(int64_t n, int64_t side) {
   const int64_t bands = recon_domain(n, side);
   return side <= kReconWaveSide ? 0 : n * bands * kReconCols;
-}
-
-bool f32_mat(const at::Tensor& t) {
-  return t.is_cuda() && t.scalar_type() == torch::kFloat32 && t.dim() == 2 && t.is_contiguous();
 }
 }  // namespace
 

@@ -10,6 +10,7 @@
 #include <stdexcept>
 
 #include "../kernels/sinkhorn.h"
+#include "ops_common.h"
 
 namespace mdt {
 
@@ -25,16 +26,7 @@ const char* sk_reason(int rc) {
   }
 }
 
-void sk_rc(int rc, const char* what) {
-  if (rc == 0) return;
-  const std::string msg = std::string("mdt: ") + what + ": " + sk_reason(rc) + " (code " + std::to_string(rc) + ")";
-  if (rc >= 1 && rc <= 4) throw std::invalid_argument(msg);
-  throw std::runtime_error(msg);
-}
-
-bool sk_f32(const at::Tensor& t, int64_t dim) {
-  return t.is_cuda() && t.scalar_type() == torch::kFloat32 && t.dim() == dim && t.is_contiguous();
-}
+void sk_rc(int rc, const char* what) { throw_rc(rc, what, sk_reason(rc), 4); }
 
 // The domain, before any size is computed from the arguments.
 void sk_domain(int64_t na, int64_t nb, int64_t D, double E, int64_t T, const char* what) {
@@ -45,13 +37,13 @@ void sk_domain(int64_t na, int64_t nb, int64_t D, double E, int64_t T, const cha
 }
 
 void sk_check_ws(const at::Tensor& ws, int64_t na, int64_t nb, const char* what) {
-  TORCH_CHECK(sk_f32(ws, 1) && (uint64_t)ws.numel() >= sk_layout((int)na, (int)nb).total, what,
+  TORCH_CHECK(f32_dense(ws, 1) && (uint64_t)ws.numel() >= sk_layout((int)na, (int)nb).total, what,
               ": ws must be a contiguous CUDA float32 vector of at least sinkhorn_ws_numel(na, nb) elements");
 }
 
 void sk_check_outs(const at::Tensor& ws, const at::Tensor& pot, const at::Tensor& out, int64_t na, int64_t nb,
                    const char* what) {
-  TORCH_CHECK(sk_f32(pot, 2) && pot.size(0) == na + nb && pot.size(1) == kSkCols && pot.device() == ws.device(), what,
+  TORCH_CHECK(f32_dense(pot, 2) && pot.size(0) == na + nb && pot.size(1) == kSkCols && pot.device() == ws.device(), what,
               ": pot must be a contiguous CUDA float32 [na + nb, ", kSkCols, "] tensor on the workspace's device");
   TORCH_CHECK(out.is_cuda() && out.scalar_type() == torch::kFloat64 && out.dim() == 1 && out.numel() == 2 &&
                   out.is_contiguous() && out.device() == ws.device(),
@@ -60,7 +52,7 @@ void sk_check_outs(const at::Tensor& ws, const at::Tensor& pot, const at::Tensor
 
 SinkhornArgs sk_inputs(const at::Tensor& real, const at::Tensor& fake, double E, int64_t T, const at::Tensor& ws,
                        const char* what) {
-  TORCH_CHECK(sk_f32(real, 2) && sk_f32(fake, 2), what, ": real and fake must be contiguous CUDA float32 matrices");
+  TORCH_CHECK(f32_dense(real, 2) && f32_dense(fake, 2), what, ": real and fake must be contiguous CUDA float32 matrices");
   TORCH_CHECK(real.size(1) == fake.size(1), what, ": real and fake must have the same width");
   TORCH_CHECK(real.device() == fake.device() && ws.device() == real.device(), what, ": all tensors must be on one device");
   const int64_t na = real.size(0), nb = fake.size(0), D = real.size(1);

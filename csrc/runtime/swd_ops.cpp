@@ -9,6 +9,7 @@
 #include <stdexcept>
 
 #include "../kernels/swd.h"
+#include "ops_common.h"
 
 namespace mdt {
 
@@ -23,16 +24,7 @@ const char* swd_reason(int rc) {
   }
 }
 
-void swd_rc(int rc, const char* what) {
-  if (rc == 0) return;
-  const std::string msg = std::string("mdt: ") + what + ": " + swd_reason(rc) + " (code " + std::to_string(rc) + ")";
-  if (rc >= 1 && rc <= 3) throw std::invalid_argument(msg);
-  throw std::runtime_error(msg);
-}
-
-bool f32_mat(const at::Tensor& t) {
-  return t.is_cuda() && t.scalar_type() == torch::kFloat32 && t.dim() == 2 && t.is_contiguous();
-}
+void swd_rc(int rc, const char* what) { throw_rc(rc, what, swd_reason(rc), 3); }
 
 // The domain, before any size is computed from the arguments.
 void swd_domain(int64_t na, int64_t nb, int64_t D, int64_t P, const char* what) {

@@ -10,12 +10,11 @@
 #include <stdexcept>
 
 #include "../kernels/two_sample.h"
+#include "ops_common.h"
 
 namespace mdt {
 
 namespace {
-inline int64_t align64(int64_t v) { return (v + 63) / 64 * 64; }
-
 const char* ts_reason(int rc) {
   switch (rc) {
     case 1: return "na and nb must be in [2, 32768]";
@@ -26,12 +25,7 @@ const char* ts_reason(int rc) {
   }
 }
 
-void ts_rc(int rc, const char* what) {
-  if (rc == 0) return;
-  const std::string msg = std::string("mdt: ") + what + ": " + ts_reason(rc) + " (code " + std::to_string(rc) + ")";
-  if (rc >= 1 && rc <= 3) throw std::invalid_argument(msg);
-  throw std::runtime_error(msg);
-}
+void ts_rc(int rc, const char* what) { throw_rc(rc, what, ts_reason(rc), 3); }
 
 // The domain, before any size is computed from the arguments.
 int64_t ts_domain(int64_t na, int64_t nb, int64_t D) {
@@ -41,15 +35,12 @@ int64_t ts_domain(int64_t na, int64_t nb, int64_t D) {
 }
 
 // float32 workspace: every segment starts on a 256-byte boundary
-struct TwoSampleLayout {
-  int64_t q, part, tpart, total;
+struct TwoSampleLayout : Segments {
+  int64_t q, part, tpart;
   TwoSampleLayout(int64_t rows, int64_t strips) {
-    int64_t o = 0;
-    auto seg = [&](int64_t numel) { const int64_t at = o; o = align64(o + numel); return at; };
     q = seg(rows);
     part = seg(strips * rows * kTsCols);
     tpart = seg((int64_t)ts_toffsets(rows) * rows * kTsCols);
-    total = o;
   }
 };
 
@@ -57,10 +48,6 @@ int64_t two_sample_strips(int64_t na, int64_t nb) { return ts_domain(na, nb, 1);
 
 int64_t two_sample_ws_numel(int64_t na, int64_t nb, int64_t D) {
   return TwoSampleLayout(na + nb, ts_domain(na, nb, D)).total;
-}
-
-bool f32_mat(const at::Tensor& t) {
-  return t.is_cuda() && t.scalar_type() == torch::kFloat32 && t.dim() == 2 && t.is_contiguous();
 }
 }  // namespace
 

@@ -6,46 +6,29 @@ time is the maximum over all ranks."""
 from __future__ import annotations
 
 from .objective import NAMES
+from .sample_scores import REPORTS
 
 __all__ = ["trial_record", "summarize"]
 
 LATENT_KEYS = ("kl", "active_units", "mi", "tc", "dwkl")
 # per-trial scores of the after-trial passes (``TrialResult.extra``); None where the pass did not run
 SCORES = ("iw_nll", "latent", "test_loss_raw")
-SAMPLE_KEYS = ("mmd2", "nn_acc", "nn_acc_real", "nn_acc_fake")
-PRDC_KEYS = ("k", "precision", "recall", "density", "coverage")
-SWD_KEYS = ("dirs", "swd1", "swd1_se", "swd2", "max_w1")
-SINKHORN_KEYS = ("blur", "iters", "scale", "sinkhorn", "w2", "ot", "marg_err")
-NDB_KEYS = ("K", "iters", "ndb", "ndb_over_k", "jsd", "missing", "inertia", "moved")
-GMM_KEYS = ("k", "iters", "rows_fit", "ll_fit", "ll_test", "lp_test", "gap", "min_weight")
-RECON_KEYS = ("mse", "psnr", "ssim", "ssim_l", "ssim_cs", "ssim_min")
 
 
 def trial_record(result, opts) -> dict:
     """One rank's record of one trial it took part in."""
     rec = dict(group_id=result.group_id, samples=result.samples, wall_s=result.wall_s, failed=result.failed,
                **{k: result.extra.get(k) for k in SCORES})
-    if opts.sample_report > 0:  # only then: the default record stays what it was
-        rec["sample_report"] = result.extra.get("sample_report")
-    if opts.prdc_k > 0:
-        rec["prdc"] = result.extra.get("prdc")
-    if opts.recon_report:
-        rec["recon_report"] = result.extra.get("recon_report")
-    if opts.swd_dirs > 0:
-        rec["swd"] = result.extra.get("swd")
-    if opts.gmm_k > 0:
-        rec["gmm"] = result.extra.get("gmm")
-    if opts.sinkhorn_blur > 0:
-        rec["sinkhorn"] = result.extra.get("sinkhorn")
-    if opts.ndb_k > 0:
-        rec["ndb"] = result.extra.get("ndb")
+    for rep in REPORTS:
+        if getattr(opts, rep.field) > 0:  # only then: the default record stays what it was
+            rec[rep.key] = result.extra.get(rep.key)
     return rec
 
 
 def summarize(gathered, specs, opts) -> dict:
     """``gathered``: per rank, the list of its ``trial_record``s (None or empty: an idle rank)."""
     per_trial, wall, failed = {}, 0.0, set()
-    scores = {k: {} for k in SCORES + ("sample_report", "prdc", "recon_report", "swd", "gmm", "sinkhorn", "ndb")}
+    scores = {k: {} for k in SCORES + tuple(rep.key for rep in REPORTS)}
     for lst in gathered:
         for r in lst or []:
             gid = r["group_id"]
@@ -84,43 +67,7 @@ def summarize(gathered, specs, opts) -> dict:
         for g, v in latent.items():  # trials with a KL floor: the dimensions it holds up
             if "below_floor" in v:
                 summary["latent"][str(g)]["below_floor"] = v["below_floor"]
-    if opts.sample_report > 0:
-        # prior samples against test rows: the lowest kernel MMD is the best trial; 1-NN accuracy 0.5 is ideal
-        samples = scores["sample_report"]
-        summary["sample_rows"] = opts.sample_report
-        summary["sample_report"] = {str(g): {k: round(v[k], 6) for k in SAMPLE_KEYS} for g, v in sorted(samples.items())}
-        summary["best_trial_by_mmd2"] = (min(samples, key=lambda g: (samples[g]["mmd2"], g)) if samples else None)
-    if opts.prdc_k > 0:
-        # fidelity (precision, density) and diversity (recall, coverage) on k-NN radii: four numbers, no single order
-        summary["prdc"] = {str(g): {k: (v[k] if k == "k" else round(v[k], 6)) for k in PRDC_KEYS}
-                           for g, v in sorted(scores["prdc"].items())}
-    if opts.recon_report:
-        # test images against their reconstructions from the posterior mean: the largest mean SSIM is the best trial
-        recon = scores["recon_report"]
-        summary["recon_report"] = {str(g): {k: round(v[k], 6) for k in RECON_KEYS} for g, v in sorted(recon.items())}
-        summary["best_trial_by_ssim"] = (min(recon, key=lambda g: (-recon[g]["ssim"], g)) if recon else None)
-    if opts.swd_dirs > 0:
-        # a distance in the units of the data with its Monte-Carlo error over the directions: the lowest is the best trial
-        w = scores["swd"]
-        summary["swd"] = {str(g): {k: (v[k] if k == "dirs" else round(v[k], 6)) for k in SWD_KEYS} for g, v in sorted(w.items())}
-        summary["best_trial_by_swd"] = min(w, key=lambda g: (w[g]["swd1"], g)) if w else None
-    if opts.gmm_k > 0:
-        # samples of the fitted mixture against the same test rows: the order by MMD with the prior hole taken out
-        m = scores["gmm"]
-        summary["gmm"] = {str(g): dict({k: (v[k] if k in ("k", "iters", "rows_fit") else round(v[k], 6)) for k in GMM_KEYS},
-                                       **{k: round(v["sample_report"][k], 6) for k in SAMPLE_KEYS})
-                          for g, v in sorted(m.items())}
-        summary["best_trial_by_gmm_mmd2"] = min(m, key=lambda g: (m[g]["sample_report"]["mmd2"], g)) if m else None
-    if opts.sinkhorn_blur > 0:
-        # the debiased entropic transport distance in the squared units of the data: the lowest is the best trial
-        w = scores["sinkhorn"]
-        summary["sinkhorn"] = {str(g): {k: (v[k] if k in ("blur", "iters") else float(f"{v[k]:.6g}")) for k in SINKHORN_KEYS}
-                               for g, v in sorted(w.items())}
-        summary["best_trial_by_sinkhorn"] = min(w, key=lambda g: (w[g]["sinkhorn"], g)) if w else None
-    if opts.ndb_k > 0:
-        # mode coverage on k-means bins of the test rows: the lowest divergence of the two histograms is the best trial
-        w = scores["ndb"]
-        summary["ndb"] = {str(g): {k: (float(f"{v[k]:.6g}") if k in ("ndb_over_k", "jsd", "inertia") else v[k]) for k in NDB_KEYS}
-                          for g, v in sorted(w.items())}
-        summary["best_trial_by_ndb_jsd"] = min(w, key=lambda g: (w[g]["jsd"], g)) if w else None
+    for rep in REPORTS:  # the sample pass and the scores that ride on it, the recon pass (hpo/sample_scores.py)
+        if getattr(opts, rep.field) > 0:
+            rep.summarize(scores[rep.key], summary, opts)
     return summary

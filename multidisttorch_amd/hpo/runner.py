@@ -48,6 +48,7 @@ from ..runtime.bootstrap import bound_device, global_barrier
 from ..runtime.faults import (InjectedFault, TrialCorrupted, TrialTimeout, agree_healthy, fault_step, group_timeout_s, guarded,
                               heartbeat_s, maybe_inject, trial_watch)
 from ..utils.images import flush_images, save_image_async
+from . import sample_scores
 from .objective import KNOBS, NAMES
 from .schedule import LR_DECAYS, Schedule
 from .trial import TrialSpec
@@ -496,24 +497,14 @@ def _sample_eval(trainer, test, opts: RunOptions, group, metrics, device, tag: s
     t = time.perf_counter()
     idx = torch.arange(n, dtype=torch.int32, device=test.data.device)
     with trace.range("sample_eval"), trainer.averaged_weights():
-        k = int(opts.prdc_k)
-        # the default call stays the call it was
-        kw = dict(prdc_k=k) if k > 0 else {}
-        P = int(opts.swd_dirs)
-        if P > 0:
-            kw["swd_dirs"] = P
+        kw = {}
+        for score in sample_scores.SCORES:  # a score that is off adds no keyword: the default call stays the call it was
+            kw.update(score.kwargs(opts, metrics))
         G = int(opts.gmm_k)
         if G > 0:
             # the mixture is fitted to codes of the rows the trial trained on
             Xf, fidx = trainer._data[0], trainer._data[1]
             kw.update(gmm_k=G, gmm_iters=int(opts.gmm_iters), fit_rows=(Xf, fidx[:MAX_GMM_ROWS]))
-        E = float(opts.sinkhorn_blur)
-        if E > 0:
-            kw.update(sinkhorn_blur=E, sinkhorn_iters=int(opts.sinkhorn_iters))
-        B = int(opts.ndb_k)
-        if B > 0:
-            # the starting rows of the bins come from the run seed and the trial: both backends see the same indices
-            kw.update(ndb=B, ndb_iters=int(opts.ndb_iters), ndb_group=int(metrics.group_id))
         r = trainer.evaluate_samples(test.data, idx, n, **kw)
         if device.type == "cuda":
             torch.cuda.synchronize(device)
@@ -521,47 +512,20 @@ def _sample_eval(trainer, test, opts: RunOptions, group, metrics, device, tag: s
     print0(tag + "====> Test set samples: MMD2 {:.6f} 1-NN acc {:.4f} (real {:.4f} gen {:.4f})".format(
         r["mmd2"], r["nn_acc"], r["nn_acc_real"], r["nn_acc_fake"]), process_group=group)
     out = dict(sample_report=r)
-    if k > 0:
-        p = r["prdc"]
-        print0(tag + "====> Test set PRDC-{}: precision {:.4f} recall {:.4f} density {:.4f} coverage {:.4f}".format(
-            p["k"], p["precision"], p["recall"], p["density"], p["coverage"]), process_group=group)
-        out["prdc"] = p
-    if P > 0:
-        w = r["swd"]
-        print0(tag + "====> Test set SWD-{}: W1 {:.6f} +- {:.6f} W2 {:.6f} max {:.6f}".format(
-            w["dirs"], w["swd1"], w["swd1_se"], w["swd2"], w["max_w1"]), process_group=group)
-        out["swd"] = w
-    sink_line = "Sinkhorn-{:g}: S {:.6f} W2 {:.6f} OT {:.6f} marg err {:.3e} ({} iters)"
-    if E > 0:
-        w = r["sinkhorn"]
-        print0(tag + "====> Test set " + sink_line.format(w["blur"], w["sinkhorn"], w["w2"], w["ot"], w["marg_err"], w["iters"]),
-               process_group=group)
-        out["sinkhorn"] = w
-    ndb_line = "NDB-{}: ndb {} ({:.3f}) JSD {:.4f} missing {} inertia {:.6g} moved {} ({} iters)"
-    ndb_args = lambda w: (w["K"], w["ndb"], w["ndb_over_k"], w["jsd"], w["missing"], w["inertia"], w["moved"], w["iters"])
-    if B > 0:
-        print0(tag + "====> Test set " + ndb_line.format(*ndb_args(r["ndb"])), process_group=group)
-        out["ndb"] = r["ndb"]
+
+    def lines(result, name=""):  # the scores the pass has added to ``result``, in the table's order
+        for score in sample_scores.SCORES:
+            if score.key in result:
+                print0(tag + "====> Test set " + name + score.format(result[score.key]), process_group=group)
+
+    lines(r)
+    out.update({key: r[key] for key in sample_scores.KEYS if key in r})
     if G > 0:
         g = r["gmm"]
         gs = g["sample_report"]
-        name = "GMM-{} ".format(g["k"])
         print0(tag + "====> Test set GMM-{}: ll {:.4f} prior {:.4f} gap {:.4f} MMD2 {:.6f} 1-NN acc {:.4f}".format(
             g["k"], g["ll_test"], g["lp_test"], g["gap"], gs["mmd2"], gs["nn_acc"]), process_group=group)
-        if k > 0:
-            p = g["prdc"]
-            print0(tag + "====> Test set " + name + "PRDC-{}: precision {:.4f} recall {:.4f} density {:.4f} coverage {:.4f}"
-                   .format(p["k"], p["precision"], p["recall"], p["density"], p["coverage"]), process_group=group)
-        if P > 0:
-            w = g["swd"]
-            print0(tag + "====> Test set " + name + "SWD-{}: W1 {:.6f} +- {:.6f} W2 {:.6f} max {:.6f}".format(
-                w["dirs"], w["swd1"], w["swd1_se"], w["swd2"], w["max_w1"]), process_group=group)
-        if E > 0:
-            w = g["sinkhorn"]
-            print0(tag + "====> Test set " + name + sink_line.format(w["blur"], w["sinkhorn"], w["w2"], w["ot"], w["marg_err"],
-                                                                    w["iters"]), process_group=group)
-        if B > 0:
-            print0(tag + "====> Test set " + name + ndb_line.format(*ndb_args(g["ndb"])), process_group=group)
+        lines(g, "GMM-{} ".format(g["k"]))
         out["gmm"] = g
     metrics.log(event="sample_eval", **r)
     return out

@@ -383,57 +383,39 @@ class SampleEval:
         mean_pair_d2, bandwidths, mmd2, mmd2_per_bandwidth, nn_acc, nn_acc_real,
         nn_acc_fake, nn_dist_real_to_fake, nn_dist_fake_to_real, rf_asym)``;
         with ``return_rows`` also ``table`` (float32 ``[rows_real + rows_fake,
-        8]``), ``real`` and ``fake``. ``prdc_k > 0`` adds ``prdc = dict(k,
-        precision, recall, density, coverage)`` of the same rows on k-NN radii
-        (models/prdc.py; csrc/kernels/prdc.hip on the hip backend), with
-        ``return_rows`` also ``prdc_table`` (float32 ``[rows_real + rows_fake,
-        3]``). ``swd_dirs > 0`` adds ``swd = dict(dirs, swd1, swd1_se, swd2,
-        max_w1)``, the sliced Wasserstein distance of the same rows over that
-        many random directions (models/swd.py; csrc/kernels/swd.hip on the hip
-        backend), with ``return_rows`` also ``swd_table`` (float32 ``[dirs,
-        2]``: w1, w2sq) and ``swd_proj`` (float32 ``[dirs, rows_real +
-        rows_fake]``: per direction the sorted real | the sorted generated
-        projections). ``sinkhorn_blur > 0`` adds ``sinkhorn = dict(blur, iters,
-        scale, sinkhorn, w2, ot, marg_err)``, the debiased entropic transport
-        distance of the same rows after ``sinkhorn_iters`` annealed iterations
-        at that blur, a fraction of the real rows' mean squared distance
-        (models/sinkhorn.py; csrc/kernels/sinkhorn.hip on the hip backend), with
-        ``return_rows`` also ``sinkhorn_pot`` (float32 ``[rows_real + rows_fake,
-        2]``: the pair's and the debiasing potentials). ``ndb > 0`` adds ``ndb =
-        dict(K, iters, ndb, ndb_over_k, jsd, missing, inertia, moved,
-        counts_real, counts_fake)``: the real rows clustered into that many
-        k-means cells by ``ndb_iters`` Lloyd iterations from rows that the seed
-        and ``ndb_group`` pick, the number of cells whose real and generated
-        shares differ significantly, the Jensen-Shannon divergence of the two
-        histograms and the cells without a generated row (models/ndb.py;
-        csrc/kernels/kmeans.hip on the hip backend), with ``return_rows`` also
-        ``ndb_labels`` (``[rows_real + rows_fake]``) and ``ndb_centroids``. ``gmm_k > 0`` (with ``fit_rows=(X_train, idx_train)``)
-        adds ``gmm = dict(k, iters, rows_fit, ll_fit, ll_history, ll_test,
-        lp_test, gap, min_weight, sample_report[, prdc][, swd][, sinkhorn][, ndb])``: a
-        ``gmm_k``-component mixture fitted by ``gmm_iters`` EM iterations to one
-        posterior draw per fit row (models/gmm.py; csrc/kernels/gmm.hip on the hip
-        backend), the mean log-density of the rows' own codes under it and under
-        N(0, I) with their difference ``gap``, and the same tables a second time
-        for decoded draws from the mixture; with ``return_rows`` also
-        ``gmm_params``, ``gmm_fake``, ``gmm_fit_z`` and ``gmm_test_z``. That part
-        runs on the latent pass's state, so ``latent_buffers()`` raises until the
-        next ``evaluate_latent``. Training, eval and iw state are not touched; the
-        result depends on (weights, data, seed, n, directions, mixture, blur,
-        iterations) only."""
+        8]``), ``real`` and ``fake``. ``prdc_k``, ``swd_dirs``, ``sinkhorn_blur``
+        (with ``sinkhorn_iters``) and ``ndb`` (with ``ndb_iters`` and
+        ``ndb_group``, which with the seed picks the bins' starting rows) above 0
+        each add one score of the same rows under its key, and with
+        ``return_rows`` its tables; ``gmm_k > 0`` (with ``gmm_iters`` and
+        ``fit_rows=(X_train, idx_train)``) adds ``gmm``: a mixture fitted to one
+        posterior draw per fit row, the scored rows' log-density under it and
+        under N(0, I), and the same tables and scores a second time for decoded
+        draws from it. docs/SAMPLE_SCORES.md lists every score's result keys.
+        The mixture part runs on the latent pass's state, so ``latent_buffers()``
+        raises until the next ``evaluate_latent``. Training, eval and iw state are
+        not touched; the result depends on (weights, data, seed, n, directions,
+        mixture, blur, iterations) only."""
         idx = idx.to(device=self.device, dtype=torch.int64).contiguous()
         na = idx.numel()
         nb = na if n_samples is None else int(n_samples)
         real = X[idx].to(self.device, torch.float32).reshape(na, -1).contiguous()
         D = real.shape[1]
         check_sample_args(na, nb, D)
+        scores = {}  # key -> the parameter its function of _SCORE_TABLES takes
         if prdc_k:
             check_prdc_args(na, nb, D, prdc_k)
+            scores["prdc"] = int(prdc_k)
         if swd_dirs:
             check_swd_args(na, nb, D, swd_dirs)
+            scores["swd"] = int(swd_dirs)
         if sinkhorn_blur:
             check_sinkhorn_args(na, nb, D, sinkhorn_blur, sinkhorn_iters)
+            scores["sinkhorn"] = (float(sinkhorn_blur), int(sinkhorn_iters))
         if ndb:
             check_ndb_args(na, nb, D, ndb, ndb_iters)
+            # the bins are fitted to the real rows once: the mixture's draws are assigned to the same centroids
+            scores["ndb"] = dict(K=int(ndb), T=int(ndb_iters), init=ndb_init_idx(na, ndb, self.seed, ndb_group))
         if gmm_k:
             if fit_rows is None:
                 raise ValueError("evaluate_samples(gmm_k=K) fits the mixture to training rows: pass fit_rows=(X, idx)")
@@ -443,16 +425,15 @@ class SampleEval:
         h = bandwidths_of(m)
         z = torch.from_numpy(sample_z(nb, self.Z, self.seed)).to(self.device)
         fake = self.decode(z).to(torch.float32).reshape(nb, -1).contiguous()
-        sink = (float(sinkhorn_blur), int(sinkhorn_iters)) if sinkhorn_blur else None
-        # the bins are fitted to the real rows once: the mixture's draws are assigned to the same centroids
-        bins = dict(K=int(ndb), T=int(ndb_iters), init=ndb_init_idx(na, ndb, self.seed, ndb_group)) if ndb else None
-        out = self._sample_tables(real, fake, m, h, prdc_k, swd_dirs, return_rows, sink, bins)
+        out = self._sample_tables(real, fake, m, h, scores, return_rows)
         if gmm_k:
-            out.update(self._gmm_report(X, idx, real, nb, m, h, prdc_k, swd_dirs, int(gmm_k), int(gmm_iters), fit_rows,
-                                        return_rows, sink, bins))
+            out.update(self._gmm_report(X, idx, real, nb, m, h, scores, int(gmm_k), int(gmm_iters), fit_rows, return_rows))
         return out
 
-    def _sample_tables(self, real, fake, m, h, prdc_k, swd_dirs, return_rows, sink=None, bins=None) -> dict:
+    def _new(self, *shape, dtype=torch.float32):
+        return torch.empty(*shape, dtype=dtype, device=self.device)
+
+    def _sample_tables(self, real, fake, m, h, scores, return_rows) -> dict:
         """The tables of ``evaluate_samples`` for ``fake`` against ``real`` and their statistics."""
         (na, D), nb = real.shape, fake.shape[0]
         if self.backend != "hip":
@@ -460,67 +441,70 @@ class SampleEval:
         else:
             C = native.require()
             # the workspace grows with (na + nb)^2 / 32 (58 MB at 20000 rows): it lives for this pass only
-            ws = torch.empty(C.two_sample_ws_numel(na, nb, D), dtype=torch.float32, device=self.device)
-            table = torch.empty(na + nb, COLS, dtype=torch.float32, device=self.device)
-            C.two_sample_rows(real, fake, list(h), ws, table)
+            table = self._new(na + nb, COLS)
+            C.two_sample_rows(real, fake, list(h), self._new(C.two_sample_ws_numel(na, nb, D)), table)
         out = dict(rows_real=na, rows_fake=nb, mean_pair_d2=m, bandwidths=list(h), **sample_stats(table, na, nb))
         if return_rows:
             out.update(table=table, real=real, fake=fake)
-        if prdc_k:
-            k = int(prdc_k)
-            if self.backend != "hip":
-                ptable = prdc_rows(real, fake, k, chunk=max(1, self.SAMPLE_CHUNK_ELEMS // (max(na, nb) * D)))
-            else:
-                ws = torch.empty(C.prdc_ws_numel(na, nb, D, k), dtype=torch.float32, device=self.device)
-                ptable = torch.empty(na + nb, PRDC_COLS, dtype=torch.float32, device=self.device)
-                C.prdc_rows(real, fake, k, ws, ptable)
-            out["prdc"] = prdc_stats(ptable, na, nb, k)
-            if return_rows:
-                out["prdc_table"] = ptable
-        if swd_dirs:
-            P = int(swd_dirs)
-            dirs = torch.from_numpy(swd_directions(P, D, self.seed)).to(self.device)
-            if self.backend != "hip":
-                sproj, stable = swd_rows(real, fake, dirs)
-            else:
-                sproj = torch.empty(P, na + nb, dtype=torch.float32, device=self.device)
-                stable = torch.empty(P, SWD_COLS, dtype=torch.float32, device=self.device)
-                C.swd_rows(real, fake, dirs, sproj, stable)
-            out["swd"] = swd_stats(stable)
-            if return_rows:
-                out.update(swd_table=stable, swd_proj=sproj)
-        if sink:
-            E, T = sink
-            if self.backend != "hip":
-                spot, scale, merr = sinkhorn_rows(real, fake, E, T)
-            else:
-                new = lambda numel, dtype=torch.float32: torch.empty(numel, dtype=dtype, device=self.device)
-                # the three stored cost matrices: 4 (na^2 + na nb + nb^2) bytes (1.2 GB at 20000 rows), for this pass only
-                spot, sout = new((na + nb) * SINKHORN_COLS).view(na + nb, SINKHORN_COLS), new(2, torch.float64)
-                C.sinkhorn_rows(real, fake, E, T, new(C.sinkhorn_ws_numel(na, nb)), spot, sout)
-                scale, merr = sout.cpu()
-            out["sinkhorn"] = sinkhorn_stats(spot, na, scale, merr, E, T)
-            if return_rows:
-                out["sinkhorn_pot"] = spot
-        if bins:
-            K, T = bins["K"], bins["T"]
-            if self.backend == "hip":
-                ws = torch.empty(C.kmeans_ws_numel(na, nb, D, K), dtype=torch.float32, device=self.device)
-            if "cent" not in bins:
-                init = bins["init"].to(self.device)
-                if self.backend != "hip":
-                    labels, _, cent, moved, inertia = kmeans_rows(real, fake, K, T, init)
-                else:
-                    labels, _, cent, moved, inertia = C.kmeans_rows(real, fake, K, T, init, ws)
-                bins.update(cent=cent, moved=int(moved[-1]), inertia=float(inertia))
-            elif self.backend != "hip":
-                labels = kmeans_assign(torch.cat([real, fake]), bins["cent"])[0]
-            else:
-                labels = C.kmeans_assign(real, fake, bins["cent"], ws)[0]
-            out["ndb"] = ndb_stats(labels, na, K, bins["inertia"], bins["moved"], T)
-            if return_rows:
-                out.update(ndb_labels=labels, ndb_centroids=bins["cent"])
+        for key, param in scores.items():
+            out[key], rows = self._SCORE_TABLES[key](self, real, fake, param, return_rows)
+            out.update(rows)
         return out
+
+    # One function per score of hpo/sample_scores.py: (real, fake, param, return_rows) -> (stats, extra rows)
+
+    def _prdc_tables(self, real, fake, k, return_rows):
+        (na, D), nb = real.shape, fake.shape[0]
+        if self.backend != "hip":
+            table = prdc_rows(real, fake, k, chunk=max(1, self.SAMPLE_CHUNK_ELEMS // (max(na, nb) * D)))
+        else:
+            C = native.require()
+            table = self._new(na + nb, PRDC_COLS)
+            C.prdc_rows(real, fake, k, self._new(C.prdc_ws_numel(na, nb, D, k)), table)
+        return prdc_stats(table, na, nb, k), dict(prdc_table=table) if return_rows else {}
+
+    def _swd_tables(self, real, fake, P, return_rows):
+        (na, D), nb = real.shape, fake.shape[0]
+        dirs = torch.from_numpy(swd_directions(P, D, self.seed)).to(self.device)
+        if self.backend != "hip":
+            proj, table = swd_rows(real, fake, dirs)
+        else:
+            proj, table = self._new(P, na + nb), self._new(P, SWD_COLS)
+            native.require().swd_rows(real, fake, dirs, proj, table)
+        return swd_stats(table), dict(swd_table=table, swd_proj=proj) if return_rows else {}
+
+    def _sinkhorn_tables(self, real, fake, sink, return_rows):
+        na, nb, (E, T) = real.shape[0], fake.shape[0], sink
+        if self.backend != "hip":
+            pot, scale, merr = sinkhorn_rows(real, fake, E, T)
+        else:
+            C = native.require()
+            # the three stored cost matrices: 4 (na^2 + na nb + nb^2) bytes (1.2 GB at 20000 rows), for this pass only
+            pot, sout = self._new(na + nb, SINKHORN_COLS), self._new(2, dtype=torch.float64)
+            C.sinkhorn_rows(real, fake, E, T, self._new(C.sinkhorn_ws_numel(na, nb)), pot, sout)
+            scale, merr = sout.cpu()
+        return sinkhorn_stats(pot, na, scale, merr, E, T), dict(sinkhorn_pot=pot) if return_rows else {}
+
+    def _ndb_tables(self, real, fake, bins, return_rows):
+        (na, D), nb, K, T = real.shape, fake.shape[0], bins["K"], bins["T"]
+        if self.backend == "hip":
+            C = native.require()
+            ws = self._new(C.kmeans_ws_numel(na, nb, D, K))
+        if "cent" not in bins:  # the first call fits the bins; a later one (the mixture's draws) assigns to them
+            init = bins["init"].to(self.device)
+            if self.backend != "hip":
+                labels, _, cent, moved, inertia = kmeans_rows(real, fake, K, T, init)
+            else:
+                labels, _, cent, moved, inertia = C.kmeans_rows(real, fake, K, T, init, ws)
+            bins.update(cent=cent, moved=int(moved[-1]), inertia=float(inertia))
+        elif self.backend != "hip":
+            labels = kmeans_assign(torch.cat([real, fake]), bins["cent"])[0]
+        else:
+            labels = C.kmeans_assign(real, fake, bins["cent"], ws)[0]
+        rows = dict(ndb_labels=labels, ndb_centroids=bins["cent"]) if return_rows else {}
+        return ndb_stats(labels, na, K, bins["inertia"], bins["moved"], T), rows
+
+    _SCORE_TABLES = dict(prdc=_prdc_tables, swd=_swd_tables, sinkhorn=_sinkhorn_tables, ndb=_ndb_tables)
 
     def _gmm_codes(self, X, idx, step: int) -> torch.Tensor:
         """One posterior draw per row of ``X[idx]`` (``gmm_fit_rows``), through the latent pass's encoder loop."""
@@ -535,8 +519,7 @@ class SampleEval:
         self._lat_last = None  # the pass buffer no longer holds an evaluate_latent pass
         return gmm_fit_rows(mulv[:, :Z], mulv[:, Z:], self.seed, step).contiguous()
 
-    def _gmm_report(self, X, idx, real, nb, m, h, prdc_k, swd_dirs, K, iters, fit_rows, return_rows, sink=None,
-                    bins=None) -> dict:
+    def _gmm_report(self, X, idx, real, nb, m, h, scores, K, iters, fit_rows, return_rows) -> dict:
         zf, zt = self._gmm_codes(fit_rows[0], fit_rows[1], 1), self._gmm_codes(X, idx, 2)
         (nf, Z), nt = zf.shape, zt.shape[0]
         if self.backend != "hip":
@@ -552,8 +535,8 @@ class SampleEval:
             C.gmm_score(zt, params["pi"], params["mu"], params["cov"], new(C.gmm_ws_numel(nt, Z, K)), ll)
         ll_test, lp_test = float(ll.double().mean()), float(prior_score(zt.double()).mean())
         gfake = self.decode(gmm_sample(params, nb, self.seed).to(self.device)).to(torch.float32).reshape(nb, -1).contiguous()
-        rep = self._sample_tables(real, gfake, m, h, prdc_k, swd_dirs, False, sink, bins)
-        extra = {k: rep.pop(k) for k in ("prdc", "swd", "sinkhorn", "ndb") if k in rep}
+        rep = self._sample_tables(real, gfake, m, h, scores, False)
+        extra = {k: rep.pop(k) for k in scores}
         hist = [float(v) for v in hist.double().cpu()]
         gmm = dict(k=K, iters=iters, rows_fit=nf, ll_fit=hist[-1], ll_history=hist, ll_test=ll_test, lp_test=lp_test,
                    gap=ll_test - lp_test, min_weight=float(params["pi"].min()), sample_report=rep, **extra)

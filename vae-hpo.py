@@ -41,7 +41,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from utils import *  # noqa: F401,F403  (reference-compatible API + re-exports)
 
 from multidisttorch_amd.data.binarize import BINARIZE_CHOICES
-from multidisttorch_amd.hpo import objective
+from multidisttorch_amd.hpo import objective, sample_scores
 from multidisttorch_amd.hpo.aggregate import summarize, trial_record
 from multidisttorch_amd.hpo.runner import RunOptions, idle_rank, run_packed_trials, run_trial
 from multidisttorch_amd.hpo.trial import build_specs, parse_list
@@ -116,62 +116,22 @@ def parse_args(argv=None):
     parser.add_argument("--sample-report", type=int, default=0, metavar="N",
                         help="after each trial's last epoch: kernel MMD and 1-NN two-sample test between N decoded "
                              "prior samples and the first N test rows (a score of the samples themselves; 0 = off)")
-    parser.add_argument("--prdc", type=int, default=0, metavar="K",
-                        help="with --sample-report N: also precision, recall, density and coverage of the same rows "
-                             "on K-nearest-neighbour radii (fidelity against diversity; 1 <= K <= 8 < N; 0 = off)")
-    parser.add_argument("--swd", type=int, default=0, metavar="P",
-                        help="with --sample-report N: also the sliced Wasserstein distance of the same rows over P "
-                             "random unit directions, with its standard error (a distance in the units of the data; "
-                             "2 <= N <= 16384, 1 <= P <= 4096; 0 = off)")
     parser.add_argument("--gmm", type=int, default=0, metavar="K",
                         help="with --sample-report N: also fit a K-component full-covariance Gaussian mixture to latent "
                              "codes of the training rows, report the test codes' log-density under it against N(0, I), "
                              "and score N decoded draws from it with the same tables (1 <= K <= 32; 0 = off)")
     parser.add_argument("--gmm-iters", type=int, default=50, metavar="T",
                         help="EM iterations of the --gmm fit (a fixed count, 0 <= T <= 1000)")
-    parser.add_argument("--sinkhorn", type=float, default=0.0, metavar="E",
-                        help="with --sample-report N: also the Sinkhorn divergence (debiased entropic optimal transport) "
-                             "of the same rows at blur E, a fraction of the test rows' mean squared distance: a "
-                             "full-dimensional transport distance in the squared units of the data "
-                             "(2 <= N <= 16384, 0 < E <= 4; 0 = off)")
-    parser.add_argument("--sinkhorn-iters", type=int, default=100, metavar="T",
-                        help="annealed iterations of --sinkhorn (a fixed count, 1 <= T <= 10000)")
-    parser.add_argument("--ndb", type=int, default=0, metavar="K",
-                        help="with --sample-report N: also which kinds of image are missing: the N test rows are "
-                             "clustered into K k-means bins in pixel space, and the number of bins whose real and "
-                             "generated shares differ significantly (NDB), the Jensen-Shannon divergence of the two "
-                             "histograms and the bins without a generated row are reported (2 <= K <= 256, K <= N; 0 = off)")
-    parser.add_argument("--ndb-iters", type=int, default=20, metavar="T",
-                        help="Lloyd iterations of the --ndb bins (a fixed count, 1 <= T <= 1000)")
+    for score in sample_scores.SCORES:  # --prdc, --swd, --sinkhorn, --ndb and their -iters (hpo/sample_scores.py)
+        for flag in score.flags:
+            parser.add_argument(flag.name, type=flag.type, default=flag.default, metavar=flag.metavar, help=flag.help)
     parser.add_argument("--recon-report", action="store_true",
                         help="after each trial's last epoch: per-pixel MSE, PSNR and SSIM (with its luminance and "
                              "contrast-structure factors) of the test images against their reconstructions from the "
                              "posterior mean: the distortion, comparable across a --beta sweep")
     args = parser.parse_args(argv)
-    if args.prdc != 0:
-        from multidisttorch_amd.models.prdc import check_prdc_args
-
-        if args.sample_report == 0:
-            raise ValueError("--prdc K scores the rows of the sample pass: it needs --sample-report N")
-        check_prdc_args(args.sample_report, args.sample_report, 1, args.prdc)
-    if args.swd != 0:
-        from multidisttorch_amd.models.swd import check_swd_args
-
-        if args.sample_report == 0:
-            raise ValueError("--swd P scores the rows of the sample pass: it needs --sample-report N")
-        check_swd_args(args.sample_report, args.sample_report, 1, args.swd)
-    if args.sinkhorn != 0:
-        from multidisttorch_amd.models.sinkhorn import check_sinkhorn_args
-
-        if args.sample_report == 0:
-            raise ValueError("--sinkhorn E scores the rows of the sample pass: it needs --sample-report N")
-        check_sinkhorn_args(args.sample_report, args.sample_report, 1, args.sinkhorn, args.sinkhorn_iters)
-    if args.ndb != 0:
-        from multidisttorch_amd.models.ndb import check_ndb_args
-
-        if args.sample_report == 0:
-            raise ValueError("--ndb K bins the rows of the sample pass: it needs --sample-report N")
-        check_ndb_args(args.sample_report, args.sample_report, 1, args.ndb, args.ndb_iters)
+    for score in sample_scores.SCORES:
+        score.check_args(args)
     if args.gmm != 0:
         from multidisttorch_amd.models.gmm import check_gmm_args
 
@@ -228,9 +188,8 @@ def main(argv=None):
                       profile=args.profile, iw_samples=max(0, args.iw_samples), latent_report=args.latent_report,
                       au_threshold=args.au_threshold, binarize=args.binarize,
                       report_objective=objective.reported(specs), sample_report=args.sample_report,
-                      prdc_k=args.prdc, recon_report=args.recon_report, swd_dirs=args.swd,
-                      gmm_k=args.gmm, gmm_iters=args.gmm_iters, sinkhorn_blur=args.sinkhorn,
-                      sinkhorn_iters=args.sinkhorn_iters, ndb_k=args.ndb, ndb_iters=args.ndb_iters)
+                      recon_report=args.recon_report, gmm_k=args.gmm, gmm_iters=args.gmm_iters,
+                      **{flag.field: getattr(args, flag.dest) for score in sample_scores.SCORES for flag in score.flags})
     results = []
     member = False
     for group_id, group in enumerate(processes_groups):
